@@ -12,10 +12,16 @@ runs its non-logging steps: replayed as captured hipGraphs (stove_amd/graphed.py
 Workload (BASELINE.json configs[1]): 3-object billiards, 32x32, T=100, batch 256 per GPU (weak scaling), frames from the
 build's numpy simulator, model with default initialisation; the colour fp32 frames -- what the reference's loader hands to
 Stove.forward -- are resident in HBM before the timed region and bw_transform runs inside every step.
-Rank 0 prints ONE JSON line (contract in the task statement): `roofline` is measured with HIP events around the dominant
-kernel, `cpu_baseline` times the CPU oracle on a bounded sample, `variants` holds the other BASELINE.json configurations
-(gravity, avoidance, multibilliards per-GPU shards; the cfg-1 evaluation protocol; Stove.rollout alone), each with its own
-roofline block and its ELBO difference against the reference's number on the matching golden fixture.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = wall time of the timed region over --steps); nothing else runs on the device or the host.
+--full adds the side measurements after the timed region: `roofline` is measured with HIP events around the dominant
+kernel, `comm` times the all-reduce of the gradient bucket, `cpu_baseline` times the CPU oracle on a bounded sample,
+`variants` holds the other BASELINE.json configurations (gravity, avoidance, multibilliards per-GPU shards; the cfg-1
+evaluation protocol; Stove.rollout alone), each with its own roofline block and its ELBO difference against the reference's
+number on the matching golden fixture, and `reference_parity` the headline path's own.  Without --full these fields are null.
+--dump-outputs DIR writes what the last timed step computed (rank 0): elbo.npy (float64, the value the step returns),
+params.npy (float32, the flat parameter arena after its update) and grads.npy (float32, its flat gradient).  Data, model
+initialisation and noise are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -69,6 +75,11 @@ def parse():
     p.add_argument('--step-mode', default='graph', choices=['graph', 'eager'],
                    help='graph (default): the step replayed as captured hipGraph(s), as Trainer.train runs its non-logging steps '
                         '(stove_amd/graphed.py); eager: every launch enqueued by the host (reported as a variant)')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed region, also run the side measurements (kernel profile / roofline, all-reduce probe, variants, '
+                        'reference parity, CPU baseline; each still subject to its --no-* / --profile-steps switch)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the outputs of the last timed step as DIR/<name>.npy (elbo, params, grads)')
     return p.parse_args()
 
 
@@ -332,6 +343,16 @@ class Job:
 
     def step(self, i):
         return self.graph_step(i) if self.step_mode == 'graph' else self.eager_step(i)
+
+    def dump_outputs(self, out_dir, elbo):
+        """What the last step handed its caller: the ELBO, the updated flat parameters and the flat gradient behind the update."""
+        os.makedirs(out_dir, exist_ok=True)
+        arrays = {'elbo': np.array([float(elbo.detach())], dtype=np.float64),
+                  'params': self.bucket.data.detach().float().cpu().numpy(),
+                  'grads': self.bucket.grad.detach().float().cpu().numpy()}
+        assert sum(v.nbytes for v in arrays.values()) <= 64 << 20, 'outputs exceed 64 MB'
+        for name, v in arrays.items():
+            np.save(os.path.join(out_dir, name + '.npy'), v)
 
     def snapshot(self):
         return (self.bucket.data.clone(), {k: v.clone() for k, v in self.opt._flat.items()}, self.opt._seg_steps.clone())
@@ -648,7 +669,7 @@ def main():
                 raise SystemExit('libstove_hip.so was not built by local rank 0 within 10 minutes')
             time.sleep(0.5)
     # ---- synthetic data, BEFORE the GPU is touched (the simulators run in a pool of forked workers)
-    side = rank == 0 and world == 1 and not a.no_variants and a.res == 32
+    side = a.full and rank == 0 and world == 1 and not a.no_variants and a.res == 32
     workers = max(1, min(64, _cores() // max(1, world)))
     log('generating data (%d workers)' % workers)
     data = make_batch(a.workload, a.batch, a.frames, rank * a.batch, a.res, workers)
@@ -657,7 +678,7 @@ def main():
         for w in ('gravity', 'avoidance', 'multibilliards'):
             side_data[w] = make_batch(w, a.batch, a.frames, 0, 32, workers)
     cpu_small = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.res == 32:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.res == 32:
         cpu_small = make_batch(a.workload, a.cpu_batch, a.frames, 10 ** 6, 32, workers)
     log('data ready')
     if not torch.cuda.is_available():
@@ -733,11 +754,14 @@ def main():
     if os.environ.get('STOVE_BENCH_SERIES'):
         log('device ms per step: ' + ' '.join('%.3f' % v for v in series))
         log('host ms per step:   ' + ' '.join('%.3f' % ((host_t[i + 1] - host_t[i]) * 1e3) for i in range(a.steps)))
+    if a.dump_outputs and rank == 0:
+        job.dump_outputs(a.dump_outputs, last)          # before any side measurement trains the model further
+        log('outputs written to %s' % a.dump_outputs)
 
     # ---- per-kernel HIP-event timing of extra steps (profiling hooks off during the timed region); every rank runs the extra
     # steps (they contain the collective), only rank 0 records events
     roofline = None
-    if a.profile_steps > 0:
+    if a.full and a.profile_steps > 0:
         from stove_amd import ops as _ops
         prof_w = job.kernel_profile(a.profile_steps, record=rank == 0, first_index=a.warmup + a.steps)
         prof_serial = None
@@ -747,15 +771,16 @@ def main():
         if rank == 0:
             roofline = make_roofline(prof_w, prof_serial, cfg.num_obj, a.batch, a.frames, a.profile_steps, a.encoder_gemm)
             attach_traffic(roofline, a.workload, a.batch, a.frames)
-    log('kernel profile done')
+        log('kernel profile done')
     # ---- data parallel: what the collective costs by itself (HIP events around the all-reduce of the flat gradient, the stream
     # otherwise idle) and what RCCL says about the group, so that a multi-GPU line explains itself.  N = 1: a dry run of the same
     # call through a one-rank RCCL group (the path the 8-GPU run takes, minus the wire).
     comm = None
-    try:
-        comm = comm_probe(bucket, dev, world, rank)
-    except Exception as exc:
-        comm = {'error': repr(exc)}
+    if a.full:
+        try:
+            comm = comm_probe(bucket, dev, world, rank)
+        except Exception as exc:
+            comm = {'error': repr(exc)}
     # ---- side measurements (N = 1 only).  Never the headline `value`.
     variants = None
     if side:
@@ -829,7 +854,7 @@ def main():
             guarded(w, lambda w=w: workload_variant(dev, w, side_data[w], a))
         log('variants done')
     parity = None
-    if rank == 0 and not os.environ.get('STOVE_BENCH_NO_PARITY'):
+    if a.full and rank == 0 and not os.environ.get('STOVE_BENCH_NO_PARITY'):
         try:
             parity = reference_parity(dev, a.workload, a.encoder_gemm)
         except Exception as exc:

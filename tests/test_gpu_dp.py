@@ -355,7 +355,7 @@ def test_bench_eight_ranks_over_gloo_on_one_gpu():
     env = dict(os.environ, STOVE_DIST_BACKEND='gloo', STOVE_BENCH_NO_PARITY='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('WORLD_SIZE', None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--batch', '16', '--steps', '4', '--warmup', '2',
-           '--no-variants', '--no-cpu-baseline', '--profile-steps', '0']
+           '--full', '--no-variants', '--no-cpu-baseline', '--profile-steps', '0']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

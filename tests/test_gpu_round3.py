@@ -125,6 +125,38 @@ def test_bench_refuses_mismatched_world():
     assert res.returncode != 0 and 'WORLD_SIZE' in (res.stderr + res.stdout)
 
 
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, leaves every side measurement out of its line, and
+    --dump-outputs writes the last timed step's ELBO, parameters and gradient; two runs with the same arguments agree."""
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    runs = []
+    for tag in ('a', 'b'):
+        out_dir = str(tmp_path / tag)
+        res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '8',
+                              '--frames', '12', '--dump-outputs', out_dir], env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, res.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['unit'] == 'frames/s' and out['higher_is_better'] is True and out['dtype'].startswith('f32')
+        assert out['metric'].startswith('frames/s') and out['ms_per_step'] > 0
+        assert abs(out['value'] - 8 * 12 / out['ms_per_step'] * 1e3) < 1e-6 * out['value']
+        for k in ('roofline', 'cpu_baseline', 'variants', 'comm', 'reference_parity', 'elbo_rel_vs_reference'):
+            assert out[k] is None, k
+        arrays = {n: np.load(os.path.join(out_dir, n + '.npy')) for n in ('elbo', 'params', 'grads')}
+        assert arrays['elbo'].dtype == np.float64 and arrays['params'].dtype == np.float32 and arrays['grads'].dtype == np.float32
+        assert arrays['params'].shape == arrays['grads'].shape and arrays['params'].size > 0
+        assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in os.listdir(out_dir)) <= 64 << 20
+        assert all(np.isfinite(v).all() for v in arrays.values())
+        assert float(arrays['elbo'][0]) == out['config']['elbo_last_step']
+        assert np.abs(arrays['grads']).max() > 0
+        runs.append(arrays)
+    for n in runs[0]:
+        np.testing.assert_array_equal(runs[0][n], runs[1][n], err_msg=n)
+
+
 def test_grad_view_registry_follows_the_live_arena():
     """ops._GRAD_VIEWS is keyed on parameter objects: a replaced arena's views are not written any more, the new arena gets the
     recognition network's gradients, and torch.autograd.grad on an arena-bound weight still returns its gradient."""

@@ -22,5 +22,5 @@ rm -rf $OUT/ks $OUT/fetch $OUT/write $OUT/sq
 # the bench line quotes roofline.traffic from profiles/*pmc_traffic.json (source-hash checked): make this run's summary the one it finds
 cp $OUT/pmc_traffic.json $R/profiles/${TAG}_pmc_traffic.json
 unset STOVE_BENCH_NO_PARITY
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.log
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.log
 tail -c 900 $OUT/bench.json

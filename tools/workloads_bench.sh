@@ -5,7 +5,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for w in gravity avoidance multibilliards; do
-  timeout 400 python3 bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-variants > $OUT/bench_$w.json 2> $OUT/bench_$w.log
+  timeout 400 python3 bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-variants > $OUT/bench_$w.json 2> $OUT/bench_$w.log
   tail -c 300 $OUT/bench_$w.json | head -c 0
 done
 bash tools/kernel_times.sh > $OUT/kernel_times.txt 2>&1
