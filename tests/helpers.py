@@ -88,3 +88,38 @@ def source_index(z, zm, tol=1e-6):
     eq = ((zm.unsqueeze(3) - z.unsqueeze(2)).abs() < tol).all(-1)
     assert bool((eq.sum(-1) == 1).all()), 'a matched row is not exactly one source row'
     return eq.long().argmax(-1)
+
+
+def replica_index(n, K, seed=0):
+    """src[row] = the distinct item (0 .. K-1) that row `row` of an n-row batch holds: item k on ceil / floor(n / K) rows (exactly
+    R rows for n = K R), placed by a fixed random permutation.  The placement has no period and no block structure, so a kernel that
+    reads row r +- s or row r mod m instead of row r reads another item on nearly every row (tests/test_batch_replication_cpu.py)."""
+    g = np.random.default_rng(seed)
+    return np.arange(n, dtype=np.int64)[g.permutation(n)] % K
+
+
+def replica_counts(src, K):
+    """how many rows hold each item: the factor of an item's share of a batch-summed gradient"""
+    return np.bincount(np.asarray(src), minlength=K)
+
+
+def oracle_stove(cfg, x, eps, actions=None, regime='analytic', dtype=torch.float64):
+    """The float64 oracle's training step on one batch: loss = -ELBO (+ 3 mean(rewards^2) with actions, a batch mean like the ELBO,
+    so that the loss of a replicated batch is the loss of its distinct sequences) -> dict(elbo, rewards, info, grads)."""
+    c, structs, params = oracle_setup(dtype, regime=regime, **cfg)
+    act = actions.to(dtype) if actions is not None else None
+    eps = {'latent': eps['latent'].to(dtype), 'std': eps['std'].to(dtype), 'steps': [e.to(dtype) for e in eps['steps']]}
+    elbo, rewards, info = O.stove_forward(c, params, structs, x.to(dtype), eps, act, detail=True)
+    loss = -elbo
+    if act is not None:
+        loss = loss + 3.0 * (rewards ** 2).mean()
+    loss.backward()
+    return {'c': c, 'params': params, 'elbo': elbo.detach(), 'rewards': rewards.detach() if act is not None else None,
+            'info': {k: (v.detach() if torch.is_tensor(v) else v) for k, v in info.items()},
+            'grads': {k: p.grad for k, p in params.items() if p.grad is not None}}
+
+
+def replicate_eps(eps, src):
+    """the oracle's noise draws (O.draw_eps) of K sequences, row b of the result = row src[b]"""
+    idx = torch.as_tensor(np.asarray(src))
+    return {'latent': eps['latent'][idx], 'std': eps['std'][idx], 'steps': [e[idx] for e in eps['steps']]}

@@ -32,8 +32,9 @@ PRESET = {'n3': 'billiards', 'grav3': 'gravity', 'n6': 'multibilliards', 'ac3': 
 @pytest.mark.parametrize('name', list(CASES))
 def test_T100_golden_inside_the_full_size_batch(name):
     """BASELINE's own shape (256 sequences x 100 frames: 25 600 encoder rows in two row chunks, one workgroup per sequence in the
-    recursion, the streamed per-step gradient workspace) with the two golden sequences as rows 0-1 and 77-78 of the batch: every
-    per-sequence output of those rows must be the reference's -- sequences are independent, so a long-T or large-B
+    recursion, the streamed per-step gradient workspace) with the two golden sequences as rows 0-1, 77-78, 200-201 (in the second
+    encoder row chunk) and 254-255 of the batch: every per-sequence output of those rows must be the reference's -- sequences are
+    independent, so a long-T or large-B
     indexing error anywhere in the path shows up here against the reference itself, not only against a property."""
     from stove_amd.arena import ParamArena
     from stove_amd.envs import envs
@@ -47,7 +48,7 @@ def test_T100_golden_inside_the_full_size_batch(name):
     data = {k: np.concatenate([v] * (B // 32), 0) for k, v in data.items()}
     x = torch.from_numpy(data['X']).float()
     gx = t_(gold['x']).float()
-    rows = [0, 1, 77, 78]
+    rows = [0, 1, 77, 78, 200, 201, 254, 255]          # (rows 128 and up: the second encoder row chunk, on the side stream)
     g = torch.Generator().manual_seed(5)
     noise = {'latent': torch.randn(B, N, 12, generator=g), 'std': torch.randn(B, N, 12, generator=g), 'steps': torch.randn(B, T - 2, N, 18, generator=g)}
     gn = {'latent': t_(gold['eps_lat'])[..., 0].float(), 'std': t_(gold['eps_std'])[..., 0].float(),
@@ -66,15 +67,18 @@ def test_T100_golden_inside_the_full_size_batch(name):
     assert np.isfinite(float(elbo))
     for k, bar in (('z', 3e-6), ('z_dyn', 3e-6), ('z_sup', 8e-6)):
         got = prop[k][rows]
-        ref = np.concatenate([gold['p_' + k], gold['p_' + k]], 0)
+        ref = np.concatenate([gold['p_' + k]] * (len(rows) // 2), 0)
         check('stoveT100.full_batch.' + k, err(got, ref), bar)
-        assert torch.equal(got[0], got[2]) and torch.equal(got[1], got[3])          # same sequence, another row: same bits
+        for j in range(2, len(rows)):
+            assert torch.equal(got[j], got[j % 2]), (k, rows[j])          # same sequence, another row: same bits
     if rewards is not None and actions is not None:
-        check('stoveT100.full_batch.rewards', err(rewards[rows], np.concatenate([gold['rewards'], gold['rewards']], 0)), 1e-6)
+        check('stoveT100.full_batch.rewards', err(rewards[rows], np.concatenate([gold['rewards']] * (len(rows) // 2), 0)), 1e-6)
     with torch.no_grad():
         zp, _ = st.rollout(prop['z'][:, -1], num=92, actions=actions[:, :5].to(DEV) if actions is not None else None,
                            appearance=prop['obj_appearances'][:, -1] if actions is not None else None)
-    check('stoveT100.full_batch.rollout_z', err(zp[rows], np.concatenate([gold['roll_z'], gold['roll_z']], 0)), 3e-6)
+    check('stoveT100.full_batch.rollout_z', err(zp[rows], np.concatenate([gold['roll_z']] * (len(rows) // 2), 0)), 3e-6)
+    for j in range(2, len(rows)):
+        assert torch.equal(zp[rows[j]], zp[rows[j % 2]]), rows[j]
 
 
 @pytest.mark.parametrize('name', ['n3', 'n6'])

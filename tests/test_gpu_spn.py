@@ -221,7 +221,7 @@ def test_scene_backward_with_parameter_stream(n_obj):
     extra = {'debug_match_objects': 'greedy'} if n_obj != 3 else {}
     c, structs, params, sup = _supair_pair(n_obj, **extra)
     g = torch.Generator().manual_seed(5 + n_obj)
-    nf = 363                                             # 17 / 34 ragged 64-glimpse batches
+    nf = 5462                                            # 16 386 / 32 772 glimpses (>= kLateTableGradGlimpses), ragged 64-glimpse batches
     frames = (torch.rand(nf, 1024, generator=g) ** 2).to(DEV)
     z = torch.zeros(nf, n_obj, 4)
     z[..., 0] = 0.1 + 0.6 * torch.rand(nf, n_obj, generator=g)
@@ -282,9 +282,9 @@ def test_scene_glimpse_kernel(n_obj):
 
 @pytest.mark.parametrize('n_obj,nf', [(3, 64), (3, 2301), (6, 130), (4, 77), (8, 40), (2, 50), (1, 9)])
 def test_glimpse_tile_kernel_lds_staging_is_bit_identical(n_obj, nf):
-    """scene_tile_fwd_lds_k (a batch's frames staged in LDS, taps as LDS gathers; round 6) against scene_tile_fwd_k (global gathers; the
-    kernel the goldens were first met with): glimpses and keep-weights bit for bit -- ragged last batches, objects leaving the frame,
-    every object count, and n_obj < 3 (a batch spans more frames than the LDS holds: the launcher falls back to the gather kernel)."""
+    """scene_tile_fwd_t_k (stove_set_tile_lds mode 2: lane = pixel, the tile transposed through LDS, for every object count) against
+    scene_tile_fwd_k (mode 0: lane = glimpse, global gathers; the kernel the goldens were first met with): glimpses and keep-weights
+    bit for bit -- ragged last batches, objects leaving the frame, every object count."""
     from stove_amd import _lib
     lib = _lib.load()
     g = torch.Generator().manual_seed(nf + n_obj)
