@@ -162,6 +162,25 @@ int stove_scene_fwd_any(const StoveSpnTables* t, const float* frames, const floa
 int stove_scene_bwd_any(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames,
                         int seq_stride, int W, int H, int align_corners, float overlap_beta, const float* saved, const float* dll,
                         float* dz, StoveSpnTableGrads* g, void* ws, void* stream, void* param_stream);
+/* The same likelihood over `channels` colour planes (1..4; reference supair.py:44-110 with config.channels = 3, debug_bw = False).
+ * frames: rows of channels*W*H floats in (c, W-major plane) order; glimpses of pw x ph pixels (patch_width x patch_height) in either
+ * sampling convention.  The object SPN is the general-size one of stove_objspn_fwd_any over D = channels*pw*ph dimensions (its tables
+ * and limits, R, G, S, D, Lmax); the background tables are bg_side [3][channels*W*H], bg_coef [3][channels*W*H][6][3] (bg_coef_floats
+ * floats), bg_wroot [3][36].  The occlusion mask is the same in every channel.  saved / ws sizes below; dz in `stream` order, the table
+ * gradients (overwritten) complete in `param_stream` order (NULL = `stream`).  hipErrorInvalidValue for channels outside 1..4,
+ * D != channels*pw*ph, bg_coef_floats != 3*channels*W*H*6*3, n_obj outside 1..8, object-SPN shapes past the limits above, null
+ * pointers.  with_grad: accepted for symmetry with stove_scene_fwd_any (the saved activations are the same). */
+size_t stove_scene_saved_floats_ch(int n_frames, int n_obj, int channels, int W, int H, int R, int G, int S, int D, int Lmax, int with_grad);
+size_t stove_scene_bwd_ws_bytes_ch(int n_frames, int n_obj, int channels, int W, int H, int R, int G, int S, int D, int Lmax);
+int stove_scene_fwd_ch(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
+                       int D, int Lmax, const int32_t* bg_side, const float* bg_coef, const float* bg_wroot, size_t bg_coef_floats,
+                       const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride, int channels, int W, int H,
+                       int pw, int ph, int align_corners, float overlap_beta, float* ll, float* parts, float* saved, void* stream, int with_grad);
+int stove_scene_bwd_ch(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
+                       int D, int Lmax, const int32_t* bg_side, const float* bg_coef, const float* bg_wroot, size_t bg_coef_floats,
+                       const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride, int channels, int W, int H,
+                       int pw, int ph, int align_corners, float overlap_beta, const float* saved, const float* dll, float* dz, float* g_coef,
+                       float* g_wsum, float* g_wroot, float* g_bg_coef, float* g_bg_wroot, void* ws, void* stream, void* param_stream);
 /* The same with the stream the internal background-SPN chain forks from given explicitly (NULL = `stream`).  For callers that run the
  * scene calls on a stream which is itself a fork inside a hipGraph capture: pass the capture's origin stream, where frames, z, saved
  * and dll must then be ready (the HIP 7.0 runtime cannot end a capture in which two forked streams wait on each other). */

@@ -11,7 +11,7 @@ from . import settings as _settings
 
 LIB_PATH = _settings.LIB_OVERRIDE or os.path.join(_HERE, 'libstove_hip.so')
 _lib = None
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 EXPORTS = [
     'stove_abi_version', 'stove_error_string', 'stove_selftest_wave_sum',
@@ -28,6 +28,7 @@ EXPORTS = [
     'stove_reward_head_param_floats', 'stove_reward_head_saved_floats', 'stove_reward_head_bwd_ws_floats', 'stove_reward_head_fwd',
     'stove_bgspn_saved_floats_d', 'stove_bgspn_fwd_d', 'stove_bgspn_bwd_ws_bytes_d', 'stove_bgspn_bwd_d', 'stove_noise_normal', 'stove_set_overlap', 'stove_set_tile_lds', 'stove_event_list_begin', 'stove_event_list_end', 'stove_event_list_destroy', 'stove_fill_words',
     'stove_reward_head_bwd', 'stove_small_linear', 'stove_set_fork_stream', 'stove_scene_fwd_from', 'stove_scene_fwd_floats', 'stove_gauss_ll_fwd', 'stove_gauss_ll_bwd', 'stove_objspn_saved_floats_any', 'stove_objspn_bwd_ws_bytes_any', 'stove_objspn_fwd_any', 'stove_objspn_bwd_any', 'stove_scene_saved_floats_any', 'stove_scene_bwd_ws_bytes_any', 'stove_scene_fwd_any', 'stove_scene_bwd_any', 'stove_scene_bwd_from',
+    'stove_scene_saved_floats_ch', 'stove_scene_bwd_ws_bytes_ch', 'stove_scene_fwd_ch', 'stove_scene_bwd_ch',
 ]
 
 
@@ -83,6 +84,10 @@ def _declare(lib):
         'stove_scene_bwd_ws_bytes_any': (S, [I, I, I]),
         'stove_scene_fwd_any': (I, [T, P, P, I, I, I, I, I, I, I, F, P, P, P, P, I]),
         'stove_scene_bwd_any': (I, [T, P, P, I, I, I, I, I, I, I, F, P, P, P, G, P, P, P]),
+        'stove_scene_saved_floats_ch': (S, [I] * 11),
+        'stove_scene_bwd_ws_bytes_ch': (S, [I] * 10),
+        'stove_scene_fwd_ch': (I, [P] * 5 + [I] * 5 + [P, P, P, S, P, P] + [I] * 10 + [F, P, P, P, P, I]),
+        'stove_scene_bwd_ch': (I, [P] * 5 + [I] * 5 + [P, P, P, S, P, P] + [I] * 10 + [F] + [P] * 11),
         'stove_scene_glimpses': (I, [P, P, I, I, P, P, P, P]),
         'stove_gnn_param_floats': (S, []),
         'stove_gnn_grad_floats': (S, []),

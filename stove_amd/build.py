@@ -45,7 +45,7 @@ def build_library(force=False, verbose=False):
     cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
            '-Wno-unused-value', '-o', LIB] + [os.path.join(CSRC, s) for s in SOURCES]
     if verbose:
-        print(' '.join(cmd))
+        print(' '.join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         sys.stderr.write(res.stdout + res.stderr)

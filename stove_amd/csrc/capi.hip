@@ -22,6 +22,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "spn_bg_generic.hip"
 #include "scene.hip"
 #include "scene_fused.hip"
+#include "scene_colour.hip"
 #include "gnn.hip"
 #include "match.hip"
 #include "gnn_small.hip"
@@ -152,7 +153,11 @@ extern "C" {
 // 3: stove_profile_report lines carry a fourth column, the time the kernel's launches cover.
 // 4 (round 5): stove_gemm_bf16 takes nsplit = 3 (half pieces); the A/B entry points whose losing side is recorded are gone
 //    (stove_set_tablegrad_placement, stove_lstm_cell_bwd_rows).
-int stove_abi_version(void) { return 5; }
+// 5: the scene likelihood and the object SPN for any frame size, glimpse size and vector widths (stove_scene_*_any,
+//    stove_objspn_*_any), the fixed-Gaussian debug models (stove_gauss_ll_*), stove_scene_bwd_from.
+// 6: the scene likelihood over 1 to 4 colour channels (stove_scene_saved_floats_ch, stove_scene_bwd_ws_bytes_ch, stove_scene_fwd_ch,
+//    stove_scene_bwd_ch).
+int stove_abi_version(void) { return 6; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
 
@@ -609,8 +614,8 @@ int stove_scene_bwd_any(const StoveSpnTables* t, const float* frames, const floa
   int rc = bgspn_any_backward(frames, inl ? nullptr : saved + L.mask, t->bg_side, t->bg_coef, t->bg_wroot, saved + L.bg_ell, saved + L.bg_out, dll,
                               nullptr, ws + Wl.d_mask, g->bg_coef, g->bg_wroot, ws + Wl.bg, n_frames, n_pix, sb, fm, boxes);
   if (rc) return rc;
-  if (n_obj <= 3) STOVE_LAUNCH((bg_mask_bwd_any_k<3>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm);
-  else STOVE_LAUNCH((bg_mask_bwd_any_k<8>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm);
+  if (n_obj <= 3) STOVE_LAUNCH((bg_mask_bwd_any_k<3>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, 1);
+  else STOVE_LAUNCH((bg_mask_bwd_any_k<8>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, 1);
   STOVE_LAUNCH_CHECK();
   // object chain: pixel / transformer backward from the unit-gradient scratch, then the per-object sums with dz_bg
   const float* d_obj = ws + Wl.d_obj;
@@ -630,6 +635,168 @@ int stove_scene_bwd_any(const StoveSpnTables* t, const float* frames, const floa
   STOVE_TRY(stream_after(sp, st));
   rc = objspn_backward_params(saved + L.xw, t->obj_scope, g->obj_coef, g->obj_wsum, g->obj_wroot, saved + L.obj_scratch, ws + Wl.obj, ws + Wl.d_obj, np, sp);
   if (rc) return rc;
+  jp.dismiss();
+  return 0;
+}
+
+// ---------------------------------------------------------------- fused scene likelihood over C colour channels
+// Glimpses and masks of every channel in one pass (scene_colour_fwd_k), the general-size object SPN on C * pw * ph dimensions, the
+// general-size background SPN on C * W * H dimensions with one mask plane for all channels; backward: the object SPN's data and table
+// gradients, the glimpse backward to z (scene_colour_bwd_k), the background's mask backward with the C planes summed.
+// saved = [ patches | marg | object-SPN saved | obj_ll | ovl | bg_out | bg_ell | mask (frames past kBgTabMax a side) ]
+// the colour kernels come in two object-count instantiations (3 and 8: the 6-object one ran at the 8-object one's occupancy); dzc has
+// nmax_ch(n_obj) entries per glimpse
+static inline int nmax_ch(int n_obj) { return n_obj <= 3 ? 3 : 8; }
+struct SceneSavedCh {
+  size_t patches, marg, obj, obj_ll, ovl, bg_out, bg_ell, mask, total;
+};
+static SceneSavedCh scene_saved_layout_ch(int nf, int n_obj, int C, int W, int H, const ObjAnyShape& sh) {
+  const size_t np = (size_t)nf * n_obj;
+  SceneSavedCh s;
+  s.patches = 0;
+  s.marg = s.patches + align64(np * sh.D);
+  s.obj = s.marg + align64(np * sh.D);
+  s.obj_ll = s.obj + align64(objany_saved_floats((int)np, sh));
+  s.ovl = s.obj_ll + align64(np);
+  s.bg_out = s.ovl + align64(np);
+  s.bg_ell = s.bg_out + align64(nf);
+  s.mask = s.bg_ell + align64(bgspn_any_saved_floats(nf, C * W * H));
+  s.total = s.mask + (scene_any_inline(W, H) ? 0 : align64((size_t)nf * W * H));
+  return s;
+}
+// ws = [ d_obj | d_ovl | dzc | dz_bg | d_patch | d_marg | object-SPN ws | d_mask (C planes) | background ws ]
+struct SceneWsCh {
+  size_t d_obj, d_ovl, dzc, dz_bg, d_patch, d_marg, obj, d_mask, bg, total;
+};
+static SceneWsCh scene_ws_layout_ch(int nf, int n_obj, int C, int W, int H, const ObjAnyShape& sh) {
+  const size_t np = (size_t)nf * n_obj, n_pix = (size_t)C * W * H;
+  SceneWsCh s;
+  s.d_obj = 0;
+  s.d_ovl = s.d_obj + align64(np);
+  s.dzc = s.d_ovl + align64(np);
+  s.dz_bg = s.dzc + align64(np * nmax_ch(n_obj) * 4);
+  s.d_patch = s.dz_bg + align64(np * 4);
+  s.d_marg = s.d_patch + align64(np * sh.D);
+  s.obj = s.d_marg + align64(np * sh.D);
+  s.d_mask = s.obj + align64(objany_bwd_ws_floats((int)np, sh));
+  s.bg = s.d_mask + align64((size_t)nf * n_pix);
+  s.total = s.bg + align64(bgspn_any_bwd_ws_floats(nf, (int)n_pix));
+  return s;
+}
+static GlimpseGeom glimpse_geom(int pw, int ph, int align_corners) {
+  GlimpseGeom g;
+  g.pw = pw; g.ph = ph;
+  if (align_corners) {
+    g.pax = 2.0f / (ph - 1); g.pbx = -1.0f; g.pay = 2.0f / (pw - 1); g.pby = -1.0f;
+  } else {
+    g.pax = 2.0f / ph; g.pbx = 1.0f / ph - 1.0f; g.pay = 2.0f / pw; g.pby = 1.0f / pw - 1.0f;
+  }
+  return g;
+}
+size_t stove_scene_saved_floats_ch(int n_frames, int n_obj, int channels, int W, int H, int R, int G, int S, int D, int Lmax, int with_grad) {
+  (void)with_grad;                // the object SPN's saved activations are the same with and without a backward to come
+  return scene_saved_layout_ch(n_frames, n_obj, channels, W, H, obj_any_shape(R, G, S, D, Lmax)).total;
+}
+size_t stove_scene_bwd_ws_bytes_ch(int n_frames, int n_obj, int channels, int W, int H, int R, int G, int S, int D, int Lmax) {
+  return scene_ws_layout_ch(n_frames, n_obj, channels, W, H, obj_any_shape(R, G, S, D, Lmax)).total * sizeof(float);
+}
+
+int stove_scene_fwd_ch(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
+                       int D, int Lmax, const int32_t* bg_side, const float* bg_coef, const float* bg_wroot, size_t bg_coef_floats,
+                       const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride, int channels, int W, int H,
+                       int pw, int ph, int align_corners, float overlap_beta, float* ll, float* parts, float* saved, void* stream, int with_grad) {
+  (void)slot;
+  (void)with_grad;
+  STOVE_VALIDATE(scene_ch_fwd(lscope, coef, wsum, wroot, R, G, S, D, Lmax, bg_side, bg_coef, bg_wroot, bg_coef_floats, frames, z, n_frames, n_obj,
+                              seq_frames, seq_stride, channels, W, H, pw, ph, ll, saved));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_frames == 0) return 0;
+  FrameMap fm;
+  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
+  const ObjAnyShape sh = obj_any_shape(R, G, S, D, Lmax);
+  const int plane = W * H, n_pix = channels * plane, np = n_frames * n_obj;
+  const SceneGeom gm = scene_geom(W, H, align_corners);
+  const GlimpseGeom gg = glimpse_geom(pw, ph, align_corners);
+  const bool inl = scene_any_inline(W, H);
+  const SceneSavedCh L = scene_saved_layout_ch(n_frames, n_obj, channels, W, H, sh);
+  SceneBoxes boxes;
+  boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
+  hipStream_t sb = scene_fork_stream(st);
+  STOVE_TRY(stream_after(sb, st));
+  JoinGuard jb(st, sb);
+  // object chain: glimpses + masks of every channel, the object SPN over C * pw * ph dimensions
+  int rc = n_obj <= 3 ? scene_colour_fwd<3>(frames, z, saved + L.patches, saved + L.marg, saved + L.ovl, n_obj, np, channels, st, fm, gm, gg)
+                      : scene_colour_fwd<8>(frames, z, saved + L.patches, saved + L.marg, saved + L.ovl, n_obj, np, channels, st, fm, gm, gg);
+  if (rc) return rc;
+  rc = objany_forward(saved + L.patches, saved + L.marg, lscope, coef, wsum, wroot, saved + L.obj, saved + L.obj_ll, np, sh, st);
+  if (rc) return rc;
+  // background chain: one mask plane for the C channels
+  if (!inl) {
+    const size_t tot = (size_t)n_frames * plane;
+    STOVE_LAUNCH(bg_mask_any_k, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sb, z, saved + L.mask, n_frames, n_obj, gm);
+    STOVE_LAUNCH_CHECK();
+  }
+  rc = bgspn_any_forward(frames, inl ? nullptr : saved + L.mask, bg_side, bg_coef, bg_wroot, saved + L.bg_ell, saved + L.bg_out, n_frames, n_pix, sb,
+                         fm, boxes, plane);
+  if (rc) return rc;
+  STOVE_TRY(jb.join());
+  STOVE_LAUNCH(scene_assemble_fwd_k, dim3((n_frames + 255) / 256), dim3(256), 0, st, saved + L.bg_out, saved + L.obj_ll,
+               saved + L.ovl, z, ll, parts, n_obj, n_frames, overlap_beta, logf(overlap_beta));
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+int stove_scene_bwd_ch(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
+                       int D, int Lmax, const int32_t* bg_side, const float* bg_coef, const float* bg_wroot, size_t bg_coef_floats,
+                       const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride, int channels, int W, int H,
+                       int pw, int ph, int align_corners, float overlap_beta, const float* saved, const float* dll, float* dz, float* g_coef,
+                       float* g_wsum, float* g_wroot, float* g_bg_coef, float* g_bg_wroot, void* ws_, void* stream, void* param_stream) {
+  STOVE_VALIDATE(scene_ch_bwd(lscope, slot, coef, wsum, wroot, R, G, S, D, Lmax, bg_side, bg_coef, bg_wroot, bg_coef_floats, frames, z, n_frames,
+                              n_obj, seq_frames, seq_stride, channels, W, H, pw, ph, saved, dll, dz, g_coef, g_wsum, g_wroot, g_bg_coef, g_bg_wroot,
+                              ws_));
+  hipStream_t st = (hipStream_t)stream;
+  hipStream_t sp = param_stream != nullptr ? (hipStream_t)param_stream : st;
+  if (n_frames == 0) return 0;
+  FrameMap fm;
+  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
+  float* ws = (float*)ws_;
+  const ObjAnyShape sh = obj_any_shape(R, G, S, D, Lmax);
+  const int plane = W * H, n_pix = channels * plane, np = n_frames * n_obj;
+  const SceneGeom gm = scene_geom(W, H, align_corners);
+  const GlimpseGeom gg = glimpse_geom(pw, ph, align_corners);
+  const bool inl = scene_any_inline(W, H);
+  const SceneSavedCh L = scene_saved_layout_ch(n_frames, n_obj, channels, W, H, sh);
+  const SceneWsCh Wl = scene_ws_layout_ch(n_frames, n_obj, channels, W, H, sh);
+  SceneBoxes boxes;
+  boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
+  STOVE_LAUNCH(scene_assemble_bwd_k, dim3((np + 255) / 256), dim3(256), 0, st, dll, z, ws + Wl.d_obj, ws + Wl.d_ovl, n_obj, np, overlap_beta);
+  STOVE_LAUNCH_CHECK();
+  hipStream_t sb = scene_fork_stream(st);
+  STOVE_TRY(stream_after(sb, st));
+  JoinGuard jb(st, sb);
+  JoinGuard jp(st, sp);
+  // background chain: operator backward (d mask of every plane, table gradients), then the mask's backward to z
+  int rc = bgspn_any_backward(frames, inl ? nullptr : saved + L.mask, bg_side, bg_coef, bg_wroot, saved + L.bg_ell, saved + L.bg_out, dll, nullptr,
+                              ws + Wl.d_mask, g_bg_coef, g_bg_wroot, ws + Wl.bg, n_frames, n_pix, sb, fm, boxes, plane);
+  if (rc) return rc;
+  if (n_obj <= 3) STOVE_LAUNCH((bg_mask_bwd_any_k<3>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, channels);
+  else STOVE_LAUNCH((bg_mask_bwd_any_k<8>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, channels);
+  STOVE_LAUNCH_CHECK();
+  // object chain: the SPN's data and table gradients, then the glimpse backward to z
+  rc = objany_backward(saved + L.patches, saved + L.marg, lscope, slot, coef, wsum, wroot, saved + L.obj, ws + Wl.d_obj, ws + Wl.d_patch,
+                       ws + Wl.d_marg, g_coef, g_wsum, g_wroot, ws + Wl.obj, np, sh, st);
+  if (rc) return rc;
+  if (n_obj <= 3)
+    rc = scene_colour_bwd<3>(frames, z, ws + Wl.d_patch, ws + Wl.d_marg, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, channels, st, fm, gm, gg);
+  else
+    rc = scene_colour_bwd<8>(frames, z, ws + Wl.d_patch, ws + Wl.d_marg, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, channels, st, fm, gm, gg);
+  if (rc) return rc;
+  STOVE_TRY(jb.join());
+  if (n_obj <= 3) STOVE_LAUNCH((scene_finalize_bwd_k<3>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
+  else STOVE_LAUNCH((scene_finalize_bwd_k<8>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
+  STOVE_LAUNCH_CHECK();
+  // every table gradient is complete in `st` order: the parameter stream is ordered behind it
+  STOVE_TRY(stream_after(sp, st));
   jp.dismiss();
   return 0;
 }

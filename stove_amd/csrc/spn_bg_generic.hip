@@ -51,7 +51,7 @@ template <int R, int G>
 __global__ __launch_bounds__(kBgThreads) void bgspn_fwd_any_k(const float* __restrict__ inputs, const float* __restrict__ marg,
                                                               const int* __restrict__ side, const float* __restrict__ coef,
                                                               float* __restrict__ ell_part, int n_frames, int n_pix, int halves, FrameMap fm,
-                                                              SceneBoxes sb) {
+                                                              SceneBoxes sb, int mask_pix) {
   constexpr int NO = R * 2 * G;
   constexpr int NW = kBgThreads / 64;
   __shared__ float part[2][NW * 4][NO];     // one partial per 16-lane row of every wave
@@ -74,14 +74,15 @@ __global__ __launch_bounds__(kBgThreads) void bgspn_fwd_any_k(const float* __res
   }
   int it = 0;
   const int fstep = gridDim.x / halves;
-  const int X = scene ? pc % sb.gm.W : 0, Y = scene ? pc / sb.gm.W : 0;
+  const int pm = pc % mask_pix;                  // the pixel's place in the mask plane (colour: C planes share one mask)
+  const int X = scene ? pm % sb.gm.W : 0, Y = scene ? pm / sb.gm.W : 0;
   if (scene && (int)(blockIdx.x / halves) < n_frames) {
     bg_fill_tables(sb, blockIdx.x / halves, tbx[0], tby[0], nullptr, nullptr);
     __syncthreads();
   }
   for (int f = blockIdx.x / halves; f < n_frames; f += fstep, ++it) {
     const float x = inputs[fm.row(f) * n_pix + pc];
-    float w = (marg != nullptr) ? 1.0f - fminf(fmaxf(marg[(size_t)f * n_pix + pc], 0.0f), 1.0f) : 1.0f;
+    float w = (marg != nullptr) ? 1.0f - fminf(fmaxf(marg[(size_t)f * mask_pix + pm], 0.0f), 1.0f) : 1.0f;
     if (scene) {
       float run = 0.0f;
       for (int k = 0; k < sb.n_obj; ++k) run = fmaf(tbx[it & 1][k][X], tby[it & 1][k][Y], run);
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(kBgThreads) void bgspn_bwd_any_k(const float* __res
                                                               const int* __restrict__ side, const float* __restrict__ coef,
                                                               const float* __restrict__ dell, float* __restrict__ d_inputs,
                                                               float* __restrict__ d_marg, float* __restrict__ gcoef_part, int n_frames,
-                                                              int n_pix, int halves, FrameMap fm, SceneBoxes sb) {
+                                                              int n_pix, int halves, FrameMap fm, SceneBoxes sb, int mask_pix) {
   constexpr int NO = R * 2 * G;
   __shared__ float tbx[2][kBgTabObj][kBgTabMax], tby[2][kBgTabObj][kBgTabMax];
   const bool scene = sb.z != nullptr;
@@ -145,7 +146,8 @@ __global__ __launch_bounds__(kBgThreads) void bgspn_bwd_any_k(const float* __res
       }
   }
   const int fstep = gridDim.x / halves;
-  const int X = scene ? pc % sb.gm.W : 0, Y = scene ? pc / sb.gm.W : 0;
+  const int pm = pc % mask_pix;                  // the pixel's place in the mask plane (colour: C planes share one mask)
+  const int X = scene ? pm % sb.gm.W : 0, Y = scene ? pm / sb.gm.W : 0;
   if (scene && (int)(blockIdx.x / halves) < n_frames) {
     bg_fill_tables(sb, blockIdx.x / halves, tbx[0], tby[0], nullptr, nullptr);
     __syncthreads();
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(kBgThreads) void bgspn_bwd_any_k(const float* __res
     const float x = inputs[fm.row(f) * n_pix + pc];
     float mraw = 0.0f, w = 1.0f;
     if (marg != nullptr) {
-      mraw = marg[(size_t)f * n_pix + pc];
+      mraw = marg[(size_t)f * mask_pix + pm];
       w = 1.0f - fminf(fmaxf(mraw, 0.0f), 1.0f);
     }
     if (scene) {
@@ -243,11 +245,12 @@ __global__ __launch_bounds__(256) void bg_mask_any_k(const float* __restrict__ z
   }
   mask[t] = fminf(run, 1.0f);
 }
-// d_mask[f][p] (= dL/d mask, from the background SPN's backward) -> dz_bg[f][k][4] = dL/d(sx, sy, x, y) of every pasted box.
-// One workgroup per frame, thread = pixels p, p + 256, ...; the 4 n_obj sums are reduced over the workgroup in a fixed order.
+// d_mask[f][c][p] (= dL/d mask, from the background SPN's backward; C planes of one mask with colour) -> dz_bg[f][k][4] = dL/d(sx, sy, x, y)
+// of every pasted box.  One workgroup per frame, thread = pixels p, p + 256, ...; the C planes are added in channel order, the 4 n_obj sums
+// reduced over the workgroup in a fixed order.
 template <int NMAX>
 __global__ __launch_bounds__(256) void bg_mask_bwd_any_k(const float* __restrict__ z, const float* __restrict__ d_mask, float* __restrict__ dz_bg,
-                                                         int n_frames, int n_obj, SceneGeom gm) {
+                                                         int n_frames, int n_obj, SceneGeom gm, int C) {
   __shared__ float red[4][NMAX * 4];
   __shared__ float tx[kBgTabObj][kBgTabMax], ty[kBgTabObj][kBgTabMax], dtx[kBgTabObj][kBgTabMax], dty[kBgTabObj][kBgTabMax];
   const int f = blockIdx.x;
@@ -285,7 +288,12 @@ __global__ __launch_bounds__(256) void bg_mask_bwd_any_k(const float* __restrict
       }
       if (k < n_obj) run += cxv[k] * cyv[k];
     }
-    const float d = run <= 1.0f ? d_mask[(size_t)f * n_pix + p] : 0.0f;        // min(1, .): the gradient passes while the sum is not clamped
+    float d = 0.0f;                                                                // min(1, .): the gradient passes while the sum is not clamped
+    if (run <= 1.0f) {
+      const float* dm = d_mask + (size_t)f * C * n_pix + p;
+      d = dm[0];
+      for (int c = 1; c < C; ++c) d += dm[(size_t)c * n_pix];
+    }
 #pragma unroll
     for (int k = 0; k < NMAX; ++k) {
       if (k < n_obj) {
@@ -322,12 +330,14 @@ size_t bgspn_any_bwd_ws_floats(int n_frames, int n_pix) {
 }
 
 int bgspn_any_forward(const float* inputs, const float* marg, const int* side, const float* coef, const float* wroot, float* ell_part,
-                      float* out, int n_frames, int n_pix, hipStream_t st, FrameMap fm = FrameMap{0, 0}, SceneBoxes sb = SceneBoxes{nullptr, 0, SceneGeom{}}) {
+                      float* out, int n_frames, int n_pix, hipStream_t st, FrameMap fm = FrameMap{0, 0}, SceneBoxes sb = SceneBoxes{nullptr, 0, SceneGeom{}},
+                      int mask_pix = 0) {           // mask_pix: floats of one mask row (marg, or sb's plane); 0 = n_pix
   if (n_frames == 0) return 0;
   if (n_pix < 1) return (int)hipErrorInvalidValue;
+  if (mask_pix <= 0) mask_pix = n_pix;
   const int halves = bg_halves_any(n_pix);
   STOVE_LAUNCH((bgspn_fwd_any_k<kBgR, kBgG>), dim3(bg_grid_any(n_frames, n_pix)), dim3(kBgThreads), 0, st, inputs, marg, side, coef, ell_part,
-               n_frames, n_pix, halves, fm, sb);
+               n_frames, n_pix, halves, fm, sb, mask_pix);
   STOVE_LAUNCH_CHECK();
   STOVE_LAUNCH((bgspn_root_fwd_k<kBgR, kBgG>), dim3((n_frames + 255) / 256), dim3(256), 0, st, ell_part, wroot, out, n_frames, halves);
   STOVE_LAUNCH_CHECK();
@@ -337,8 +347,10 @@ int bgspn_any_forward(const float* inputs, const float* marg, const int* side, c
 // g_coef [R][n_pix][G][3], g_wroot [R*G*G] overwritten
 int bgspn_any_backward(const float* inputs, const float* marg, const int* side, const float* coef, const float* wroot, const float* ell_part,
                        const float* out, const float* dout, float* d_inputs, float* d_marg, float* g_coef, float* g_wroot, float* ws,
-                       int n_frames, int n_pix, hipStream_t st, FrameMap fm = FrameMap{0, 0}, SceneBoxes sb = SceneBoxes{nullptr, 0, SceneGeom{}}) {
+                       int n_frames, int n_pix, hipStream_t st, FrameMap fm = FrameMap{0, 0}, SceneBoxes sb = SceneBoxes{nullptr, 0, SceneGeom{}},
+                       int mask_pix = 0) {
   if (n_pix < 1) return (int)hipErrorInvalidValue;
+  if (mask_pix <= 0) mask_pix = n_pix;
   if (n_frames == 0) {
     hipMemsetAsync(g_coef, 0, sizeof(float) * kBgR * (size_t)n_pix * kBgG * 3, st);
     hipMemsetAsync(g_wroot, 0, sizeof(float) * kBgR * kBgG * kBgG, st);
@@ -352,7 +364,7 @@ int bgspn_any_backward(const float* inputs, const float* marg, const int* side, 
   STOVE_LAUNCH((bgspn_root_bwd_k<kBgR, kBgG>), dim3((n_frames + 255) / 256), dim3(256), 0, st, ell_part, wroot, out, dout, dell, rsc, n_frames, halves);
   STOVE_LAUNCH_CHECK();
   STOVE_LAUNCH((bgspn_bwd_any_k<kBgR, kBgG>), dim3(grid), dim3(kBgThreads), 0, st, inputs, marg, side, coef, (const float*)dell, d_inputs, d_marg,
-               gpart, n_frames, n_pix, halves, fm, sb);
+               gpart, n_frames, n_pix, halves, fm, sb, mask_pix);
   STOVE_LAUNCH_CHECK();
   const size_t nc = (size_t)kBgR * n_pix * kBgG * 3;
   STOVE_LAUNCH((bgspn_coef_reduce_any_k<kBgR, kBgG>), dim3((unsigned)((nc + 31) / 32)), dim3(256), 0, st, (const float*)gpart, g_coef, grid, n_pix, halves);

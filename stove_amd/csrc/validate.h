@@ -90,6 +90,39 @@ inline int scene_bwd(const StoveSpnTables* t, const float* frames, const float* 
   return 0;
 }
 
+// ---- the scene likelihood over colour channels (stove_scene_*_ch): object SPN of any shape over channels x pw x ph dimensions
+// (the limits of stove_objspn_fwd_any), background tables [3][channels * W * H][6][3]
+inline bool obj_any_bad(int R, int G, int S, int D, int Lmax) {
+  return R < 1 || R > 8 || G < 1 || G > 16 || S < 1 || S > 16 || D < 4 || D > 1024 || Lmax < 1 || Lmax > D;
+}
+inline bool scene_ch_bad(int R, int G, int S, int D, int Lmax, size_t bg_coef_floats, int n_frames, int n_obj, int seq_frames, int seq_stride,
+                        int channels, int W, int H, int pw, int ph) {
+  if (n_frames < 0 || n_obj < 1 || n_obj > kMaxObjects || frame_map(n_frames, seq_frames, seq_stride)) return true;
+  if (channels < 1 || channels > 4 || W < 2 || H < 2 || pw < 2 || ph < 2 || obj_any_bad(R, G, S, D, Lmax)) return true;
+  return (long long)D != (long long)channels * pw * ph || bg_coef_floats != (size_t)3 * channels * W * H * 6 * 3;
+}
+inline int scene_ch_fwd(const int32_t* lscope, const float* coef, const float* wsum, const float* wroot, int R, int G, int S, int D, int Lmax,
+                        const int32_t* bg_side, const float* bg_coef, const float* bg_wroot, size_t bg_coef_floats, const float* frames,
+                        const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride, int channels, int W, int H, int pw, int ph,
+                        const float* ll, const float* saved) {
+  if (scene_ch_bad(R, G, S, D, Lmax, bg_coef_floats, n_frames, n_obj, seq_frames, seq_stride, channels, W, H, pw, ph)) return kStoveInvalidValue;
+  if (n_frames == 0) return 0;
+  if (lscope == nullptr || bg_side == nullptr || null_any(coef, wsum, wroot, bg_coef, bg_wroot, frames, z, ll, saved)) return kStoveInvalidValue;
+  return 0;
+}
+inline int scene_ch_bwd(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
+                        int D, int Lmax, const int32_t* bg_side, const float* bg_coef, const float* bg_wroot, size_t bg_coef_floats,
+                        const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride, int channels, int W, int H,
+                        int pw, int ph, const float* saved, const float* dll, const float* dz, const float* g_coef, const float* g_wsum,
+                        const float* g_wroot, const float* g_bg_coef, const float* g_bg_wroot, const void* ws) {
+  if (scene_ch_bad(R, G, S, D, Lmax, bg_coef_floats, n_frames, n_obj, seq_frames, seq_stride, channels, W, H, pw, ph)) return kStoveInvalidValue;
+  if (n_frames == 0) return 0;
+  if (lscope == nullptr || slot == nullptr || bg_side == nullptr || ws == nullptr ||
+      null_any(coef, wsum, wroot, bg_coef, bg_wroot, frames, z, saved, dll, dz, g_coef, g_wsum, g_wroot, g_bg_coef, g_bg_wroot))
+    return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- Dynamics.forward (stove_gnn_*), the recursion (stove_dynloop_*), Stove.rollout
 inline int gnn_shape(int B, int N, int sin_dim) {
   if (B < 0 || N < 1 || N > kMaxObjects || sin_dim < 16 || sin_dim > 32) return kStoveInvalidValue;

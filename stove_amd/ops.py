@@ -186,6 +186,24 @@ def join_side_after_backward(dev):
     torch.autograd.Variable._execution_engine.queue_callback(lambda: torch.cuda.current_stream(dev).wait_stream(_side_stream(dev)))
 
 
+def _frame_rows(frames):
+    """frames: (nf, n_pix) dense, or a (n, T', n_pix) time-slice of longer clips (x[:, 1:] in Stove.forward) whose rows are contiguous:
+    handed to the kernels as it lies in memory (frame map) instead of a 100 MB copy per step -> (frames, nf, seq_frames, seq_stride)."""
+    seq_frames = seq_stride = 0
+    if frames.dim() == 3:
+        if frames.stride(2) == 1 and frames.stride(1) == frames.shape[2] and frames.stride(0) >= frames.shape[1] * frames.shape[2] \
+                and frames.stride(0) % frames.shape[2] == 0 and frames.dtype == torch.float32 and frames.is_cuda:
+            seq_frames, seq_stride = frames.shape[1], frames.stride(0) // frames.shape[2]
+            nf = frames.shape[0] * frames.shape[1]
+        else:
+            frames = _f32(frames.reshape(-1, frames.shape[2]))
+            nf = frames.shape[0]
+    else:
+        frames = _f32(frames)
+        nf = frames.shape[0]
+    return frames, nf, seq_frames, seq_stride
+
+
 class _SceneFn(torch.autograd.Function):
     """Supair.likelihood fused (reference supair.py:44-110)."""
 
@@ -196,20 +214,7 @@ class _SceneFn(torch.autograd.Function):
         lib = _lib.load()
         z = _f32(z)
         tabs = [_f32(x) for x in (obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot)]
-        # frames: (nf, 1024) dense, or a (n, T', 1024) time-slice of longer clips (x[:, 1:] in Stove.forward) whose rows are
-        # contiguous: handed to the kernels as it lies in memory (frame map) instead of a 100 MB copy per step
-        seq_frames = seq_stride = 0
-        if frames.dim() == 3:
-            if frames.stride(2) == 1 and frames.stride(1) == frames.shape[2] and frames.stride(0) >= frames.shape[1] * frames.shape[2] \
-                    and frames.stride(0) % frames.shape[2] == 0 and frames.dtype == torch.float32 and frames.is_cuda:
-                seq_frames, seq_stride = frames.shape[1], frames.stride(0) // frames.shape[2]
-                nf = frames.shape[0] * frames.shape[1]
-            else:
-                frames = _f32(frames.reshape(-1, frames.shape[2]))
-                nf = frames.shape[0]
-        else:
-            frames = _f32(frames)
-            nf = frames.shape[0]
+        frames, nf, seq_frames, seq_stride = _frame_rows(frames)
         ctx.frame_map = (nf, seq_frames, seq_stride)
         dev = frames.device
         with torch.cuda.device(dev):
@@ -287,6 +292,62 @@ class _SceneFn(torch.autograd.Function):
             ctx.sink(grads)
             grads = [None] * 5
         return (None, dz, *grads) + (None,) * 9
+
+
+class _SceneChFn(torch.autograd.Function):
+    """Supair.likelihood fused over C colour channels (reference supair.py:44-110 with config.channels = C, debug_bw = False):
+    stove_scene_fwd_ch / stove_scene_bwd_ch, the object SPN of the general-size kind ('obj_any') over C * pw * ph dimensions."""
+
+    @staticmethod
+    def forward(ctx, frames, z, obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot, lscope, slot, bg_side, shape, n_obj, beta, geom,
+                with_grad=True):
+        # geom = (C, W, H, pw, ph, align_corners); shape = (R, G, S, D, Lmax) of the object SPN
+        lib = _lib.load()
+        z = _f32(z)
+        tabs = [_f32(x) for x in (obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot)]
+        frames, nf, seq_frames, seq_stride = _frame_rows(frames)
+        C, W, H, pw, ph, ac = geom
+        R, G, S, D, lmax = shape
+        if frames.shape[-1] != C * W * H or D != C * pw * ph:
+            raise ValueError('scene_likelihood_colour: frames %s / object SPN over %d dimensions do not match %d channels of %d x %d '
+                             'frames and %d x %d glimpses' % (tuple(frames.shape), D, C, W, H, pw, ph))
+        dev = frames.device
+        with torch.cuda.device(dev):
+            ll = torch.empty(nf, dtype=torch.float32, device=dev)
+            parts = torch.empty(nf, 3, dtype=torch.float32, device=dev)
+            grad = int(bool(with_grad) and any(ctx.needs_input_grad))
+            saved = torch.empty(lib.stove_scene_saved_floats_ch(nf, n_obj, C, W, H, R, G, S, D, lmax, grad) + 1, dtype=torch.float32,
+                                device=dev)
+            check(lib.stove_scene_fwd_ch(ptr(lscope), ptr(slot), ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), R, G, S, D, lmax, ptr(bg_side),
+                                         ptr(tabs[3]), ptr(tabs[4]), tabs[3].numel(), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames,
+                                         seq_stride, C, W, H, pw, ph, int(ac), float(beta), ptr(ll), ptr(parts), ptr(saved), stream(), grad),
+                  'stove_scene_fwd_ch')
+        ctx.save_for_backward(frames, z, *tabs, lscope, slot, bg_side, saved)
+        ctx.frame_map, ctx.n_obj, ctx.beta, ctx.geom, ctx.shape = (nf, seq_frames, seq_stride), n_obj, float(beta), geom, shape
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(parts)
+        return ll, parts
+
+    @staticmethod
+    def backward(ctx, dll, _dparts):
+        lib = _lib.load()
+        frames, z, oc, ow, orr, bc, bw, lscope, slot, bg_side, saved = ctx.saved_tensors
+        (nf, seq_frames, seq_stride), n_obj = ctx.frame_map, ctx.n_obj
+        C, W, H, pw, ph, ac = ctx.geom
+        R, G, S, D, lmax = ctx.shape
+        if dll is None:
+            return (None,) * 15
+        dll = _f32(dll)
+        dev = frames.device
+        with torch.cuda.device(dev):
+            dz = torch.empty_like(z)
+            grads = [torch.empty_like(x) for x in (oc, ow, orr, bc, bw)]
+            ws = _ws(lib.stove_scene_bwd_ws_bytes_ch(nf, n_obj, C, W, H, R, G, S, D, lmax), dev)
+            check(lib.stove_scene_bwd_ch(ptr(lscope), ptr(slot), ptr(oc), ptr(ow), ptr(orr), R, G, S, D, lmax, ptr(bg_side), ptr(bc), ptr(bw),
+                                         bc.numel(), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames, seq_stride, C, W, H, pw, ph, int(ac),
+                                         ctx.beta, ptr(saved), ptr(dll), ptr(dz), *[ptr(g) for g in grads], ptr(ws), stream(), None),
+                  'stove_scene_bwd_ch')
+        return (None, dz, *grads) + (None,) * 8
 
 
 class _ObjSpnAnyFn(torch.autograd.Function):
@@ -419,6 +480,16 @@ def scene_likelihood(frames, z, obj_tabs, bg_tabs, n_obj, beta, sink=None, geom=
         z = z.detach().requires_grad_()        # the sink needs the backward to run
     return _SceneFn.apply(frames, z, oc, ow, orr, bc, bw, osc, ols, bs, int(n_obj), float(beta), sink, dense, torch.is_grad_enabled(),
                           geom)
+
+
+def scene_likelihood_colour(frames, z, obj_tabs, bg_tabs, n_obj, beta, geom):
+    """Supair.likelihood over C colour channels.  frames (nf, C*W*H) or a (n, T', C*W*H) time-slice view, z (nf*n_obj, 4) = [sx, sy, x, y];
+    obj_tabs = (coef, wsum, wroot, lscope, slot, (R, G, S, D, Lmax)) of the general-size object SPN (RatSpn.tables, kind 'obj_any'),
+    bg_tabs = (coef, wroot, side); geom = (C, W, H, patch_width, patch_height, align_corners) -> ll (nf,), parts (nf, 3)."""
+    oc, ow, orr, lscope, slot, shape = obj_tabs
+    bc, bw, bs = bg_tabs[:3]
+    return _SceneChFn.apply(frames, z, oc, ow, orr, bc, bw, lscope, slot, bs, tuple(int(v) for v in shape), int(n_obj), float(beta),
+                            tuple(geom), torch.is_grad_enabled())
 
 
 def scene_glimpses(frames, z, n_obj):

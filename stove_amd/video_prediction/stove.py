@@ -38,6 +38,10 @@ def _normal_log_prob(x, mean, std):
 class Stove(nn.Module):
     def __init__(self, config):
         super().__init__()
+        if config.channels > 1 and config.debug_bw:
+            # the bw transform hands over one plane, which models of config.channels planes cannot score (the reference fails later
+            # on a shape mismatch)
+            raise ValueError('config.channels = %d needs config.debug_bw = False (debug_bw models a single bw plane)' % config.channels)
         self.c = config
         self.step_counter = 0
         self.prop_dict = {}

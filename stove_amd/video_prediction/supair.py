@@ -40,8 +40,16 @@ class Supair(nn.Module):
                 + sum_k log Exponential(overlap_beta)(overlap_k)      (reference supair.py:44-110)
         `log_from` (build addition) restricts the logged part means to frames x[:, log_from:].
         """
+        if x.dim() != 5 or x.shape[2] != self.c.channels:
+            raise ValueError('Supair.likelihood: frames %s do not have config.channels = %d planes (n, T, channels, w, h)'
+                             % (tuple(x.shape), self.c.channels))
         if self.c.channels != 1:
-            raise NotImplementedError('SPN kernels are built for single-channel frames')
+            # [amd] colour frames (config.channels = 3, debug_bw = False): glimpses and masks of every channel fused with the
+            # general-size SPN operators (stove_scene_fwd_ch).  scene_composed and the fixed-Gaussian debug models: the reference's
+            # op sequence (_likelihood_general)
+            if getattr(self.c, 'scene_composed', False) or self.obj_spn._kind != 'obj_any' or self.bg_spn._kind != 'bg':
+                return self._likelihood_general(x, z_obj, log_from)
+            return self._likelihood_colour(x, z_obj, log_from)
         if self.obj_spn._kind != 'obj' or self.bg_spn._kind != 'bg' or self.c.patch_width != 10 or self.c.patch_height != 10:
             # [amd] other glimpse sizes / SPN vector widths (config.patch_width, patch_height, obj_spn_num_gauss, obj_spn_num_sums): the
             # reference's op sequence with the general-size SPN operators (csrc/spn_obj_generic.hip, spn_bg_generic.hip); the fused
@@ -73,6 +81,20 @@ class Supair(nn.Module):
                 self.prop_dict['bg'] = m[0]
                 self.prop_dict['patch'] = m[1]
                 self.prop_dict['overlap'] = m[2]
+        return log_p_xz, self.prop_dict
+
+    def _likelihood_colour(self, x, z_obj, log_from=0):
+        """Supair.likelihood over config.channels colour planes: one fused pipeline (ops.scene_likelihood_colour)."""
+        c = self.c
+        geom = (c.channels, int(x.shape[-1]), int(x.shape[-2]), c.patch_width, c.patch_height, bool(getattr(c, 'align_corners', False)))
+        frames = x.flatten(start_dim=2)                 # (n, T', C*w*h) view: a time-slice of longer clips is not copied
+        log_p_xz, parts = ops.scene_likelihood_colour(frames, z_obj.reshape(-1, 4), self.obj_spn.tables(), self.bg_spn.tables(), c.num_obj,
+                                                      c.overlap_beta, geom)
+        if ((self.step_counter % c.print_every == 0) or (self.step_counter % c.plot_every == 0)) and c.debug:
+            m = parts.view(x.shape[0], x.shape[1], 3)[:, log_from:].mean((0, 1))
+            self.prop_dict['bg'] = m[0]
+            self.prop_dict['patch'] = m[1]
+            self.prop_dict['overlap'] = m[2]
         return log_p_xz, self.prop_dict
 
     def _likelihood_general(self, x, z_obj, log_from=0):
