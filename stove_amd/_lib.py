@@ -13,25 +13,6 @@ LIB_PATH = _settings.LIB_OVERRIDE or os.path.join(_HERE, 'libstove_hip.so')
 _lib = None
 ABI_VERSION = 6
 
-EXPORTS = [
-    'stove_abi_version', 'stove_error_string', 'stove_selftest_wave_sum',
-    'stove_objspn_tile_floats', 'stove_objspn_fwd', 'stove_objspn_bwd_ws_bytes', 'stove_objspn_bwd',
-    'stove_bgspn_saved_floats', 'stove_bgspn_fwd', 'stove_bgspn_bwd_ws_bytes', 'stove_bgspn_bwd',
-    'stove_scene_saved_floats', 'stove_scene_fwd', 'stove_scene_bwd_ws_bytes', 'stove_scene_bwd',
-    'stove_scene_glimpses',
-    'stove_gnn_param_floats', 'stove_gnn_grad_floats', 'stove_gnn_blocks', 'stove_gnn_fwd', 'stove_gnn_bwd_ws_bytes',
-    'stove_gnn_bwd', 'stove_dynloop_act_floats', 'stove_dynloop_fwd', 'stove_dynloop_bwd_ws_bytes', 'stove_dynloop_bwd', 'stove_rollout_fwd', 'stove_match_objects', 'stove_profile_enable', 'stove_profile_report', 'stove_gnn_debug_stamps', 'stove_lstm_cell_fwd', 'stove_lstm_cell_bwd',
-    'stove_spn_bake', 'stove_spn_bake_bwd', 'stove_arena_gather', 'stove_arena_scatter_add', 'stove_debug_set_stamps',
-    'stove_supair_state_fwd', 'stove_supair_state_bwd', 'stove_zall_fwd', 'stove_zall_bwd', 'stove_elbo_fwd', 'stove_elbo_bwd', 'stove_flat_adam', 'stove_flat_adam_ws_bytes', 'stove_gemm_bf16', 'stove_gemm_bf16_ws_floats', 'stove_sum_chunks', 'stove_colsum_ws_floats', 'stove_colsum', 'stove_bw_transform', 'stove_dynloop_bwd_ws_bytes_ts', 'stove_scene_bwd_overlap', 'stove_dynloop_bwd_overlap', 'stove_glimpse_mean', 'stove_objspn_mpe', 'stove_render_frames',
-    'stove_enc_head_fwd', 'stove_enc_head_bwd_ws_floats', 'stove_enc_head_bwd', 'stove_colsum2', 'stove_small_tn', 'stove_small_tn_ws_floats', 'stove_supair_state_fwd2', 'stove_supair_state_bwd2', 'stove_bg_dense', 'stove_bg_dense_floats',
-    'stove_bw_transform_u8', 'stove_stream_after', 'stove_capture_begin', 'stove_capture_end', 'stove_graph_instantiate', 'stove_graph_launch', 'stove_graph_destroy',
-    'stove_reward_head_param_floats', 'stove_reward_head_saved_floats', 'stove_reward_head_bwd_ws_floats', 'stove_reward_head_fwd',
-    'stove_bgspn_saved_floats_d', 'stove_bgspn_fwd_d', 'stove_bgspn_bwd_ws_bytes_d', 'stove_bgspn_bwd_d', 'stove_noise_normal', 'stove_set_overlap', 'stove_set_tile_lds', 'stove_event_list_begin', 'stove_event_list_end', 'stove_event_list_destroy', 'stove_fill_words',
-    'stove_reward_head_bwd', 'stove_small_linear', 'stove_set_fork_stream', 'stove_scene_fwd_from', 'stove_scene_fwd_floats', 'stove_gauss_ll_fwd', 'stove_gauss_ll_bwd', 'stove_objspn_saved_floats_any', 'stove_objspn_bwd_ws_bytes_any', 'stove_objspn_fwd_any', 'stove_objspn_bwd_any', 'stove_scene_saved_floats_any', 'stove_scene_bwd_ws_bytes_any', 'stove_scene_fwd_any', 'stove_scene_bwd_any', 'stove_scene_bwd_from',
-    'stove_scene_saved_floats_ch', 'stove_scene_bwd_ws_bytes_ch', 'stove_scene_fwd_ch', 'stove_scene_bwd_ch',
-]
-
-
 class SpnTables(Structure):
     _fields_ = [('obj_scope', c_void_p), ('obj_leaf_slot', c_void_p), ('obj_coef', c_void_p),
                 ('obj_wsum', c_void_p), ('obj_wroot', c_void_p),
@@ -170,13 +151,6 @@ def _declare(lib):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    for name in OPTIONAL_SIGS:
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = OPTIONAL_SIGS[name]
-
-
-OPTIONAL_SIGS = {}
 
 
 def load():

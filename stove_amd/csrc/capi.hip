@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <math.h>
 #include <atomic>
+#include <type_traits>
 #include "validate.h"
 // argument checks shared with the sanitizer-built host driver (csrc/validate.h, tests/abi/validate_driver.cpp)
 static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "validate.h returns hipErrorInvalidValue");
@@ -66,30 +67,17 @@ static inline bool tile_transposed(int n_obj) {
   const int m = g_tile_lds.load();
   return m == 2 || (m == 1 && n_obj <= 3);
 }
-template <int NMAX>
-static int scene_tile_fwd(const float* frames, const float* z, float* xw, int n_obj, int np, hipStream_t st, FrameMap fm) {
+// ANY: the frame size / sampling convention at run time from `gm` (stove_scene_fwd_any); otherwise the tuned path's constants
+template <int NMAX, bool ANY = false>
+static int scene_tile_fwd(const float* frames, const float* z, float* xw, int n_obj, int np, hipStream_t st, FrameMap fm, SceneGeom gm = SceneGeom{}) {
   const int nb = (np + 63) / 64;
   const int grid = nb < 8192 ? nb : 8192;          // one workgroup per batch of 64 glimpses
   if (tile_transposed(n_obj)) {          // lane = pixel, tile transposed through LDS (scene_tile_fwd_t_k)
-    STOVE_LAUNCH((scene_tile_fwd_t_k<NMAX>), dim3(grid), dim3(64 * kTileTWaves), 0, st, frames, z, xw, n_obj, np, nb, fm, SceneGeom{});
+    STOVE_LAUNCH((scene_tile_fwd_t_k<NMAX, ANY>), dim3(grid), dim3(64 * kTileTWaves), 0, st, frames, z, xw, n_obj, np, nb, fm, gm);
     STOVE_LAUNCH_CHECK();
     return 0;
   }
-  STOVE_LAUNCH((scene_tile_fwd_k<NMAX>), dim3(grid), dim3(256), 0, st, frames, z, xw, n_obj, np, nb, fm, SceneGeom{});
-  STOVE_LAUNCH_CHECK();
-  return 0;
-}
-// the same kernels with the frame size / sampling convention at run time (stove_scene_fwd_any)
-template <int NMAX>
-static int scene_tile_fwd_g(const float* frames, const float* z, float* xw, int n_obj, int np, hipStream_t st, FrameMap fm, SceneGeom gm) {
-  const int nb = (np + 63) / 64;
-  const int grid = nb < 8192 ? nb : 8192;
-  if (tile_transposed(n_obj)) {
-    STOVE_LAUNCH((scene_tile_fwd_t_k<NMAX, true>), dim3(grid), dim3(64 * kTileTWaves), 0, st, frames, z, xw, n_obj, np, nb, fm, gm);
-    STOVE_LAUNCH_CHECK();
-    return 0;
-  }
-  STOVE_LAUNCH((scene_tile_fwd_k<NMAX, true>), dim3(grid), dim3(256), 0, st, frames, z, xw, n_obj, np, nb, fm, gm);
+  STOVE_LAUNCH((scene_tile_fwd_k<NMAX, ANY>), dim3(grid), dim3(256), 0, st, frames, z, xw, n_obj, np, nb, fm, gm);
   STOVE_LAUNCH_CHECK();
   return 0;
 }
@@ -110,28 +98,19 @@ static SceneGeom scene_geom(int W, int H, int align_corners) {
   return g;
 }
 
-static int scene_tile_fwd_any(const float* frames, const float* z, float* xw, int n_obj, int np, hipStream_t st, FrameMap fm = FrameMap{0, 0}) {
-  if (n_obj <= 3) return scene_tile_fwd<3>(frames, z, xw, n_obj, np, st, fm);
-  if (n_obj <= 6) return scene_tile_fwd<6>(frames, z, xw, n_obj, np, st, fm);
-  if (n_obj <= 8) return scene_tile_fwd<8>(frames, z, xw, n_obj, np, st, fm);
-  return (int)hipErrorInvalidValue;
-}
-
 static inline int nmax_of(int n_obj) { return n_obj <= 3 ? 3 : (n_obj <= 6 ? 6 : 8); }
 
-// Tail of the scene backward: dL/d tile + transformer / mask backward in one pass over the leaf gradients `Dscr`
-// (scene_pixtile_bwd_k), then the per-object sums with the background chain's dz_bg.
-template <int NMAX>
-static int scene_bwd_tail(const float* frames, const float* z, const float* xw, const float* Dscr, const int* leaf_slot,
-                          const float* coef, const float* d_ovl, float* dzc, const float* dll, const float* obj_ll,
-                          const float* dz_bg, float* dz, int n_obj, int np, hipStream_t st, hipStream_t bg_stream, FrameMap fm,
-                          const float* d_obj, int bg_parts) {      // Dscr is at unit upstream gradient: times d_obj[patch] as it is staged
-  int rc = scene_pixtile_bwd<NMAX>(frames, z, xw, Dscr, leaf_slot, coef, d_ovl, dzc, n_obj, np, st, fm, d_obj);
-  if (rc) return rc;
-  STOVE_TRY(stream_after(st, bg_stream));       // join: only the last kernel needs the background chain's dz_bg
-  STOVE_LAUNCH((scene_finalize_bwd_k<NMAX>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, obj_ll, dz_bg, dzc, dz, n_obj, np, bg_parts);
-  STOVE_LAUNCH_CHECK();
-  return 0;
+// The object-count ladder of the kernel templates: f(std::integral_constant<int, NMAX>) with the smallest NMAX of 3 / 6 / 8 that holds
+// `n` objects (n may be an NMAX already: nmax_of, nmax_ch).  SIX = false: 3 / 8, for the kernels without a six-object instantiation
+// (bg_mask_bwd_any_k, the colour kernels) -- the ladder is what instantiates them, so it must not name one.
+template <bool SIX = true, class F>
+static int with_nmax(int n, F f) {
+  if (n <= 3) return f(std::integral_constant<int, 3>{});
+  if constexpr (SIX) {
+    if (n <= 6) return f(std::integral_constant<int, 6>{});
+  }
+  if (n <= 8) return f(std::integral_constant<int, 8>{});
+  return (int)hipErrorInvalidValue;
 }
 
 __global__ void fill_words_k(uint32_t* __restrict__ p, uint32_t v, size_t n) {
@@ -233,28 +212,6 @@ int stove_bgspn_bwd_d(const StoveSpnTables* t, const float* inputs, const float*
 }
 
 // ---------------------------------------------------------------- fused scene likelihood
-// saved = [ xw tile | obj_ll (np) | ovl (np) | bg_out (nf) | bg_ell | box coverage tables | object-SPN backward scratch at unit gradient ]
-// (the last section only exists / is only written when the forward is asked for it: with_grad)
-struct SceneSaved {
-  size_t xw, obj_ll, ovl, bg_out, bg_ell, cover, obj_scratch, total;
-};
-static SceneSaved scene_saved_layout(int nf, int n_obj, bool with_grad = true) {
-  const size_t np = (size_t)nf * n_obj;
-  SceneSaved s;
-  s.xw = 0;
-  s.obj_ll = align64(stove_objspn_tile_floats((int)np));
-  s.ovl = s.obj_ll + align64(np);
-  s.bg_out = s.ovl + align64(np);
-  s.bg_ell = s.bg_out + align64(nf);
-  s.cover = s.bg_ell + align64(bgspn_fwd_ws_floats(nf));
-  s.obj_scratch = s.cover + align64(bg_cover_floats(nf, n_obj));
-  s.total = s.obj_scratch + (with_grad ? align64(objspn_scratch_floats((int)np)) : 0);
-  return s;
-}
-
-size_t stove_scene_saved_floats(int n_frames, int n_obj) { return scene_saved_layout(n_frames, n_obj).total; }
-size_t stove_scene_fwd_floats(int n_frames, int n_obj, int with_grad) { return scene_saved_layout(n_frames, n_obj, with_grad != 0).total; }
-
 // Internal fork stream (one per device, created on first use): the background-SPN chain of a scene call runs on it next
 // to the object-SPN chain -- they are independent until the assemble / tail kernels -- and is joined back before the call
 // returns, so callers see plain single-stream semantics.  STOVE_NO_OVERLAP=1 keeps everything on the caller's stream.
@@ -306,6 +263,235 @@ static int frame_map(int n_frames, int seq_frames, int seq_stride, FrameMap* fm)
   return 0;
 }
 
+}  // extern "C": the host side that the three scene pipelines share has templates
+
+// The tuned 32 x 32 / 10 x 10 pipeline (stove_scene_fwd*, stove_scene_bwd*), the one for any frame size / sampling convention
+// (stove_scene_*_any) and the one over 1 to 4 colour channels (stove_scene_*_ch) share what follows: the buffer layouts, the call
+// context with the fork / join / parameter-stream protocol, and one skeleton each for the forward and the backward.
+namespace stove {
+
+// offsets of consecutive sections of one buffer, each a multiple of 64 floats long
+struct Layout {
+  size_t total = 0;
+  size_t take(size_t floats) {
+    const size_t at = total;
+    total += align64(floats);
+    return at;
+  }
+};
+
+// saved = [ head | obj_ll (np) | ovl (np) | bg_out (nf) | bg_ell | bg_aux | obj_scratch ]
+//   head: the xw tile (tuned, any size), or patches | marg | obj, the object SPN's saved activations (colour)
+//   bg_aux: the box coverage tables (tuned), or the mask image (any size, colour; frames up to kBgTabMax a side keep none)
+//   obj_scratch: the object-SPN backward scratch at unit gradient (tuned, any size; the section only exists / is only written when the
+//   forward is asked for it: with_grad)
+struct SceneSaved {
+  size_t xw, patches, marg, obj, obj_ll, ovl, bg_out, bg_ell, bg_aux, obj_scratch, total;
+};
+static void scene_saved_shared(Layout& l, SceneSaved& s, size_t nf, size_t np, size_t bg_ell, size_t bg_aux) {
+  s.obj_ll = l.take(np);
+  s.ovl = l.take(np);
+  s.bg_out = l.take(nf);
+  s.bg_ell = l.take(bg_ell);
+  s.bg_aux = l.take(bg_aux);
+}
+// tuned and any size: they differ in the two background sections
+static SceneSaved scene_saved_layout(int nf, int n_obj, bool with_grad, size_t bg_ell, size_t bg_aux) {
+  const size_t np = (size_t)nf * n_obj;
+  Layout l;
+  SceneSaved s{};
+  s.xw = l.take(stove_objspn_tile_floats((int)np));
+  scene_saved_shared(l, s, nf, np, bg_ell, bg_aux);
+  s.obj_scratch = l.take(with_grad ? objspn_scratch_floats((int)np) : 0);
+  s.total = l.total;
+  return s;
+}
+
+// ws = [ d_obj (np) | d_ovl (np) | dzc (np*NMAX*4) | dz_bg (np*4) | d_patch | d_marg | obj | d_mask | bg ]
+//   d_patch, d_marg: the glimpse gradients (colour only); obj: the object SPN's table-gradient chunk partials (tuned, any size) or its
+//   backward workspace (colour); d_mask: the mask gradient (any size; colour: C planes); bg: the background operator's workspace
+struct SceneWs {
+  size_t d_obj, d_ovl, dzc, dz_bg, d_patch, d_marg, obj, d_mask, bg, total;
+};
+static SceneWs scene_ws_layout(size_t np, int nmax, size_t d_glimpse, size_t obj, size_t d_mask, size_t bg) {
+  Layout l;
+  SceneWs s;
+  s.d_obj = l.take(np);
+  s.d_ovl = l.take(np);
+  s.dzc = l.take(np * nmax * 4);
+  s.dz_bg = l.take(np * 4);
+  s.d_patch = l.take(d_glimpse);
+  s.d_marg = l.take(d_glimpse);
+  s.obj = l.take(obj);
+  s.d_mask = l.take(d_mask);
+  s.bg = l.take(bg);
+  s.total = l.total;
+  return s;
+}
+
+// frames up to kBgTabMax a side: the background kernels form the mask themselves from per-frame coverage tables (spn_bg_generic.hip), no
+// mask image is kept
+static bool scene_any_inline(int W, int H) { return W <= kBgTabMax && H <= kBgTabMax; }
+
+// One scene call: its inputs, buffers and streams.  The background-SPN chain runs on the fork stream `sb` next to the object chain on
+// the call's stream `st` -- they are independent until the assemble / finalize kernels; the table gradients, which only feed the
+// optimiser, may go to the caller's parameter stream `sp`.  The call owns the guards of both, so every exit path joins what it forked.
+struct SceneCall {
+  const float *frames, *z;
+  int nf, n_obj, np;
+  hipStream_t st, root, sp, sb;     // root: the stream the fork is ordered behind (stove_scene_fwd_from); sb: set by fork()
+  FrameMap fm{0, 0};
+  // the pipelines with the geometry at run time (geometry()); the tuned one leaves these as they are
+  SceneGeom gm{};
+  SceneBoxes boxes{nullptr, 0, SceneGeom{}};
+  bool inl = false;                 // scene_any_inline: no mask image
+  int plane = 0, channels = 1;      // pixels of one colour plane; the background SPN sees channels * plane dimensions
+  SceneSaved L{};
+  SceneWs W{};
+  const float* saved = nullptr;
+  float* ws = nullptr;
+  JoinGuard jb, jp;                 // armed by fork()
+
+  SceneCall(const float* frames_, const float* z_, int n_frames, int n_obj_, void* stream, void* fork_from = nullptr, void* param_stream = nullptr)
+      : frames(frames_), z(z_), nf(n_frames), n_obj(n_obj_), np(n_frames * n_obj_), st((hipStream_t)stream),
+        root(fork_from != nullptr ? (hipStream_t)fork_from : st), sp(param_stream != nullptr ? (hipStream_t)param_stream : st), sb(st),
+        jb(st, st), jp(st, st) {}
+  void geometry(int W_, int H_, int align_corners, int channels_) {
+    gm = scene_geom(W_, H_, align_corners);
+    inl = scene_any_inline(W_, H_);
+    boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
+    plane = W_ * H_;
+    channels = channels_;
+  }
+  // fork: the background chain's inputs are ready in `root` order.  From here on `sb` is joined on every exit path (jb: the skeletons
+  // join it before their last kernel) and so is the parameter stream on the error paths (jp: the caller joins it after a clean return)
+  int fork() {
+    sb = scene_fork_stream(st);
+    STOVE_TRY(stream_after(sb, root));
+    jb.from = sb; jb.done = sb == st;
+    jp.from = sp; jp.done = sp == st;
+    return 0;
+  }
+};
+
+// Forward: fork, object chain (on c.st), background chain (on c.sb: MFMA-bound next to the VALU-bound object chain), join, assemble.
+template <class Obj, class Bg>
+static int scene_forward(SceneCall& c, float overlap_beta, float* ll, float* parts, Obj obj_chain, Bg bg_chain) {
+  int rc = c.fork();
+  if (rc) return rc;
+  if ((rc = obj_chain())) return rc;
+  if ((rc = bg_chain())) return rc;
+  STOVE_TRY(c.jb.join());
+  STOVE_LAUNCH(scene_assemble_fwd_k, dim3((c.nf + 255) / 256), dim3(256), 0, c.st, c.saved + c.L.bg_out, c.saved + c.L.obj_ll,
+               c.saved + c.L.ovl, c.z, ll, parts, c.n_obj, c.nf, overlap_beta, logf(overlap_beta));
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// Backward: assemble, fork, what runs off the call's stream (the background chain on c.sb, which leaves dz_bg as `bg_parts` partial
+// images; the tuned pipeline may also start its table gradients on c.sp here), the object chain (on c.st, leaves dzc with `nmax`
+// entries per glimpse), join -- only the last kernel needs dz_bg --, finalize, and what the pipeline does once dz is out: the
+// parameter stream is at least ordered behind c.st there.
+template <class Side, class Obj, class After>
+static int scene_backward(SceneCall& c, const float* dll, float* dz, float overlap_beta, int nmax, const float* dz_bg, int bg_parts,
+                          Side side_chains, Obj obj_chain, After after_finalize) {
+  STOVE_LAUNCH(scene_assemble_bwd_k, dim3((c.np + 255) / 256), dim3(256), 0, c.st, dll, c.z, c.ws + c.W.d_obj, c.ws + c.W.d_ovl, c.n_obj,
+               c.np, overlap_beta);
+  STOVE_LAUNCH_CHECK();
+  int rc = c.fork();
+  if (rc) return rc;
+  if ((rc = side_chains())) return rc;
+  if ((rc = obj_chain())) return rc;
+  STOVE_TRY(c.jb.join());
+  rc = with_nmax(nmax, [&](auto n) {
+    STOVE_LAUNCH((scene_finalize_bwd_k<decltype(n)::value>), dim3((c.np + 255) / 256), dim3(256), 0, c.st, dll, c.z, c.saved + c.L.obj_ll,
+                 dz_bg, c.ws + c.W.dzc, dz, c.n_obj, c.np, bg_parts);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+  if (rc) return rc;
+  if ((rc = after_finalize())) return rc;
+  c.jp.dismiss();
+  return 0;
+}
+
+// Object chain of the tuned (ANY = false) and any-size pipelines: the 32 x 32 path's kernels, with the geometry at run time for ANY.
+// with_grad != 0: the object SPN runs forward + backward at unit upstream gradient in one pass (objspn_fwd_unit_k) and leaves the
+// per-glimpse backward scratch in `saved`.
+template <bool ANY>
+static int scene_obj_fwd(const SceneCall& c, const StoveSpnTables* t, float* saved, int with_grad) {
+  float* xw = saved + c.L.xw;
+  int rc = with_nmax(c.n_obj, [&](auto n) { return scene_tile_fwd<decltype(n)::value, ANY>(c.frames, c.z, xw, c.n_obj, c.np, c.st, c.fm, c.gm); });
+  if (rc) return rc;
+  if (with_grad)
+    return objspn_forward_unit(xw, t->obj_scope, t->obj_coef, t->obj_wsum, t->obj_wroot, saved + c.L.obj_ll, saved + c.L.ovl,
+                               saved + c.L.obj_scratch, c.np, c.st);
+  return objspn_forward(xw, t->obj_scope, t->obj_coef, t->obj_wsum, t->obj_wroot, saved + c.L.obj_ll, saved + c.L.ovl, c.np, c.st);
+}
+// The object SPN's backward already ran, at unit upstream gradient, inside the forward: what is left is to apply d_obj[patch] where its
+// scratch is consumed -- dL/d tile + transformer / mask backward in one pass over the leaf gradients (scene_pixtile_bwd_k) here, and
+// the table gradients below.
+template <bool ANY>
+static int scene_obj_bwd(const SceneCall& c, const StoveSpnTables* t) {
+  return with_nmax(c.n_obj, [&](auto n) {
+    return scene_pixtile_bwd<decltype(n)::value, ANY>(c.frames, c.z, c.saved + c.L.xw, c.saved + c.L.obj_scratch, t->obj_leaf_slot, t->obj_coef,
+                                                      c.ws + c.W.d_ovl, c.ws + c.W.dzc, c.n_obj, c.np, c.st, c.fm, c.ws + c.W.d_obj, c.gm);
+  });
+}
+// table gradients of the object SPN on the parameter stream, behind everything c.st holds so far
+static int scene_obj_tablegrads(const SceneCall& c, const StoveSpnTables* t, StoveSpnTableGrads* g, bool under = false) {
+  STOVE_TRY(stream_after(c.sp, c.st));
+  return objspn_backward_params(c.saved + c.L.xw, t->obj_scope, g->obj_coef, g->obj_wsum, g->obj_wroot, c.saved + c.L.obj_scratch,
+                                c.ws + c.W.obj, c.ws + c.W.d_obj, c.np, c.sp, under);
+}
+
+// Background chain of the any-size and colour pipelines: the mask in closed form (bg_mask_any_k; one plane for all channels), the
+// general-size operator of spn_bg_generic.hip over channels * plane dimensions ...
+static int scene_bg_fwd_any(const SceneCall& c, const int32_t* side, const float* coef, const float* wroot, float* saved) {
+  if (!c.inl) {
+    const size_t tot = (size_t)c.nf * c.plane;
+    STOVE_LAUNCH(bg_mask_any_k, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.sb, c.z, saved + c.L.bg_aux, c.nf, c.n_obj, c.gm);
+    STOVE_LAUNCH_CHECK();
+  }
+  return bgspn_any_forward(c.frames, c.inl ? nullptr : saved + c.L.bg_aux, side, coef, wroot, saved + c.L.bg_ell, saved + c.L.bg_out, c.nf,
+                           c.channels * c.plane, c.sb, c.fm, c.boxes, c.plane);
+}
+// ... backward: the operator's (d mask of every plane, table gradients), then the mask's backward to z (bg_mask_bwd_any_k, planes summed)
+static int scene_bg_bwd_any(const SceneCall& c, const int32_t* side, const float* coef, const float* wroot, const float* dll, float* g_coef,
+                            float* g_wroot) {
+  float* d_mask = c.ws + c.W.d_mask;
+  int rc = bgspn_any_backward(c.frames, c.inl ? nullptr : c.saved + c.L.bg_aux, side, coef, wroot, c.saved + c.L.bg_ell, c.saved + c.L.bg_out,
+                              dll, nullptr, d_mask, g_coef, g_wroot, c.ws + c.W.bg, c.nf, c.channels * c.plane, c.sb, c.fm, c.boxes, c.plane);
+  if (rc) return rc;
+  return with_nmax<false>(c.n_obj, [&](auto n) {
+    STOVE_LAUNCH((bg_mask_bwd_any_k<decltype(n)::value>), dim3(c.nf), dim3(256), 0, c.sb, c.z, (const float*)d_mask, c.ws + c.W.dz_bg, c.nf,
+                 c.n_obj, c.gm, c.channels);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+}  // namespace stove
+
+extern "C" {
+
+// ---- the tuned pipeline: 32 x 32 frames, 10 x 10 glimpses, align_corners = False
+static SceneSaved scene_saved_tuned(int nf, int n_obj, bool with_grad = true) {
+  return scene_saved_layout(nf, n_obj, with_grad, bgspn_fwd_ws_floats(nf), bg_cover_floats(nf, n_obj));
+}
+static SceneWs scene_ws_tuned(int nf, int n_obj) {
+  return scene_ws_layout((size_t)nf * n_obj, nmax_of(n_obj), 0, objspn_partial_floats(), 0, bgspn_bwd_ws_floats(nf, n_obj));
+}
+size_t stove_scene_saved_floats(int n_frames, int n_obj) { return scene_saved_tuned(n_frames, n_obj).total; }
+size_t stove_scene_fwd_floats(int n_frames, int n_obj, int with_grad) { return scene_saved_tuned(n_frames, n_obj, with_grad != 0).total; }
+size_t stove_scene_bwd_ws_bytes(int n_frames, int n_obj) { return scene_ws_tuned(n_frames, n_obj).total * sizeof(float); }
+
+size_t stove_bg_dense_floats(void) { return (size_t)kBgDenseF; }
+int stove_bg_dense(const int32_t* bg_side, const float* bg_coef, float* dense, void* stream) {
+  STOVE_LAUNCH(bg_dense_fwd_k, dim3((kBgDenseF + 255) / 256), dim3(256), 0, (hipStream_t)stream, bg_side, bg_coef, dense);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
 int stove_scene_fwd(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames,
                     int seq_stride, float overlap_beta, float* ll, float* parts, float* saved, void* stream) {
   return stove_scene_fwd_from(t, frames, z, n_frames, n_obj, seq_frames, seq_stride, overlap_beta, ll, parts, saved, stream, stream, 1);
@@ -322,66 +508,19 @@ int stove_scene_fwd_from(const StoveSpnTables* t, const float* frames, const flo
                          int seq_stride, float overlap_beta, float* ll, float* parts, float* saved, void* stream, void* fork_from,
                          int with_grad) {
   STOVE_VALIDATE(scene_fwd(t, frames, z, n_frames, n_obj, seq_frames, seq_stride, ll, saved));
-  hipStream_t st = (hipStream_t)stream;
-  hipStream_t root = fork_from != nullptr ? (hipStream_t)fork_from : st;
   if (n_frames == 0) return 0;
-  FrameMap fm;
-  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
-  const SceneSaved L = scene_saved_layout(n_frames, n_obj);
-  const int np = n_frames * n_obj;
-  hipStream_t sb = scene_fork_stream(st);       // background chain (MFMA-bound) next to the object chain (VALU-bound)
-  STOVE_TRY(stream_after(sb, root));            // fork: inputs are ready in `root` order
-  JoinGuard jb(st, sb);                         // joined on every exit path
-  int rc = scene_tile_fwd_any(frames, z, saved + L.xw, n_obj, np, st, fm);
-  if (rc) return rc;
-  if (with_grad)
-    rc = objspn_forward_unit(saved + L.xw, t->obj_scope, t->obj_coef, t->obj_wsum, t->obj_wroot, saved + L.obj_ll, saved + L.ovl,
-                             saved + L.obj_scratch, np, st);
-  else
-    rc = objspn_forward(saved + L.xw, t->obj_scope, t->obj_coef, t->obj_wsum, t->obj_wroot, saved + L.obj_ll, saved + L.ovl, np, st);
-  if (rc) return rc;
-  rc = bgspn_forward(frames, nullptr, z, n_obj, t->bg_side, t->bg_coef, t->bg_wroot, saved + L.bg_ell, saved + L.bg_out, n_frames, sb, fm, t->bg_dense);
-  if (rc) return rc;
-  rc = bg_cover_tables(z, saved + L.cover, n_frames, n_obj, sb);       // for the backward of this z
-  if (rc) return rc;
-  STOVE_TRY(jb.join());
-  STOVE_LAUNCH(scene_assemble_fwd_k, dim3((n_frames + 255) / 256), dim3(256), 0, st, saved + L.bg_out, saved + L.obj_ll,
-                     saved + L.ovl, z, ll, parts, n_obj, n_frames, overlap_beta, logf(overlap_beta));
-  STOVE_LAUNCH_CHECK();
-  return 0;
-}
-
-// ws = [ d_obj (np) | d_ovl (np) | dzc (np*NMAX*4) | dz_bg (np*4) | obj table-gradient chunk partials | bg ws ]
-struct SceneWs {
-  size_t d_obj, d_ovl, dzc, dz_bg, obj, bg, total;
-};
-static SceneWs scene_ws_layout(int nf, int n_obj) {
-  const size_t np = (size_t)nf * n_obj;
-  SceneWs s;
-  s.d_obj = 0;
-  s.d_ovl = s.d_obj + align64(np);
-  s.dzc = s.d_ovl + align64(np);
-  s.dz_bg = s.dzc + align64(np * nmax_of(n_obj) * 4);
-  s.obj = s.dz_bg + align64(np * 4);
-  s.bg = s.obj + align64(objspn_partial_floats());
-  s.total = s.bg + align64(bgspn_bwd_ws_floats(nf, n_obj));
-  return s;
-}
-
-size_t stove_scene_bwd_ws_bytes(int n_frames, int n_obj) { return scene_ws_layout(n_frames, n_obj).total * sizeof(float); }
-
-constexpr int kLateTableGradGlimpses = 16384;
-// Where the object-SPN table gradients run when the caller gives a parameter stream: with up to four objects they are held back
-// until dz is out and then run underneath the recursion's backward as objspn_tablegrad_under_k (one wave per SIMD in the registers
-// and LDS that kernel leaves free).  Measured in round 2 (B = 256): the SPN backward phase 600 -> 495 us without them, the
-// recursion's backward 470 -> 545 us with them on its SIMDs, the step 3.273 -> 3.254 ms.  (The round-1 placement -- right behind
-// their producer, next to pix / bgspn_bwd -- was a switch until round 5.)
-
-size_t stove_bg_dense_floats(void) { return (size_t)kBgDenseF; }
-int stove_bg_dense(const int32_t* bg_side, const float* bg_coef, float* dense, void* stream) {
-  STOVE_LAUNCH(bg_dense_fwd_k, dim3((kBgDenseF + 255) / 256), dim3(256), 0, (hipStream_t)stream, bg_side, bg_coef, dense);
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  SceneCall c(frames, z, n_frames, n_obj, stream, fork_from);
+  if (frame_map(n_frames, seq_frames, seq_stride, &c.fm)) return (int)hipErrorInvalidValue;
+  c.L = scene_saved_tuned(n_frames, n_obj);
+  c.saved = saved;
+  return scene_forward(
+      c, overlap_beta, ll, parts, [&] { return scene_obj_fwd<false>(c, t, saved, with_grad); },
+      [&] {
+        int rc = bgspn_forward(frames, nullptr, z, n_obj, t->bg_side, t->bg_coef, t->bg_wroot, saved + c.L.bg_ell, saved + c.L.bg_out, n_frames,
+                               c.sb, c.fm, t->bg_dense);
+        if (rc) return rc;
+        return bg_cover_tables(z, saved + c.L.bg_aux, n_frames, n_obj, c.sb);       // for the backward of this z
+      });
 }
 
 int stove_scene_bwd(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames,
@@ -396,30 +535,25 @@ int stove_scene_bwd_overlap(const StoveSpnTables* t, const float* frames, const 
   return stove_scene_bwd_from(t, frames, z, n_frames, n_obj, seq_frames, seq_stride, overlap_beta, saved, dll, dz, g, ws_, stream, param_stream, stream);
 }
 
+constexpr int kLateTableGradGlimpses = 16384;
+// Where the object-SPN table gradients run when the caller gives a parameter stream: with up to four objects they are held back
+// until dz is out and then run underneath the recursion's backward as objspn_tablegrad_under_k (one wave per SIMD in the registers
+// and LDS that kernel leaves free).  Measured in round 2 (B = 256): the SPN backward phase 600 -> 495 us without them, the
+// recursion's backward 470 -> 545 us with them on its SIMDs, the step 3.273 -> 3.254 ms.  (The round-1 placement -- right behind
+// their producer, next to pix / bgspn_bwd -- was a switch until round 5.)
+
 // fork_from: see stove_scene_fwd_from (the background chain's inputs -- frames, z, saved, dll -- must be ready in its order)
 int stove_scene_bwd_from(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames,
                          int seq_stride, float overlap_beta, const float* saved, const float* dll, float* dz,
                          StoveSpnTableGrads* g, void* ws_, void* stream, void* param_stream, void* fork_from) {
   STOVE_VALIDATE(scene_bwd(t, frames, z, n_frames, n_obj, seq_frames, seq_stride, saved, dll, dz, g, ws_));
-  hipStream_t st = (hipStream_t)stream;
-  hipStream_t root = fork_from != nullptr ? (hipStream_t)fork_from : st;
-  hipStream_t sp = param_stream != nullptr ? (hipStream_t)param_stream : st;
   if (n_frames == 0) return 0;
-  FrameMap fm;
-  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
-  float* ws = (float*)ws_;
-  const SceneSaved L = scene_saved_layout(n_frames, n_obj);
-  const SceneWs W = scene_ws_layout(n_frames, n_obj);
-  const int np = n_frames * n_obj;
-  STOVE_LAUNCH(scene_assemble_bwd_k, dim3((np + 255) / 256), dim3(256), 0, st, dll, z, ws + W.d_obj, ws + W.d_ovl, n_obj, np, overlap_beta);
-  STOVE_LAUNCH_CHECK();
-  hipStream_t sb = scene_fork_stream(st);       // background chain next to the object chain, joined before the tail
-  STOVE_TRY(stream_after(sb, root));
-  JoinGuard jb(st, sb);                         // error paths: the tail below is what joins `sb` normally
-  JoinGuard jp(st, sp);                         // error paths only: the caller joins the parameter stream after a clean return
-  // The object SPN's backward already ran, at unit upstream gradient, inside the forward (objspn_fwd_unit_k): what is left is to
-  // apply d_obj[patch] where its scratch is consumed -- the tail below and the table gradients.
-  int rc = 0;
+  SceneCall c(frames, z, n_frames, n_obj, stream, fork_from, param_stream);
+  if (frame_map(n_frames, seq_frames, seq_stride, &c.fm)) return (int)hipErrorInvalidValue;
+  c.L = scene_saved_tuned(n_frames, n_obj);
+  c.saved = saved;
+  c.W = scene_ws_tuned(n_frames, n_obj);
+  c.ws = (float*)ws_;
   // The object-SPN table gradients go to the parameter stream once dz is out (underneath what the caller enqueues next, the
   // recursion's backward) ...
   // ... for up to four objects: that recursion (dyn_loop_bwd_small_k<4, ..>: 253 + 58 registers, one wave per SIMD on every CU at
@@ -430,40 +564,21 @@ int stove_scene_bwd_from(const StoveSpnTables* t, const float* frames, const flo
   // ... and for a batch large enough that the recursion's backward is long (98 steps): at the reference's default training shape
   // (256 clips x 8 frames: 6 912 glimpses, a 35 us recursion) the held-back table gradients would be the head of a 260 us chain of
   // small launches on the parameter stream that outlasts the main stream by 110 us -- there they start at once, beside the data half
-  const bool late = sp != st && n_obj <= 4 && np >= kLateTableGradGlimpses;
-  if (!late) {
-    STOVE_TRY(stream_after(sp, st));
-    rc = objspn_backward_params(saved + L.xw, t->obj_scope, g->obj_coef, g->obj_wsum, g->obj_wroot, saved + L.obj_scratch, ws + W.obj,
-                                ws + W.d_obj, np, sp);
-    if (rc) return rc;
-  }
-  // (dz = null: the per-half partial images of dz_bg stay where bgspn_bwd_k wrote them; the tail's last kernel sums them)
-  rc = bgspn_backward(frames, nullptr, z, n_obj, t->bg_side, t->bg_coef, t->bg_wroot, saved + L.bg_ell, saved + L.bg_out, dll,
-                      nullptr, nullptr, nullptr, g->bg_coef, g->bg_wroot, ws + W.bg, n_frames, sb, sp == st ? sb : sp, fm, saved + L.cover);
-  if (rc) return rc;
-  const float* dz_bg_parts = bgspn_dz_parts(ws + W.bg, n_frames);
-  // the tail joins `sb` before its last kernel (dz_bg; without a parameter stream also the bg table grads)
-  if (n_obj <= 3)
-    rc = scene_bwd_tail<3>(frames, z, saved + L.xw, saved + L.obj_scratch, t->obj_leaf_slot, t->obj_coef, ws + W.d_ovl, ws + W.dzc, dll, saved + L.obj_ll,
-                           dz_bg_parts, dz, n_obj, np, st, sb, fm, ws + W.d_obj, kBgHalves);
-  else if (n_obj <= 6)
-    rc = scene_bwd_tail<6>(frames, z, saved + L.xw, saved + L.obj_scratch, t->obj_leaf_slot, t->obj_coef, ws + W.d_ovl, ws + W.dzc, dll, saved + L.obj_ll,
-                           dz_bg_parts, dz, n_obj, np, st, sb, fm, ws + W.d_obj, kBgHalves);
-  else if (n_obj <= 8)
-    rc = scene_bwd_tail<8>(frames, z, saved + L.xw, saved + L.obj_scratch, t->obj_leaf_slot, t->obj_coef, ws + W.d_ovl, ws + W.dzc, dll, saved + L.obj_ll,
-                           dz_bg_parts, dz, n_obj, np, st, sb, fm, ws + W.d_obj, kBgHalves);
-  else
-    rc = (int)hipErrorInvalidValue;
-  if (rc) return rc;
-  jb.dismiss();                                 // scene_bwd_tail joined `sb`
-  if (late) {
-    STOVE_TRY(stream_after(sp, st));
-    rc = objspn_backward_params(saved + L.xw, t->obj_scope, g->obj_coef, g->obj_wsum, g->obj_wroot, saved + L.obj_scratch, ws + W.obj,
-                                ws + W.d_obj, np, sp, true);
-    if (rc) return rc;
-  }
-  jp.dismiss();
-  return 0;
+  const bool late = c.sp != c.st && n_obj <= 4 && c.np >= kLateTableGradGlimpses;
+  return scene_backward(
+      c, dll, dz, overlap_beta, nmax_of(n_obj), bgspn_dz_parts(c.ws + c.W.bg, n_frames), kBgHalves,
+      [&] {
+        if (!late) {
+          const int rc = scene_obj_tablegrads(c, t, g);
+          if (rc) return rc;
+        }
+        // (dz = null: the per-half partial images of dz_bg stay where bgspn_bwd_k wrote them; the finalize kernel sums them.  Without a
+        // parameter stream the background's table gradients stay on the fork stream, joined before that kernel as well)
+        return bgspn_backward(frames, nullptr, z, n_obj, t->bg_side, t->bg_coef, t->bg_wroot, saved + c.L.bg_ell, saved + c.L.bg_out, dll, nullptr,
+                              nullptr, nullptr, g->bg_coef, g->bg_wroot, c.ws + c.W.bg, n_frames, c.sb, c.sp == c.st ? c.sb : c.sp, c.fm,
+                              saved + c.L.bg_aux);
+      },
+      [&] { return scene_obj_bwd<false>(c, t); }, [&] { return late ? scene_obj_tablegrads(c, t, g, true) : 0; });
 }
 
 // ---------------------------------------------------------------- object RAT-SPN operator, any glimpse size / vector widths
@@ -506,182 +621,75 @@ int stove_gauss_ll_bwd(const float* x, const float* marg, const float* dout, flo
 // The object side is the 32 x 32 path's own kernels with the geometry at run time (scene_tile_fwd_k / scene_pixtile_bwd_k <.., ANY>,
 // objspn_fwd_unit_k, the table-gradient kernels); the background side is the mask in closed form (bg_mask_any_k), the general-size
 // operator of spn_bg_generic.hip, and the mask's backward to z (bg_mask_bwd_any_k).
-// saved = [ xw tile | obj_ll | ovl | bg_out | bg_ell (n x halves x 36) | mask (n x n_pix) | object-SPN scratch at unit gradient ]
-struct SceneSavedAny {
-  size_t xw, obj_ll, ovl, bg_out, bg_ell, mask, obj_scratch, total;
-};
-// frames up to kBgTabMax a side: the background kernels form the mask themselves from per-frame coverage tables (spn_bg_generic.hip), no
-// mask image is kept
-static bool scene_any_inline(int W, int H) { return W <= kBgTabMax && H <= kBgTabMax; }
-static SceneSavedAny scene_saved_layout_any(int nf, int n_obj, int n_pix, bool with_grad, bool inline_mask = false) {
-  const size_t np = (size_t)nf * n_obj;
-  SceneSavedAny s;
-  s.xw = 0;
-  s.obj_ll = align64(stove_objspn_tile_floats((int)np));
-  s.ovl = s.obj_ll + align64(np);
-  s.bg_out = s.ovl + align64(np);
-  s.bg_ell = s.bg_out + align64(nf);
-  s.mask = s.bg_ell + align64(bgspn_any_saved_floats(nf, n_pix));
-  s.obj_scratch = s.mask + (inline_mask ? 0 : align64((size_t)nf * n_pix));
-  s.total = s.obj_scratch + (with_grad ? align64(objspn_scratch_floats((int)np)) : 0);
-  return s;
+// saved: bg_ell is (n x halves x 36), bg_aux the mask (n x n_pix)
+static SceneSaved scene_saved_any(int nf, int n_obj, int n_pix, bool with_grad, bool inline_mask = false) {
+  return scene_saved_layout(nf, n_obj, with_grad, bgspn_any_saved_floats(nf, n_pix), inline_mask ? 0 : (size_t)nf * n_pix);
 }
-struct SceneWsAny {
-  size_t d_obj, d_ovl, dzc, dz_bg, obj, d_mask, bg, total;
-};
-static SceneWsAny scene_ws_layout_any(int nf, int n_obj, int n_pix) {
-  const size_t np = (size_t)nf * n_obj;
-  SceneWsAny s;
-  s.d_obj = 0;
-  s.d_ovl = s.d_obj + align64(np);
-  s.dzc = s.d_ovl + align64(np);
-  s.dz_bg = s.dzc + align64(np * nmax_of(n_obj) * 4);
-  s.obj = s.dz_bg + align64(np * 4);
-  s.d_mask = s.obj + align64(objspn_partial_floats());
-  s.bg = s.d_mask + align64((size_t)nf * n_pix);
-  s.total = s.bg + align64(bgspn_any_bwd_ws_floats(nf, n_pix));
-  return s;
+static SceneWs scene_ws_any(int nf, int n_obj, int n_pix) {
+  return scene_ws_layout((size_t)nf * n_obj, nmax_of(n_obj), 0, objspn_partial_floats(), (size_t)nf * n_pix, bgspn_any_bwd_ws_floats(nf, n_pix));
 }
-size_t stove_scene_saved_floats_any(int n_frames, int n_obj, int n_pix, int with_grad) { return scene_saved_layout_any(n_frames, n_obj, n_pix, with_grad != 0).total; }
-size_t stove_scene_bwd_ws_bytes_any(int n_frames, int n_obj, int n_pix) { return scene_ws_layout_any(n_frames, n_obj, n_pix).total * sizeof(float); }
+size_t stove_scene_saved_floats_any(int n_frames, int n_obj, int n_pix, int with_grad) { return scene_saved_any(n_frames, n_obj, n_pix, with_grad != 0).total; }
+size_t stove_scene_bwd_ws_bytes_any(int n_frames, int n_obj, int n_pix) { return scene_ws_any(n_frames, n_obj, n_pix).total * sizeof(float); }
 
 int stove_scene_fwd_any(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride,
                         int W, int H, int align_corners, float overlap_beta, float* ll, float* parts, float* saved, void* stream, int with_grad) {
   STOVE_VALIDATE(scene_fwd(t, frames, z, n_frames, n_obj, seq_frames, seq_stride, ll, saved));
-  hipStream_t st = (hipStream_t)stream;
   if (n_frames == 0) return 0;
   if (W < 2 || H < 2 || n_obj < 1 || n_obj > 8) return (int)hipErrorInvalidValue;
-  FrameMap fm;
-  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
-  const int n_pix = W * H, np = n_frames * n_obj;
-  const SceneGeom gm = scene_geom(W, H, align_corners);
-  const bool inl = scene_any_inline(W, H);
-  const SceneSavedAny L = scene_saved_layout_any(n_frames, n_obj, n_pix, true, inl);
-  SceneBoxes boxes;
-  boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
-  hipStream_t sb = scene_fork_stream(st);
-  STOVE_TRY(stream_after(sb, st));
-  JoinGuard jb(st, sb);
-  int rc = n_obj <= 3 ? scene_tile_fwd_g<3>(frames, z, saved + L.xw, n_obj, np, st, fm, gm)
-                      : (n_obj <= 6 ? scene_tile_fwd_g<6>(frames, z, saved + L.xw, n_obj, np, st, fm, gm) : scene_tile_fwd_g<8>(frames, z, saved + L.xw, n_obj, np, st, fm, gm));
-  if (rc) return rc;
-  if (with_grad)
-    rc = objspn_forward_unit(saved + L.xw, t->obj_scope, t->obj_coef, t->obj_wsum, t->obj_wroot, saved + L.obj_ll, saved + L.ovl,
-                             saved + L.obj_scratch, np, st);
-  else
-    rc = objspn_forward(saved + L.xw, t->obj_scope, t->obj_coef, t->obj_wsum, t->obj_wroot, saved + L.obj_ll, saved + L.ovl, np, st);
-  if (rc) return rc;
-  if (!inl) {
-    const size_t tot = (size_t)n_frames * n_pix;
-    STOVE_LAUNCH(bg_mask_any_k, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sb, z, saved + L.mask, n_frames, n_obj, gm);
-    STOVE_LAUNCH_CHECK();
-  }
-  rc = bgspn_any_forward(frames, inl ? nullptr : saved + L.mask, t->bg_side, t->bg_coef, t->bg_wroot, saved + L.bg_ell, saved + L.bg_out, n_frames,
-                         n_pix, sb, fm, boxes);
-  if (rc) return rc;
-  STOVE_TRY(jb.join());
-  STOVE_LAUNCH(scene_assemble_fwd_k, dim3((n_frames + 255) / 256), dim3(256), 0, st, saved + L.bg_out, saved + L.obj_ll,
-               saved + L.ovl, z, ll, parts, n_obj, n_frames, overlap_beta, logf(overlap_beta));
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  SceneCall c(frames, z, n_frames, n_obj, stream);
+  if (frame_map(n_frames, seq_frames, seq_stride, &c.fm)) return (int)hipErrorInvalidValue;
+  c.geometry(W, H, align_corners, 1);
+  c.L = scene_saved_any(n_frames, n_obj, W * H, true, c.inl);
+  c.saved = saved;
+  return scene_forward(
+      c, overlap_beta, ll, parts, [&] { return scene_obj_fwd<true>(c, t, saved, with_grad); },
+      [&] { return scene_bg_fwd_any(c, t->bg_side, t->bg_coef, t->bg_wroot, saved); });
 }
 
 int stove_scene_bwd_any(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames, int seq_stride,
                         int W, int H, int align_corners, float overlap_beta, const float* saved, const float* dll, float* dz,
                         StoveSpnTableGrads* g, void* ws_, void* stream, void* param_stream) {
   STOVE_VALIDATE(scene_bwd(t, frames, z, n_frames, n_obj, seq_frames, seq_stride, saved, dll, dz, g, ws_));
-  hipStream_t st = (hipStream_t)stream;
-  hipStream_t sp = param_stream != nullptr ? (hipStream_t)param_stream : st;
   if (n_frames == 0) return 0;
   if (W < 2 || H < 2 || n_obj < 1 || n_obj > 8) return (int)hipErrorInvalidValue;
-  FrameMap fm;
-  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
-  float* ws = (float*)ws_;
-  const int n_pix = W * H, np = n_frames * n_obj;
-  const SceneGeom gm = scene_geom(W, H, align_corners);
-  const bool inl = scene_any_inline(W, H);
-  const SceneSavedAny L = scene_saved_layout_any(n_frames, n_obj, n_pix, true, inl);
-  const SceneWsAny Wl = scene_ws_layout_any(n_frames, n_obj, n_pix);
-  SceneBoxes boxes;
-  boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
-  STOVE_LAUNCH(scene_assemble_bwd_k, dim3((np + 255) / 256), dim3(256), 0, st, dll, z, ws + Wl.d_obj, ws + Wl.d_ovl, n_obj, np, overlap_beta);
-  STOVE_LAUNCH_CHECK();
-  hipStream_t sb = scene_fork_stream(st);
-  STOVE_TRY(stream_after(sb, st));
-  JoinGuard jb(st, sb);
-  JoinGuard jp(st, sp);
-  // background chain: operator backward (d mask, table gradients), then the mask's backward to z
-  int rc = bgspn_any_backward(frames, inl ? nullptr : saved + L.mask, t->bg_side, t->bg_coef, t->bg_wroot, saved + L.bg_ell, saved + L.bg_out, dll,
-                              nullptr, ws + Wl.d_mask, g->bg_coef, g->bg_wroot, ws + Wl.bg, n_frames, n_pix, sb, fm, boxes);
-  if (rc) return rc;
-  if (n_obj <= 3) STOVE_LAUNCH((bg_mask_bwd_any_k<3>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, 1);
-  else STOVE_LAUNCH((bg_mask_bwd_any_k<8>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, 1);
-  STOVE_LAUNCH_CHECK();
-  // object chain: pixel / transformer backward from the unit-gradient scratch, then the per-object sums with dz_bg
-  const float* d_obj = ws + Wl.d_obj;
-  if (n_obj <= 3)
-    rc = scene_pixtile_bwd<3, true>(frames, z, saved + L.xw, saved + L.obj_scratch, t->obj_leaf_slot, t->obj_coef, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, st, fm, d_obj, gm);
-  else if (n_obj <= 6)
-    rc = scene_pixtile_bwd<6, true>(frames, z, saved + L.xw, saved + L.obj_scratch, t->obj_leaf_slot, t->obj_coef, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, st, fm, d_obj, gm);
-  else
-    rc = scene_pixtile_bwd<8, true>(frames, z, saved + L.xw, saved + L.obj_scratch, t->obj_leaf_slot, t->obj_coef, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, st, fm, d_obj, gm);
-  if (rc) return rc;
-  STOVE_TRY(jb.join());
-  if (n_obj <= 3) STOVE_LAUNCH((scene_finalize_bwd_k<3>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
-  else if (n_obj <= 6) STOVE_LAUNCH((scene_finalize_bwd_k<6>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
-  else STOVE_LAUNCH((scene_finalize_bwd_k<8>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
-  STOVE_LAUNCH_CHECK();
-  // table gradients of the object SPN on the parameter stream (the background's are complete in `st` order: ordered into it as well)
-  STOVE_TRY(stream_after(sp, st));
-  rc = objspn_backward_params(saved + L.xw, t->obj_scope, g->obj_coef, g->obj_wsum, g->obj_wroot, saved + L.obj_scratch, ws + Wl.obj, ws + Wl.d_obj, np, sp);
-  if (rc) return rc;
-  jp.dismiss();
-  return 0;
+  SceneCall c(frames, z, n_frames, n_obj, stream, nullptr, param_stream);
+  if (frame_map(n_frames, seq_frames, seq_stride, &c.fm)) return (int)hipErrorInvalidValue;
+  c.geometry(W, H, align_corners, 1);
+  c.L = scene_saved_any(n_frames, n_obj, W * H, true, c.inl);
+  c.saved = saved;
+  c.W = scene_ws_any(n_frames, n_obj, W * H);
+  c.ws = (float*)ws_;
+  return scene_backward(
+      c, dll, dz, overlap_beta, nmax_of(n_obj), c.ws + c.W.dz_bg, 1,
+      [&] { return scene_bg_bwd_any(c, t->bg_side, t->bg_coef, t->bg_wroot, dll, g->bg_coef, g->bg_wroot); },
+      [&] { return scene_obj_bwd<true>(c, t); },
+      // the table gradients of the object SPN last (the background's are complete in `st` order: ordered into the parameter stream too)
+      [&] { return scene_obj_tablegrads(c, t, g); });
 }
 
 // ---------------------------------------------------------------- fused scene likelihood over C colour channels
 // Glimpses and masks of every channel in one pass (scene_colour_fwd_k), the general-size object SPN on C * pw * ph dimensions, the
 // general-size background SPN on C * W * H dimensions with one mask plane for all channels; backward: the object SPN's data and table
 // gradients, the glimpse backward to z (scene_colour_bwd_k), the background's mask backward with the C planes summed.
-// saved = [ patches | marg | object-SPN saved | obj_ll | ovl | bg_out | bg_ell | mask (frames past kBgTabMax a side) ]
 // the colour kernels come in two object-count instantiations (3 and 8: the 6-object one ran at the 8-object one's occupancy); dzc has
 // nmax_ch(n_obj) entries per glimpse
 static inline int nmax_ch(int n_obj) { return n_obj <= 3 ? 3 : 8; }
-struct SceneSavedCh {
-  size_t patches, marg, obj, obj_ll, ovl, bg_out, bg_ell, mask, total;
-};
-static SceneSavedCh scene_saved_layout_ch(int nf, int n_obj, int C, int W, int H, const ObjAnyShape& sh) {
+// saved = [ patches | marg | object-SPN saved | obj_ll | ovl | bg_out | bg_ell | mask (frames past kBgTabMax a side) ]
+static SceneSaved scene_saved_ch(int nf, int n_obj, int C, int W, int H, const ObjAnyShape& sh) {
   const size_t np = (size_t)nf * n_obj;
-  SceneSavedCh s;
-  s.patches = 0;
-  s.marg = s.patches + align64(np * sh.D);
-  s.obj = s.marg + align64(np * sh.D);
-  s.obj_ll = s.obj + align64(objany_saved_floats((int)np, sh));
-  s.ovl = s.obj_ll + align64(np);
-  s.bg_out = s.ovl + align64(np);
-  s.bg_ell = s.bg_out + align64(nf);
-  s.mask = s.bg_ell + align64(bgspn_any_saved_floats(nf, C * W * H));
-  s.total = s.mask + (scene_any_inline(W, H) ? 0 : align64((size_t)nf * W * H));
+  Layout l;
+  SceneSaved s{};
+  s.patches = l.take(np * sh.D);
+  s.marg = l.take(np * sh.D);
+  s.obj = l.take(objany_saved_floats((int)np, sh));
+  scene_saved_shared(l, s, nf, np, bgspn_any_saved_floats(nf, C * W * H), scene_any_inline(W, H) ? 0 : (size_t)nf * W * H);
+  s.total = l.total;
   return s;
 }
 // ws = [ d_obj | d_ovl | dzc | dz_bg | d_patch | d_marg | object-SPN ws | d_mask (C planes) | background ws ]
-struct SceneWsCh {
-  size_t d_obj, d_ovl, dzc, dz_bg, d_patch, d_marg, obj, d_mask, bg, total;
-};
-static SceneWsCh scene_ws_layout_ch(int nf, int n_obj, int C, int W, int H, const ObjAnyShape& sh) {
+static SceneWs scene_ws_ch(int nf, int n_obj, int C, int W, int H, const ObjAnyShape& sh) {
   const size_t np = (size_t)nf * n_obj, n_pix = (size_t)C * W * H;
-  SceneWsCh s;
-  s.d_obj = 0;
-  s.d_ovl = s.d_obj + align64(np);
-  s.dzc = s.d_ovl + align64(np);
-  s.dz_bg = s.dzc + align64(np * nmax_ch(n_obj) * 4);
-  s.d_patch = s.dz_bg + align64(np * 4);
-  s.d_marg = s.d_patch + align64(np * sh.D);
-  s.obj = s.d_marg + align64(np * sh.D);
-  s.d_mask = s.obj + align64(objany_bwd_ws_floats((int)np, sh));
-  s.bg = s.d_mask + align64((size_t)nf * n_pix);
-  s.total = s.bg + align64(bgspn_any_bwd_ws_floats(nf, (int)n_pix));
-  return s;
+  return scene_ws_layout(np, nmax_ch(n_obj), np * sh.D, objany_bwd_ws_floats((int)np, sh), (size_t)nf * n_pix, bgspn_any_bwd_ws_floats(nf, (int)n_pix));
 }
 static GlimpseGeom glimpse_geom(int pw, int ph, int align_corners) {
   GlimpseGeom g;
@@ -695,10 +703,10 @@ static GlimpseGeom glimpse_geom(int pw, int ph, int align_corners) {
 }
 size_t stove_scene_saved_floats_ch(int n_frames, int n_obj, int channels, int W, int H, int R, int G, int S, int D, int Lmax, int with_grad) {
   (void)with_grad;                // the object SPN's saved activations are the same with and without a backward to come
-  return scene_saved_layout_ch(n_frames, n_obj, channels, W, H, obj_any_shape(R, G, S, D, Lmax)).total;
+  return scene_saved_ch(n_frames, n_obj, channels, W, H, obj_any_shape(R, G, S, D, Lmax)).total;
 }
 size_t stove_scene_bwd_ws_bytes_ch(int n_frames, int n_obj, int channels, int W, int H, int R, int G, int S, int D, int Lmax) {
-  return scene_ws_layout_ch(n_frames, n_obj, channels, W, H, obj_any_shape(R, G, S, D, Lmax)).total * sizeof(float);
+  return scene_ws_ch(n_frames, n_obj, channels, W, H, obj_any_shape(R, G, S, D, Lmax)).total * sizeof(float);
 }
 
 int stove_scene_fwd_ch(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
@@ -709,41 +717,25 @@ int stove_scene_fwd_ch(const int32_t* lscope, const int32_t* slot, const float* 
   (void)with_grad;
   STOVE_VALIDATE(scene_ch_fwd(lscope, coef, wsum, wroot, R, G, S, D, Lmax, bg_side, bg_coef, bg_wroot, bg_coef_floats, frames, z, n_frames, n_obj,
                               seq_frames, seq_stride, channels, W, H, pw, ph, ll, saved));
-  hipStream_t st = (hipStream_t)stream;
   if (n_frames == 0) return 0;
-  FrameMap fm;
-  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
+  SceneCall c(frames, z, n_frames, n_obj, stream);
+  if (frame_map(n_frames, seq_frames, seq_stride, &c.fm)) return (int)hipErrorInvalidValue;
   const ObjAnyShape sh = obj_any_shape(R, G, S, D, Lmax);
-  const int plane = W * H, n_pix = channels * plane, np = n_frames * n_obj;
-  const SceneGeom gm = scene_geom(W, H, align_corners);
   const GlimpseGeom gg = glimpse_geom(pw, ph, align_corners);
-  const bool inl = scene_any_inline(W, H);
-  const SceneSavedCh L = scene_saved_layout_ch(n_frames, n_obj, channels, W, H, sh);
-  SceneBoxes boxes;
-  boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
-  hipStream_t sb = scene_fork_stream(st);
-  STOVE_TRY(stream_after(sb, st));
-  JoinGuard jb(st, sb);
-  // object chain: glimpses + masks of every channel, the object SPN over C * pw * ph dimensions
-  int rc = n_obj <= 3 ? scene_colour_fwd<3>(frames, z, saved + L.patches, saved + L.marg, saved + L.ovl, n_obj, np, channels, st, fm, gm, gg)
-                      : scene_colour_fwd<8>(frames, z, saved + L.patches, saved + L.marg, saved + L.ovl, n_obj, np, channels, st, fm, gm, gg);
-  if (rc) return rc;
-  rc = objany_forward(saved + L.patches, saved + L.marg, lscope, coef, wsum, wroot, saved + L.obj, saved + L.obj_ll, np, sh, st);
-  if (rc) return rc;
-  // background chain: one mask plane for the C channels
-  if (!inl) {
-    const size_t tot = (size_t)n_frames * plane;
-    STOVE_LAUNCH(bg_mask_any_k, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, sb, z, saved + L.mask, n_frames, n_obj, gm);
-    STOVE_LAUNCH_CHECK();
-  }
-  rc = bgspn_any_forward(frames, inl ? nullptr : saved + L.mask, bg_side, bg_coef, bg_wroot, saved + L.bg_ell, saved + L.bg_out, n_frames, n_pix, sb,
-                         fm, boxes, plane);
-  if (rc) return rc;
-  STOVE_TRY(jb.join());
-  STOVE_LAUNCH(scene_assemble_fwd_k, dim3((n_frames + 255) / 256), dim3(256), 0, st, saved + L.bg_out, saved + L.obj_ll,
-               saved + L.ovl, z, ll, parts, n_obj, n_frames, overlap_beta, logf(overlap_beta));
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  c.geometry(W, H, align_corners, channels);
+  c.L = scene_saved_ch(n_frames, n_obj, channels, W, H, sh);
+  c.saved = saved;
+  float *patches = saved + c.L.patches, *marg = saved + c.L.marg;
+  return scene_forward(
+      c, overlap_beta, ll, parts,
+      [&] {      // glimpses + masks of every channel, the object SPN over C * pw * ph dimensions
+        int rc = with_nmax<false>(n_obj, [&](auto n) {
+          return scene_colour_fwd<decltype(n)::value>(frames, z, patches, marg, saved + c.L.ovl, n_obj, c.np, channels, c.st, c.fm, c.gm, gg);
+        });
+        if (rc) return rc;
+        return objany_forward(patches, marg, lscope, coef, wsum, wroot, saved + c.L.obj, saved + c.L.obj_ll, c.np, sh, c.st);
+      },
+      [&] { return scene_bg_fwd_any(c, bg_side, bg_coef, bg_wroot, saved); });
 }
 
 int stove_scene_bwd_ch(const int32_t* lscope, const int32_t* slot, const float* coef, const float* wsum, const float* wroot, int R, int G, int S,
@@ -754,51 +746,31 @@ int stove_scene_bwd_ch(const int32_t* lscope, const int32_t* slot, const float* 
   STOVE_VALIDATE(scene_ch_bwd(lscope, slot, coef, wsum, wroot, R, G, S, D, Lmax, bg_side, bg_coef, bg_wroot, bg_coef_floats, frames, z, n_frames,
                               n_obj, seq_frames, seq_stride, channels, W, H, pw, ph, saved, dll, dz, g_coef, g_wsum, g_wroot, g_bg_coef, g_bg_wroot,
                               ws_));
-  hipStream_t st = (hipStream_t)stream;
-  hipStream_t sp = param_stream != nullptr ? (hipStream_t)param_stream : st;
   if (n_frames == 0) return 0;
-  FrameMap fm;
-  if (frame_map(n_frames, seq_frames, seq_stride, &fm)) return (int)hipErrorInvalidValue;
-  float* ws = (float*)ws_;
+  SceneCall c(frames, z, n_frames, n_obj, stream, nullptr, param_stream);
+  if (frame_map(n_frames, seq_frames, seq_stride, &c.fm)) return (int)hipErrorInvalidValue;
   const ObjAnyShape sh = obj_any_shape(R, G, S, D, Lmax);
-  const int plane = W * H, n_pix = channels * plane, np = n_frames * n_obj;
-  const SceneGeom gm = scene_geom(W, H, align_corners);
   const GlimpseGeom gg = glimpse_geom(pw, ph, align_corners);
-  const bool inl = scene_any_inline(W, H);
-  const SceneSavedCh L = scene_saved_layout_ch(n_frames, n_obj, channels, W, H, sh);
-  const SceneWsCh Wl = scene_ws_layout_ch(n_frames, n_obj, channels, W, H, sh);
-  SceneBoxes boxes;
-  boxes.z = inl ? z : nullptr; boxes.n_obj = n_obj; boxes.gm = gm;
-  STOVE_LAUNCH(scene_assemble_bwd_k, dim3((np + 255) / 256), dim3(256), 0, st, dll, z, ws + Wl.d_obj, ws + Wl.d_ovl, n_obj, np, overlap_beta);
-  STOVE_LAUNCH_CHECK();
-  hipStream_t sb = scene_fork_stream(st);
-  STOVE_TRY(stream_after(sb, st));
-  JoinGuard jb(st, sb);
-  JoinGuard jp(st, sp);
-  // background chain: operator backward (d mask of every plane, table gradients), then the mask's backward to z
-  int rc = bgspn_any_backward(frames, inl ? nullptr : saved + L.mask, bg_side, bg_coef, bg_wroot, saved + L.bg_ell, saved + L.bg_out, dll, nullptr,
-                              ws + Wl.d_mask, g_bg_coef, g_bg_wroot, ws + Wl.bg, n_frames, n_pix, sb, fm, boxes, plane);
-  if (rc) return rc;
-  if (n_obj <= 3) STOVE_LAUNCH((bg_mask_bwd_any_k<3>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, channels);
-  else STOVE_LAUNCH((bg_mask_bwd_any_k<8>), dim3(n_frames), dim3(256), 0, sb, z, (const float*)(ws + Wl.d_mask), ws + Wl.dz_bg, n_frames, n_obj, gm, channels);
-  STOVE_LAUNCH_CHECK();
-  // object chain: the SPN's data and table gradients, then the glimpse backward to z
-  rc = objany_backward(saved + L.patches, saved + L.marg, lscope, slot, coef, wsum, wroot, saved + L.obj, ws + Wl.d_obj, ws + Wl.d_patch,
-                       ws + Wl.d_marg, g_coef, g_wsum, g_wroot, ws + Wl.obj, np, sh, st);
-  if (rc) return rc;
-  if (n_obj <= 3)
-    rc = scene_colour_bwd<3>(frames, z, ws + Wl.d_patch, ws + Wl.d_marg, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, channels, st, fm, gm, gg);
-  else
-    rc = scene_colour_bwd<8>(frames, z, ws + Wl.d_patch, ws + Wl.d_marg, ws + Wl.d_ovl, ws + Wl.dzc, n_obj, np, channels, st, fm, gm, gg);
-  if (rc) return rc;
-  STOVE_TRY(jb.join());
-  if (n_obj <= 3) STOVE_LAUNCH((scene_finalize_bwd_k<3>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
-  else STOVE_LAUNCH((scene_finalize_bwd_k<8>), dim3((np + 255) / 256), dim3(256), 0, st, dll, z, saved + L.obj_ll, ws + Wl.dz_bg, ws + Wl.dzc, dz, n_obj, np, 1);
-  STOVE_LAUNCH_CHECK();
-  // every table gradient is complete in `st` order: the parameter stream is ordered behind it
-  STOVE_TRY(stream_after(sp, st));
-  jp.dismiss();
-  return 0;
+  c.geometry(W, H, align_corners, channels);
+  c.L = scene_saved_ch(n_frames, n_obj, channels, W, H, sh);
+  c.saved = saved;
+  c.W = scene_ws_ch(n_frames, n_obj, channels, W, H, sh);
+  c.ws = (float*)ws_;
+  float *d_patch = c.ws + c.W.d_patch, *d_marg = c.ws + c.W.d_marg;
+  return scene_backward(
+      c, dll, dz, overlap_beta, nmax_ch(n_obj), c.ws + c.W.dz_bg, 1,
+      [&] { return scene_bg_bwd_any(c, bg_side, bg_coef, bg_wroot, dll, g_bg_coef, g_bg_wroot); },
+      [&] {      // the object SPN's data and table gradients, then the glimpse backward to z
+        int rc = objany_backward(saved + c.L.patches, saved + c.L.marg, lscope, slot, coef, wsum, wroot, saved + c.L.obj, c.ws + c.W.d_obj, d_patch,
+                                 d_marg, g_coef, g_wsum, g_wroot, c.ws + c.W.obj, c.np, sh, c.st);
+        if (rc) return rc;
+        return with_nmax<false>(n_obj, [&](auto n) {
+          return scene_colour_bwd<decltype(n)::value>(frames, z, d_patch, d_marg, c.ws + c.W.d_ovl, c.ws + c.W.dzc, n_obj, c.np, channels, c.st, c.fm,
+                                                      c.gm, gg);
+        });
+      },
+      // every table gradient is complete in `st` order: the parameter stream is ordered behind it
+      [&] { return (int)stream_after(c.sp, c.st); });
 }
 
 int stove_glimpse_mean(const float* x_color, const float* z, float* emb, int n_frames, int n_obj, int channels, void* stream) {
@@ -835,7 +807,7 @@ int stove_scene_glimpses(const float* frames, const float* z, int n_frames, int 
   hipStream_t st = (hipStream_t)stream;
   const int np = n_frames * n_obj;
   if (np == 0) return 0;
-  int rc = scene_tile_fwd_any(frames, z, tile, n_obj, np, st);
+  int rc = with_nmax(n_obj, [&](auto n) { return scene_tile_fwd<decltype(n)::value>(frames, z, tile, n_obj, np, st, FrameMap{0, 0}); });
   if (rc) return rc;
   const int nb = (np + 63) / 64;
   STOVE_LAUNCH(tile_unpack_k, dim3(nb < 2048 ? nb * 25 : 2048 * 25), dim3(256), 0, st, tile, patches, keep, np, nb);
@@ -919,34 +891,15 @@ size_t stove_dynloop_act_floats(int B, int Ts, int N) {
   return blockwise;
 }
 
-// the recursion over the steps [ts0, ts1) (the whole range from the entry points; the kernels keep the piece interface of the
-// round-3 pipelining experiment, docs/experiments/r06_pipeline_pieces_removed.patch)
-static int dynloop_fwd_range(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
-                            const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred, float* act,
-                            int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
-                            int ts0, int ts1, void* stream);
-static int dynloop_bwd_range(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
-                            const float* params, const float* z, const float* act, const float* dz, const float* dzdyn,
-                            const float* dmean, const float* dstd, const float* dpred, float* dz1, float* dzsup, float* dzsstd,
-                            float* dextra, float* g_params, void* ws, int B, int Ts, int N, int sin_dim, int lim_enc, int elu,
-                            float pos_var, float vel_std, float lat_std, int ts0, int ts1, float* carry, void* stream, void* param_stream);
+// The small-graph kernels keep the piece interface of the round-3 pipelining experiment (the steps [ts0, ts1), the gradient carried
+// between pieces: docs/experiments/r06_pipeline_pieces_removed.patch) -- taking it out changes the device code of the most
+// latency-sensitive kernels, a measured change of its own.  The entry points always run the whole range: 0, Ts, no carry.
 int stove_dynloop_fwd(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
                       const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred, float* act,
                       int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
                       void* stream) {
-  return dynloop_fwd_range(z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, elu,
-                                 pos_var, vel_std, lat_std, 0, Ts, stream);
-}
-
-
-static int dynloop_fwd_range(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
-                            const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred, float* act,
-                            int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
-                            int ts0, int ts1, void* stream) {
   STOVE_VALIDATE(dynloop_fwd(z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, B, Ts, N, sin_dim));
   if (B == 0 || Ts == 0) return 0;
-  if (ts0 < 0 || ts1 > Ts || ts0 >= ts1) return (int)hipErrorInvalidValue;
-  if ((ts0 != 0 || ts1 != Ts) && !small_graph(N)) return (int)hipErrorInvalidValue;      // pieces: small-graph kernels only
   if (N < 1 || N > 8 || sin_dim < 16 || sin_dim > 32 || (sin_dim > 16 && extra == nullptr)) return (int)hipErrorInvalidValue;
   LoopConst kc{pos_var, vel_std, lat_std};
   if (small_graph(N)) {      // small graphs: (half-)wave-per-node-row formulation, two barriers per step (gnn_small.hip)
@@ -957,7 +910,7 @@ static int dynloop_fwd_range(const float* z1, const float* zsup, const float* zs
     if (rc) return rc;                                                                                                          \
     STOVE_LAUNCH((dyn_loop_fwd_small_k<SAVE_, NMX_, ELU_, NT_>), dim3(B), dim3(64 * kSmWaves), SmShape<NMX_>::kLdsFloats * sizeof(float), \
                  (hipStream_t)stream, z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, \
-                 elu, kc, g_sm_stamps, ts0, ts1);                                                                               \
+                 elu, kc, g_sm_stamps, 0, Ts);                                                                                  \
   } while (0)
 #define STOVE_LOOP_LAUNCH_E(SAVE_, ELU_)                          \
   do {                                                            \
@@ -977,7 +930,7 @@ static int dynloop_fwd_range(const float* z1, const float* zsup, const float* zs
       if (rc) return rc;
       STOVE_LAUNCH((dyn_loop_fwd_small_k<2, 4, false, 3, true>), dim3(B), dim3(64 * kSmWaves), SmShape<4>::kLdsFloats * sizeof(float), (hipStream_t)stream,
                    z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, elu, kc, g_sm_stamps,
-                   ts0, ts1);
+                   0, Ts);
     } else if (act != nullptr) {
       STOVE_LOOP_LAUNCH(2);
     } else {
@@ -1033,20 +986,8 @@ int stove_dynloop_bwd_overlap(const float* z1, const float* zsup, const float* z
                               const float* dmean, const float* dstd, const float* dpred, float* dz1, float* dzsup, float* dzsstd,
                               float* dextra, float* g_params, void* ws, int B, int Ts, int N, int sin_dim, int lim_enc, int elu,
                               float pos_var, float vel_std, float lat_std, void* stream, void* param_stream) {
-  return dynloop_bwd_range(z1, zsup, zsstd, eps, extra, params, z, act, dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra,
-                                 g_params, ws, B, Ts, N, sin_dim, lim_enc, elu, pos_var, vel_std, lat_std, 0, Ts, nullptr, stream, param_stream);
-}
-
-static int dynloop_bwd_range(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
-                            const float* params, const float* z, const float* act, const float* dz, const float* dzdyn,
-                            const float* dmean, const float* dstd, const float* dpred, float* dz1, float* dzsup, float* dzsstd,
-                            float* dextra, float* g_params, void* ws, int B, int Ts, int N, int sin_dim, int lim_enc, int elu,
-                            float pos_var, float vel_std, float lat_std, int ts0, int ts1, float* carry, void* stream, void* param_stream) {
   STOVE_VALIDATE(dynloop_bwd(z1, zsup, zsstd, eps, extra, params, z, dz1, dzsup, dzsstd, dextra, g_params, ws, B, Ts, N, sin_dim));
   hipStream_t st = (hipStream_t)stream;
-  if (ts0 < 0 || ts1 > Ts || ts0 >= ts1) return (int)hipErrorInvalidValue;
-  const bool whole = ts0 == 0 && ts1 == Ts;
-  if (!whole && (!small_bwd_path(N, act) || carry == nullptr)) return (int)hipErrorInvalidValue;
   hipStream_t sp = param_stream != nullptr ? (hipStream_t)param_stream : st;
   if (B == 0 || Ts == 0) return (int)hipErrorInvalidValue;
   if (N < 1 || N > 8 || sin_dim < 16 || sin_dim > 32 || (sin_dim > 16 && (extra == nullptr || dextra == nullptr)))
@@ -1064,7 +1005,7 @@ static int dynloop_bwd_range(const float* z1, const float* zsup, const float* zs
     if (rc) return rc;                                                                                                                \
     STOVE_LAUNCH((dyn_loop_bwd_small_k<NMX_, ELU_, NT_, HD_>), dim3(B), dim3(64 * kSmWaves), smb_lds_floats<NMX_>() * sizeof(float), st, zsup, \
                  zsstd, eps, params, const_cast<float*>(act), dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, dy, B, Ts, N, \
-                 sin_dim, lim_enc, elu, kc, g_sm_stamps, ts0, ts1, carry);                                                            \
+                 sin_dim, lim_enc, elu, kc, g_sm_stamps, 0, Ts, (float*)nullptr);                                                     \
   } while (0)
     const bool head = dz != nullptr && dzdyn != nullptr && dmean != nullptr && dstd != nullptr && dpred == nullptr && sin_dim == 16 && lim_enc == 2;
 #define STOVE_LOOPB_LAUNCH(ELU_)                                          \
@@ -1081,13 +1022,12 @@ static int dynloop_bwd_range(const float* z1, const float* zsup, const float* zs
       if (rc) return rc;
       STOVE_LAUNCH((dyn_loop_bwd_small_k<4, false, 3, true, true>), dim3(B), dim3(64 * kSmWaves), smb_lds_floats<4>() * sizeof(float), st, zsup, zsstd,
                    eps, params, const_cast<float*>(act), dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, dy, B, Ts, N, sin_dim,
-                   lim_enc, elu, kc, g_sm_stamps, ts0, ts1, carry);
+                   lim_enc, elu, kc, g_sm_stamps, 0, Ts, (float*)nullptr);
     } else if (elu) STOVE_LOOPB_LAUNCH(true);
     else STOVE_LOOPB_LAUNCH(false);
 #undef STOVE_LOOPB_LAUNCH
 #undef STOVE_LOOPB_LAUNCH_H
     STOVE_LAUNCH_CHECK();
-    if (ts0 > 0) return 0;           // the weight-gradient pass contracts the streams of ALL steps: behind the piece that ends the backward
     rc = (int)hipFuncSetAttribute((const void*)gnn_dw_small_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDwLdsFloats * sizeof(float)));
     if (rc) return rc;
     STOVE_TRY(stream_after(sp, st));        // the weight-gradient pass reads the dY streams; it only feeds the optimiser (second stream)

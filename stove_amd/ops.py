@@ -86,6 +86,11 @@ class _BgSpnFn(torch.autograd.Function):
     dimensions, the general-size ones (csrc/spn_bg_generic.hip)."""
 
     @staticmethod
+    def _entry(D):
+        """(suffix of the entry points, their extra arguments) for D input dimensions"""
+        return ('', ()) if D == 1024 else ('_d', (D,))
+
+    @staticmethod
     def forward(ctx, inputs, marg, coef, wroot, side):
         lib = _lib.load()
         inputs, marg, coef, wroot = _f32(inputs), _f32(marg), _f32(coef), _f32(wroot)
@@ -96,12 +101,10 @@ class _BgSpnFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             out = torch.empty(n, dtype=torch.float32, device=dev)
             t = _tables(bg=(side, coef, wroot))
-            if D == 1024:
-                ell = torch.empty(lib.stove_bgspn_saved_floats(n) + 1, dtype=torch.float32, device=dev)
-                check(lib.stove_bgspn_fwd(ctypes.byref(t), ptr(inputs), ptr(marg), ptr(ell), ptr(out), n, stream()), 'stove_bgspn_fwd')
-            else:
-                ell = torch.empty(lib.stove_bgspn_saved_floats_d(n, D) + 1, dtype=torch.float32, device=dev)
-                check(lib.stove_bgspn_fwd_d(ctypes.byref(t), ptr(inputs), ptr(marg), ptr(ell), ptr(out), n, D, stream()), 'stove_bgspn_fwd_d')
+            sfx, dims = _BgSpnFn._entry(D)
+            ell = torch.empty(getattr(lib, 'stove_bgspn_saved_floats' + sfx)(n, *dims) + 1, dtype=torch.float32, device=dev)
+            check(getattr(lib, 'stove_bgspn_fwd' + sfx)(ctypes.byref(t), ptr(inputs), ptr(marg), ptr(ell), ptr(out), n, *dims, stream()),
+                  'stove_bgspn_fwd' + sfx)
         ctx.save_for_backward(inputs, marg, coef, wroot, side, ell, out)
         return out.unsqueeze(1)
 
@@ -120,14 +123,10 @@ class _BgSpnFn(torch.autograd.Function):
             g = SpnTableGrads()
             g.bg_coef, g.bg_wroot = ptr(g_coef), ptr(g_wroot)
             t = _tables(bg=(side, coef, wroot))
-            if D == 1024:
-                ws = _ws(lib.stove_bgspn_bwd_ws_bytes(n), dev)
-                check(lib.stove_bgspn_bwd(ctypes.byref(t), ptr(inputs), ptr(marg), ptr(ell), ptr(out), ptr(dout), ptr(d_in),
-                                          ptr(d_m), ctypes.byref(g), ptr(ws), n, stream()), 'stove_bgspn_bwd')
-            else:
-                ws = _ws(lib.stove_bgspn_bwd_ws_bytes_d(n, D), dev)
-                check(lib.stove_bgspn_bwd_d(ctypes.byref(t), ptr(inputs), ptr(marg), ptr(ell), ptr(out), ptr(dout), ptr(d_in),
-                                            ptr(d_m), ctypes.byref(g), ptr(ws), n, D, stream()), 'stove_bgspn_bwd_d')
+            sfx, dims = _BgSpnFn._entry(D)
+            ws = _ws(getattr(lib, 'stove_bgspn_bwd_ws_bytes' + sfx)(n, *dims), dev)
+            check(getattr(lib, 'stove_bgspn_bwd' + sfx)(ctypes.byref(t), ptr(inputs), ptr(marg), ptr(ell), ptr(out), ptr(dout), ptr(d_in),
+                                                        ptr(d_m), ctypes.byref(g), ptr(ws), n, *dims, stream()), 'stove_bgspn_bwd' + sfx)
         return d_in, d_m, g_coef, g_wroot, None
 
 
@@ -204,6 +203,25 @@ def _frame_rows(frames):
     return frames, nf, seq_frames, seq_stride
 
 
+def _scene_begin(ctx, frames, z, tabs, with_grad):
+    """What the scene Functions' forwards share: float32 z and tables, the frame map, the outputs, and `grad` -- with a backward to
+    come, the object SPN runs forward + backward (at unit upstream gradient) in one pass (grad mode is off inside a Function's
+    forward: the caller says whether it was on)."""
+    z, tabs = _f32(z), [_f32(x) for x in tabs]
+    frames, nf, seq_frames, seq_stride = _frame_rows(frames)
+    ctx.frame_map = (nf, seq_frames, seq_stride)
+    with torch.cuda.device(frames.device):
+        ll = torch.empty(nf, dtype=torch.float32, device=frames.device)
+        parts = torch.empty(nf, 3, dtype=torch.float32, device=frames.device)
+    return frames, z, tabs, ll, parts, int(bool(with_grad) and any(ctx.needs_input_grad))
+
+
+def _scene_end(ctx, parts, *saved):
+    ctx.save_for_backward(*saved)
+    ctx.set_materialize_grads(False)          # no zero tensors (one fill launch each) for the outputs nothing differentiates
+    ctx.mark_non_differentiable(parts)
+
+
 class _SceneFn(torch.autograd.Function):
     """Supair.likelihood fused (reference supair.py:44-110)."""
 
@@ -212,17 +230,10 @@ class _SceneFn(torch.autograd.Function):
                 obj_scope, obj_leaf_slot, bg_side, n_obj, beta, sink=None, bg_dense=None, with_grad=True, geom=None):
         # geom = (W, H, align_corners) for frames other than 32 x 32 / align_corners=False (stove_scene_fwd_any), else None
         lib = _lib.load()
-        z = _f32(z)
-        tabs = [_f32(x) for x in (obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot)]
-        frames, nf, seq_frames, seq_stride = _frame_rows(frames)
-        ctx.frame_map = (nf, seq_frames, seq_stride)
+        frames, z, tabs, ll, parts, grad = _scene_begin(ctx, frames, z, (obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot), with_grad)
+        nf, seq_frames, seq_stride = ctx.frame_map
         dev = frames.device
         with torch.cuda.device(dev):
-            ll = torch.empty(nf, dtype=torch.float32, device=dev)
-            parts = torch.empty(nf, 3, dtype=torch.float32, device=dev)
-            # with a backward to come, the object SPN runs forward + backward (at unit upstream gradient) in one pass
-            # (grad mode is off inside a Function's forward: the caller says whether it was on)
-            grad = int(bool(with_grad) and any(ctx.needs_input_grad))
             t = _tables(obj=(obj_scope, obj_leaf_slot, tabs[0], tabs[1], tabs[2]), bg=(bg_side, tabs[3], tabs[4]), bg_dense=bg_dense)
             if geom is not None:
                 W, H, ac = geom
@@ -236,10 +247,8 @@ class _SceneFn(torch.autograd.Function):
                 saved = torch.empty(lib.stove_scene_fwd_floats(nf, n_obj, grad) + 1, dtype=torch.float32, device=dev)
                 check(lib.stove_scene_fwd_from(ctypes.byref(t), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames, seq_stride, float(beta),
                                                ptr(ll), ptr(parts), ptr(saved), stream(), None, grad), 'stove_scene_fwd_from')
-        ctx.save_for_backward(frames, z, *tabs, obj_scope, obj_leaf_slot, bg_side, saved)
         ctx.n_obj, ctx.beta, ctx.sink, ctx.geom = n_obj, float(beta), sink, geom
-        ctx.set_materialize_grads(False)          # no zero tensors (one fill launch each) for the outputs nothing differentiates
-        ctx.mark_non_differentiable(parts)
+        _scene_end(ctx, parts, frames, z, *tabs, obj_scope, obj_leaf_slot, bg_side, saved)
         return ll, parts
 
     @staticmethod
@@ -257,40 +266,27 @@ class _SceneFn(torch.autograd.Function):
             g = SpnTableGrads()
             g.obj_coef, g.obj_wsum, g.obj_wroot, g.bg_coef, g.bg_wroot = [ptr(x) for x in grads]
             t = _tables(obj=(obj_scope, obj_leaf_slot, oc, ow, orr), bg=(bg_side, bc, bw))
+            # Flat-arena path: the table gradients only feed the optimiser.  Their passes (and the arena sink) go to a second stream
+            # and overlap with what autograd enqueues next on this one: the recursion's backward, latency-bound with one sequence
+            # per CU.  The main stream waits for them at the end of the backward pass.
+            overlap = ctx.sink is not None and _settings.OVERLAP
+            main, side = torch.cuda.current_stream(dev).cuda_stream, (_side_stream(dev).cuda_stream if overlap else None)
             if ctx.geom is not None:
                 W, H, ac = ctx.geom
                 ws = _ws(lib.stove_scene_bwd_ws_bytes_any(nf, n_obj, W * H), dev)
-                overlap = ctx.sink is not None and _settings.OVERLAP
-                main, side = torch.cuda.current_stream(dev), (_side_stream(dev) if overlap else None)
-                check(lib.stove_scene_bwd_any(ctypes.byref(t), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames, seq_stride, W, H, int(ac),
-                                              ctx.beta, ptr(saved), ptr(dll), ptr(dz), ctypes.byref(g), ptr(ws), main.cuda_stream,
-                                              side.cuda_stream if overlap else None), 'stove_scene_bwd_any')
-                if overlap:
-                    run_on_side(dev, lambda: ctx.sink(grads), (ws, saved, *grads), after_main=False)     # ordered by the C call above
-                    join_side_after_backward(dev)
-                    return (None, dz) + (None,) * 14
-                if ctx.sink is not None:
-                    ctx.sink(grads)
-                    grads = [None] * 5
-                return (None, dz, *grads) + (None,) * 9
-            ws = _ws(lib.stove_scene_bwd_ws_bytes(nf, n_obj), dev)
-            if ctx.sink is not None and _settings.OVERLAP:
-                # Flat-arena path: the table gradients only feed the optimiser.  Their passes (and the arena sink) go to a
-                # second stream and overlap with what autograd enqueues next on this one: the recursion's backward,
-                # latency-bound with one sequence per CU.  The main stream waits for them at the end of the backward pass.
-                main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-                check(lib.stove_scene_bwd_overlap(ctypes.byref(t), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames, seq_stride, ctx.beta,
-                                                  ptr(saved), ptr(dll), ptr(dz), ctypes.byref(g), ptr(ws), main.cuda_stream,
-                                                  side.cuda_stream),
-                      'stove_scene_bwd_overlap')
+                name, extra, streams = 'stove_scene_bwd_any', (W, H, int(ac)), (main, side)
+            else:           # without a parameter stream: the library's stream, which a section may have redirected (_lib.force_stream)
+                ws = _ws(lib.stove_scene_bwd_ws_bytes(nf, n_obj), dev)
+                name, extra, streams = ('stove_scene_bwd_overlap', (), (main, side)) if overlap else ('stove_scene_bwd', (), (stream(),))
+            check(getattr(lib, name)(ctypes.byref(t), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames, seq_stride, *extra, ctx.beta,
+                                     ptr(saved), ptr(dll), ptr(dz), ctypes.byref(g), ptr(ws), *streams), name)
+            if overlap:
                 run_on_side(dev, lambda: ctx.sink(grads), (ws, saved, *grads), after_main=False)     # ordered by the C call above
                 join_side_after_backward(dev)
                 return (None, dz) + (None,) * 14
-            check(lib.stove_scene_bwd(ctypes.byref(t), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames, seq_stride, ctx.beta,
-                                      ptr(saved), ptr(dll), ptr(dz), ctypes.byref(g), ptr(ws), stream()), 'stove_scene_bwd')
-        if ctx.sink is not None:               # flat parameter arena: table gradients go straight into the bucket
-            ctx.sink(grads)
-            grads = [None] * 5
+            if ctx.sink is not None:               # flat parameter arena: table gradients go straight into the bucket
+                ctx.sink(grads)
+                grads = [None] * 5
         return (None, dz, *grads) + (None,) * 9
 
 
@@ -303,9 +299,8 @@ class _SceneChFn(torch.autograd.Function):
                 with_grad=True):
         # geom = (C, W, H, pw, ph, align_corners); shape = (R, G, S, D, Lmax) of the object SPN
         lib = _lib.load()
-        z = _f32(z)
-        tabs = [_f32(x) for x in (obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot)]
-        frames, nf, seq_frames, seq_stride = _frame_rows(frames)
+        frames, z, tabs, ll, parts, grad = _scene_begin(ctx, frames, z, (obj_coef, obj_wsum, obj_wroot, bg_coef, bg_wroot), with_grad)
+        nf, seq_frames, seq_stride = ctx.frame_map
         C, W, H, pw, ph, ac = geom
         R, G, S, D, lmax = shape
         if frames.shape[-1] != C * W * H or D != C * pw * ph:
@@ -313,19 +308,14 @@ class _SceneChFn(torch.autograd.Function):
                              'frames and %d x %d glimpses' % (tuple(frames.shape), D, C, W, H, pw, ph))
         dev = frames.device
         with torch.cuda.device(dev):
-            ll = torch.empty(nf, dtype=torch.float32, device=dev)
-            parts = torch.empty(nf, 3, dtype=torch.float32, device=dev)
-            grad = int(bool(with_grad) and any(ctx.needs_input_grad))
             saved = torch.empty(lib.stove_scene_saved_floats_ch(nf, n_obj, C, W, H, R, G, S, D, lmax, grad) + 1, dtype=torch.float32,
                                 device=dev)
             check(lib.stove_scene_fwd_ch(ptr(lscope), ptr(slot), ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), R, G, S, D, lmax, ptr(bg_side),
                                          ptr(tabs[3]), ptr(tabs[4]), tabs[3].numel(), frames.data_ptr(), ptr(z), nf, n_obj, seq_frames,
                                          seq_stride, C, W, H, pw, ph, int(ac), float(beta), ptr(ll), ptr(parts), ptr(saved), stream(), grad),
                   'stove_scene_fwd_ch')
-        ctx.save_for_backward(frames, z, *tabs, lscope, slot, bg_side, saved)
-        ctx.frame_map, ctx.n_obj, ctx.beta, ctx.geom, ctx.shape = (nf, seq_frames, seq_stride), n_obj, float(beta), geom, shape
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(parts)
+        ctx.n_obj, ctx.beta, ctx.geom, ctx.shape = n_obj, float(beta), geom, shape
+        _scene_end(ctx, parts, frames, z, *tabs, lscope, slot, bg_side, saved)
         return ll, parts
 
     @staticmethod
