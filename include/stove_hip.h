@@ -304,6 +304,33 @@ int stove_rollout_fwd(const float* z_last, const float* extra, const float* para
                       int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std,
                       float lat_std, void* stream);
 
+/* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
+ * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
+ * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),
+ * states cl/2 + 2 wide, dyn means / stds cl/2, extra (B,Ts,N,sin_dim - cl/2).  Any other cl, N or sin_dim: hipErrorInvalidValue.
+ * The recursion runs all Ts steps in one launch each way (the backward recomputes each step's forward, so there is no `act` buffer)
+ * plus one fixed-order reduction launch for the weight gradients; ws: stove_gnn_bwd_ws_bytes_cl(cl, B, N) bytes.
+ * An empty batch (B == 0, or Ts == 0 for the recursion) is a valid call everywhere; the backwards then zero g_params. */
+size_t stove_gnn_param_floats_cl(int cl);
+size_t stove_gnn_grad_floats_cl(int cl);
+size_t stove_gnn_bwd_ws_bytes_cl(int cl, int B, int N);
+int stove_gnn_fwd_cl(const float* s_in, const float* params, float* result, float* pred, int cl, int B, int N, int sin_dim,
+                     int lim_enc, int elu, void* stream);
+int stove_gnn_bwd_cl(const float* s_in, const float* params, const float* d_result, const float* d_pred, float* d_s_in,
+                     float* g_params, void* ws, int cl, int B, int N, int sin_dim, int lim_enc, int elu, void* stream);
+int stove_dynloop_fwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
+                         const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred,
+                         int cl, int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
+                         void* stream);
+int stove_dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
+                         const float* params, const float* z, const float* dz, const float* dzdyn, const float* dmean,
+                         const float* dstd, const float* dpred, float* dz1, float* dzsup, float* dzsstd, float* dextra,
+                         float* g_params, void* ws, int cl, int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var,
+                         float vel_std, float lat_std, void* stream);
+int stove_rollout_fwd_cl(const float* z_last, const float* extra, const float* params, float* z_pred, float* zstd, float* pred,
+                         int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std,
+                         float lat_std, void* stream);
+
 /* ---- Stove._3_only_match_objects / _greedy_match_objects / _volatile_match_objects
  * (stove.py:200-329, 432-514, 331-430): the T-serial nearest-neighbour re-ordering of objects.
  * feat (B,T,N,F) matching features in [-1,1] (positions [, appearance]); mode 0 = '3_only',

@@ -11,7 +11,7 @@ from . import settings as _settings
 
 LIB_PATH = _settings.LIB_OVERRIDE or os.path.join(_HERE, 'libstove_hip.so')
 _lib = None
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 class SpnTables(Structure):
     _fields_ = [('obj_scope', c_void_p), ('obj_leaf_slot', c_void_p), ('obj_coef', c_void_p),
@@ -82,6 +82,14 @@ def _declare(lib):
         'stove_dynloop_bwd': (I, [P] * 19 + [I] * 6 + [F] * 3 + [P]),
         'stove_dynloop_bwd_overlap': (I, [P] * 19 + [I] * 6 + [F] * 3 + [P, P]),
         'stove_rollout_fwd': (I, [P] * 6 + [I] * 7 + [F] * 3 + [P]),
+        'stove_gnn_param_floats_cl': (S, [I]),
+        'stove_gnn_grad_floats_cl': (S, [I]),
+        'stove_gnn_bwd_ws_bytes_cl': (S, [I, I, I]),
+        'stove_gnn_fwd_cl': (I, [P, P, P, P, I, I, I, I, I, I, P]),
+        'stove_gnn_bwd_cl': (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+        'stove_dynloop_fwd_cl': (I, [P] * 12 + [I] * 7 + [F] * 3 + [P]),
+        'stove_dynloop_bwd_cl': (I, [P] * 18 + [I] * 7 + [F] * 3 + [P]),
+        'stove_rollout_fwd_cl': (I, [P] * 6 + [I] * 8 + [F] * 3 + [P]),
         'stove_match_objects': (I, [P, P, P, I, I, I, I, I, P]),
         'stove_profile_enable': (None, [I]),
         'stove_lstm_cell_fwd': (I, [P, P, P, P, P, I, I, I, P]),

@@ -28,6 +28,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "match.hip"
 #include "gnn_small.hip"
 #include "gnn_small_bwd.hip"
+#include "gnn_cl.hip"
 #include "lstm.hip"
 #include "arena.hip"
 #include "state.hip"
@@ -136,7 +137,10 @@ extern "C" {
 //    stove_objspn_*_any), the fixed-Gaussian debug models (stove_gauss_ll_*), stove_scene_bwd_from.
 // 6: the scene likelihood over 1 to 4 colour channels (stove_scene_saved_floats_ch, stove_scene_bwd_ws_bytes_ch, stove_scene_fwd_ch,
 //    stove_scene_bwd_ch).
-int stove_abi_version(void) { return 6; }
+// 7: the GNN step, the inference recursion and the rollout at state-code lengths 16 and 64 (stove_gnn_param_floats_cl,
+//    stove_gnn_grad_floats_cl, stove_gnn_bwd_ws_bytes_cl, stove_gnn_fwd_cl, stove_gnn_bwd_cl, stove_dynloop_fwd_cl, stove_dynloop_bwd_cl,
+//    stove_rollout_fwd_cl).
+int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
 
@@ -1096,6 +1100,110 @@ int stove_rollout_fwd(const float* z_last, const float* extra, const float* para
                      z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
   STOVE_LAUNCH_CHECK();
   return 0;
+}
+
+// ---------------------------------------------------------------- GNN dynamics core at state-code lengths 16 / 64 (gnn_cl.hip)
+size_t stove_gnn_param_floats_cl(int cl) { return cl == 16 ? GC<16>::kParams : (cl == 64 ? GC<64>::kParams : 0); }
+size_t stove_gnn_grad_floats_cl(int cl) { return cl == 16 ? GC<16>::kGrads : (cl == 64 ? GC<64>::kGrads : 0); }
+size_t stove_gnn_bwd_ws_bytes_cl(int cl, int B, int N) {
+  if (B < 1 || N < 1 || N > 6) return 0;
+  if (cl == 16) return (size_t)cl_blocks<16>(B, N) * GC<16>::kGrads * sizeof(float);
+  if (cl == 64) return (size_t)cl_blocks<64>(B, N) * GC<64>::kGrads * sizeof(float);
+  return 0;
+}
+
+int stove_gnn_fwd_cl(const float* s_in, const float* params, float* result, float* pred, int cl, int B, int N, int sin_dim,
+                     int lim_enc, int elu, void* stream) {
+  STOVE_VALIDATE(gnn_fwd_cl(s_in, params, result, cl, B, N, sin_dim));
+  if (B == 0) return 0;
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    int rc = cl_lds_attr<CL>((const void*)gnn_cl_step_fwd_k<CL>);
+    if (rc) return rc;
+    STOVE_LAUNCH(gnn_cl_step_fwd_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                 s_in, params, result, pred, B, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int stove_gnn_bwd_cl(const float* s_in, const float* params, const float* d_result, const float* d_pred, float* d_s_in,
+                     float* g_params, void* ws, int cl, int B, int N, int sin_dim, int lim_enc, int elu, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  STOVE_VALIDATE(gnn_bwd_cl(s_in, params, d_result, d_s_in, g_params, ws, cl, B, N, sin_dim));
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    if (B == 0) return (int)hipMemsetAsync(g_params, 0, GC<CL>::kGrads * sizeof(float), st);
+    int rc = cl_lds_attr<CL>((const void*)gnn_cl_step_bwd_k<CL>);
+    if (rc) return rc;
+    const int nb = cl_blocks<CL>(B, N);
+    STOVE_LAUNCH(gnn_cl_step_bwd_k<CL>, dim3(nb), dim3(256), GC<CL>::kLdsFloats * sizeof(float), st, s_in, params, d_result, d_pred,
+                 d_s_in, (float*)ws, B, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu);
+    STOVE_LAUNCH_CHECK();
+    STOVE_LAUNCH(reduce_chunks_k, dim3((GC<CL>::kGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, GC<CL>::kGrads, nb, 0);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int stove_dynloop_fwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
+                         const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred,
+                         int cl, int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
+                         void* stream) {
+  STOVE_VALIDATE(dynloop_fwd_cl(z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, cl, B, Ts, N, sin_dim));
+  if (B == 0 || Ts == 0) return 0;
+  LoopConst kc{pos_var, vel_std, lat_std};
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    int rc = cl_lds_attr<CL>((const void*)gnn_cl_loop_fwd_k<CL>);
+    if (rc) return rc;
+    STOVE_LAUNCH(gnn_cl_loop_fwd_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                 z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, B, Ts, N, cl_group_for<CL>(B, N), sin_dim, lim_enc,
+                 elu, kc);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int stove_dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
+                         const float* params, const float* z, const float* dz, const float* dzdyn, const float* dmean,
+                         const float* dstd, const float* dpred, float* dz1, float* dzsup, float* dzsstd, float* dextra,
+                         float* g_params, void* ws, int cl, int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var,
+                         float vel_std, float lat_std, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  STOVE_VALIDATE(dynloop_bwd_cl(z1, zsup, zsstd, eps, extra, params, z, dz1, dzsup, dzsstd, dextra, g_params, ws, cl, B, Ts, N, sin_dim));
+  LoopConst kc{pos_var, vel_std, lat_std};
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    if (B == 0 || Ts == 0) return (int)hipMemsetAsync(g_params, 0, GC<CL>::kGrads * sizeof(float), st);
+    int rc = cl_lds_attr<CL>((const void*)gnn_cl_loop_bwd_k<CL>);
+    if (rc) return rc;
+    const int nb = cl_blocks<CL>(B, N);
+    STOVE_LAUNCH(gnn_cl_loop_bwd_k<CL>, dim3(nb), dim3(256), GC<CL>::kLdsFloats * sizeof(float), st, z1, zsup, zsstd, eps, extra, params, z,
+                 dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, (float*)ws, B, Ts, N, cl_group_for<CL>(B, N), sin_dim, lim_enc,
+                 elu, kc);
+    STOVE_LAUNCH_CHECK();
+    STOVE_LAUNCH(reduce_chunks_k, dim3((GC<CL>::kGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, GC<CL>::kGrads, nb, 0);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int stove_rollout_fwd_cl(const float* z_last, const float* extra, const float* params, float* z_pred, float* zstd, float* pred,
+                         int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std,
+                         float lat_std, void* stream) {
+  STOVE_VALIDATE(rollout_fwd_cl(z_last, extra, params, z_pred, cl, B, num, A, N, sin_dim));
+  if (B == 0 || num == 0) return 0;
+  LoopConst kc{pos_var, vel_std, lat_std};
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    int rc = cl_lds_attr<CL>((const void*)gnn_cl_rollout_k<CL>);
+    if (rc) return rc;
+    STOVE_LAUNCH(gnn_cl_rollout_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                 z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu, kc);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------- flat parameter arena

@@ -165,6 +165,49 @@ inline int rollout_fwd(const float* z_last, const float* extra, const float* par
   return 0;
 }
 
+// ---- the same at state-code lengths other than 32 (stove_*_cl, csrc/gnn_cl.hip): cl 16 or 64, N <= 6, cl/2 <= sin_dim <= cl
+constexpr int kMaxObjectsCl = 6;
+inline bool gnn_cl_bad(int cl, int B, int N, int sin_dim) {
+  return (cl != 16 && cl != 64) || B < 0 || N < 1 || N > kMaxObjectsCl || sin_dim < cl / 2 || sin_dim > cl;
+}
+inline int gnn_fwd_cl(const float* s_in, const float* params, const float* result, int cl, int B, int N, int sin_dim) {
+  if (gnn_cl_bad(cl, B, N, sin_dim)) return kStoveInvalidValue;
+  if (B == 0) return 0;
+  return null_any(s_in, params, result) ? kStoveInvalidValue : 0;
+}
+inline int gnn_bwd_cl(const float* s_in, const float* params, const float* d_result, const float* d_s_in, const float* g_params,
+                      const void* ws, int cl, int B, int N, int sin_dim) {
+  if (gnn_cl_bad(cl, B, N, sin_dim) || g_params == nullptr) return kStoveInvalidValue;
+  if (B == 0) return 0;
+  return (null_any(s_in, params, d_result, d_s_in) || ws == nullptr) ? kStoveInvalidValue : 0;
+}
+inline int dynloop_fwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra, const float* params,
+                          const float* z, const float* zdyn, const float* zdstd, const float* mean, const float* std_, int cl, int B, int Ts,
+                          int N, int sin_dim) {
+  if (gnn_cl_bad(cl, B, N, sin_dim) || Ts < 0) return kStoveInvalidValue;
+  if (B == 0 || Ts == 0) return 0;
+  if (null_any(z1, zsup, zsstd, eps, params, z, zdyn, zdstd, mean, std_)) return kStoveInvalidValue;
+  if (sin_dim > cl / 2 && extra == nullptr) return kStoveInvalidValue;
+  return 0;
+}
+inline int dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra, const float* params,
+                          const float* z, const float* dz1, const float* dzsup, const float* dzsstd, const float* dextra,
+                          const float* g_params, const void* ws, int cl, int B, int Ts, int N, int sin_dim) {
+  if (gnn_cl_bad(cl, B, N, sin_dim) || Ts < 0 || g_params == nullptr) return kStoveInvalidValue;
+  if (B == 0 || Ts == 0) return 0;                    // an empty backward zeroes g_params, as stove_gnn_bwd_cl does
+  if (null_any(z1, zsup, zsstd, eps, params, z, dz1, dzsup, dzsstd) || ws == nullptr) return kStoveInvalidValue;
+  if (sin_dim > cl / 2 && (extra == nullptr || dextra == nullptr)) return kStoveInvalidValue;
+  return 0;
+}
+inline int rollout_fwd_cl(const float* z_last, const float* extra, const float* params, const float* z_pred, int cl, int B, int num, int A,
+                          int N, int sin_dim) {
+  if (gnn_cl_bad(cl, B, N, sin_dim) || num < 0) return kStoveInvalidValue;
+  if (B == 0 || num == 0) return 0;
+  if (null_any(z_last, params, z_pred)) return kStoveInvalidValue;
+  if (sin_dim > cl / 2 && (extra == nullptr || A < 1)) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

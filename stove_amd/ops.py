@@ -720,6 +720,137 @@ class _DynLoopFn(torch.autograd.Function):
         return (dz1, dzsup, dzsstd, None, dextra, g[:GNN_W_FLOATS], g[GNN_W_FLOATS:], None, None, None, None, None, None)
 
 
+# ---- state-code lengths other than 32 (csrc/gnn_cl.hip): image [W | W^T | vectors], 22 cl^2 weight and 21 cl vector floats
+GNN_CL_WIDTHS = (16, 64)
+
+
+def gnn_w_floats(cl):
+    return 22 * cl * cl
+
+
+def _check_image_cl(image, cl):
+    """A parameter image -- (w_img, v_img, wt_img) or (flat image, None, None) -- must have the size of its width's layout."""
+    if cl == 32:
+        return                                  # (_gnn_image checks the flat cl = 32 image against stove_gnn_param_floats)
+    if cl not in GNN_CL_WIDTHS:
+        raise NotImplementedError('the GNN kernels are built for cl in (16, 32, 64), got %d' % cl)
+    have = image[0].numel() if image[1] is None else image[0].numel() + image[1].numel() + image[2].numel()
+    need = 2 * gnn_w_floats(cl) + 21 * cl
+    if have != need:
+        raise ValueError('GNN parameter image has %d floats, cl = %d needs %d' % (have, cl, need))
+
+
+def _gnn_image_cl(w_img, v_img, wt_img, cl):
+    if cl not in GNN_CL_WIDTHS:
+        raise NotImplementedError('the GNN kernels are built for cl in (16, 32, 64), got %d' % cl)
+    if v_img is None:                          # prebuilt [W | W^T | vectors] image
+        need = _lib.load().stove_gnn_param_floats_cl(cl)
+        if w_img.numel() != need:
+            raise ValueError('GNN parameter image has %d floats, libstove_hip.so expects %d at cl = %d' % (w_img.numel(), need, cl))
+        return w_img
+    return torch.cat([w_img, wt_img, v_img]).contiguous()
+
+
+class _GnnStepClFn(torch.autograd.Function):
+    """_GnnStepFn at cl = 16 / 64: s_in (B,N,sin_dim) -> result, dynamic_pred (B,N,cl)."""
+
+    @staticmethod
+    def forward(ctx, s_in, w_img, v_img, wt_img, cl, lim_enc, elu, sink=None):
+        lib = _lib.load()
+        s_in = _f32(s_in)
+        B, N, sd = s_in.shape
+        dev = s_in.device
+        params = _gnn_image_cl(_f32(w_img), _f32(v_img), _f32(wt_img), cl)
+        ctx.sink = sink
+        with torch.cuda.device(dev):
+            res = torch.empty(B, N, cl, dtype=torch.float32, device=dev)
+            pred = torch.empty(B, N, cl, dtype=torch.float32, device=dev)
+            check(lib.stove_gnn_fwd_cl(ptr(s_in), ptr(params), ptr(res), ptr(pred), cl, B, N, sd, int(lim_enc), int(elu), stream()),
+                  'stove_gnn_fwd_cl')
+        ctx.save_for_backward(s_in, params)
+        ctx.cfg = (cl, int(lim_enc), int(elu))
+        return res, pred
+
+    @staticmethod
+    def backward(ctx, dres, dpred):
+        lib = _lib.load()
+        s_in, params = ctx.saved_tensors
+        B, N, sd = s_in.shape
+        dev = s_in.device
+        cl, lim_enc, elu = ctx.cfg
+        with torch.cuda.device(dev):
+            dres = _f32(dres) if dres is not None else torch.zeros(B, N, cl, device=dev)
+            dpred = _f32(dpred) if dpred is not None else None
+            d_s = torch.empty_like(s_in)
+            g = torch.empty(lib.stove_gnn_grad_floats_cl(cl), dtype=torch.float32, device=dev)
+            ws = _ws(lib.stove_gnn_bwd_ws_bytes_cl(cl, B, N), dev)
+            check(lib.stove_gnn_bwd_cl(ptr(s_in), ptr(params), ptr(dres), ptr(dpred), ptr(d_s), ptr(g), ptr(ws), cl, B, N, sd,
+                                       lim_enc, elu, stream()), 'stove_gnn_bwd_cl')
+        if ctx.sink is not None:
+            ctx.sink(g)
+            return (d_s,) + (None,) * 7
+        W = gnn_w_floats(cl)
+        return d_s, g[:W], g[W:], None, None, None, None, None
+
+
+class _DynLoopClFn(torch.autograd.Function):
+    """_DynLoopFn at cl = 16 / 64: all Ts steps in one launch each way; the backward recomputes each step's forward."""
+
+    @staticmethod
+    def forward(ctx, z1, zsup, zsstd, eps, extra, w_img, v_img, wt_img, cl, lim_enc, elu, consts, want_pred, sink=None):
+        lib = _lib.load()
+        z1, zsup, zsstd, eps = _f32(z1), _f32(zsup), _f32(zsstd), _f32(eps)
+        extra = _f32(extra)
+        B, Ts, N = zsup.shape[:3]
+        D = cl // 2
+        sd = D + (extra.shape[-1] if extra is not None else 0)
+        dev = z1.device
+        params = _gnn_image_cl(_f32(w_img), _f32(v_img), _f32(wt_img), cl)
+        with torch.cuda.device(dev):
+            def out(d):
+                return torch.empty(B, Ts, N, d, dtype=torch.float32, device=dev)
+            z, zdyn, zdstd, mean, std = out(D + 2), out(D), out(D), out(D + 2), out(D + 2)
+            pred = out(cl) if want_pred else None
+            check(lib.stove_dynloop_fwd_cl(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z), ptr(zdyn),
+                                           ptr(zdstd), ptr(mean), ptr(std), ptr(pred), cl, B, Ts, N, sd, int(lim_enc), int(elu),
+                                           *[float(c) for c in consts], stream()), 'stove_dynloop_fwd_cl')
+        ctx.save_for_backward(z1, zsup, zsstd, eps, extra, params, z)
+        ctx.cfg = (cl, int(lim_enc), int(elu), tuple(float(c) for c in consts), sd)
+        ctx.sink = sink
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(zdstd)
+        if pred is None:
+            pred = z.new_zeros(0)
+            ctx.mark_non_differentiable(pred)
+        return z, zdyn, zdstd, mean, std, pred
+
+    @staticmethod
+    def backward(ctx, dz, dzdyn, _dzdstd, dmean, dstd, dpred):
+        lib = _lib.load()
+        z1, zsup, zsstd, eps, extra, params, z = ctx.saved_tensors
+        cl, lim_enc, elu, consts, sd = ctx.cfg
+        B, Ts, N = zsup.shape[:3]
+        dev = z1.device
+
+        def up(g):
+            return None if g is None or g.numel() == 0 else _f32(g)
+        with torch.cuda.device(dev):
+            dz1 = torch.empty_like(z1)
+            dzsup, dzsstd = torch.empty_like(zsup), torch.empty_like(zsstd)
+            dextra = torch.empty_like(extra) if extra is not None else None
+            g = torch.empty(lib.stove_gnn_grad_floats_cl(cl), dtype=torch.float32, device=dev)
+            ws = _ws(lib.stove_gnn_bwd_ws_bytes_cl(cl, B, N), dev)
+            check(lib.stove_dynloop_bwd_cl(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z),
+                                           ptr(up(dz)), ptr(up(dzdyn)), ptr(up(dmean)), ptr(up(dstd)), ptr(up(dpred)),
+                                           ptr(dz1), ptr(dzsup), ptr(dzsstd), ptr(dextra), ptr(g), ptr(ws),
+                                           cl, B, Ts, N, sd, lim_enc, elu, *consts, stream()), 'stove_dynloop_bwd_cl')
+        if ctx.sink is not None:
+            ctx.sink(g)
+            return (dz1, dzsup, dzsstd, None, dextra) + (None,) * 9
+        W = gnn_w_floats(cl)
+        return (dz1, dzsup, dzsstd, None, dextra, g[:W], g[W:]) + (None,) * 7
+
+
 def _sunk(t, sink):
     """With a gradient sink the parameters are not autograd inputs: make sure the backward still runs."""
     if sink is not None and not t.requires_grad and torch.is_grad_enabled():
@@ -727,12 +858,22 @@ def _sunk(t, sink):
     return t
 
 
-def gnn_step(s_in, image, lim_enc=2, elu=False, sink=None):
-    """image = (w_img, v_img, wt_img) from Dynamics.param_image(), or (flat image, None, None) + a gradient sink."""
+def gnn_step(s_in, image, lim_enc=2, elu=False, sink=None, cl=32):
+    """image = (w_img, v_img, wt_img) from Dynamics.param_image(), or (flat image, None, None) + a gradient sink.
+    `cl`: the state-code length the image was built for (Dynamics passes config.cl); 16 and 64 run the width-generic kernels
+    (csrc/gnn_cl.hip).  An image of another size than that width's is an error."""
+    _check_image_cl(image, cl)
+    if cl != 32:
+        return _GnnStepClFn.apply(_sunk(s_in, sink), image[0], image[1], image[2], cl, lim_enc, elu, sink)
     return _GnnStepFn.apply(_sunk(s_in, sink), image[0], image[1], image[2], lim_enc, elu, sink)
 
 
 def dyn_loop(z1, zsup, zsstd, eps, extra, image, lim_enc, elu, consts, want_pred=False, sink=None):
+    cl = 2 * (z1.shape[-1] - 2)                # states are cl/2 + 2 wide
+    if cl != 32:
+        _check_image_cl(image, cl)
+        return _DynLoopClFn.apply(_sunk(z1, sink), zsup, zsstd, eps, extra, image[0], image[1], image[2], cl, lim_enc, elu, consts,
+                                  want_pred, sink)
     return _DynLoopFn.apply(_sunk(z1, sink), zsup, zsstd, eps, extra, image[0], image[1], image[2], lim_enc, elu, consts,
                             want_pred, sink)
 
@@ -744,6 +885,20 @@ def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, wan
     z_last, extra = _f32(z_last), _f32(extra)
     B, N = z_last.shape[:2]
     A = extra.shape[1] if extra is not None else 1
+    cl = 2 * (z_last.shape[-1] - 2)
+    if cl != 32:
+        _check_image_cl(image, cl)
+        D = cl // 2
+        sd = D + (extra.shape[-1] if extra is not None else 0)
+        dev = z_last.device
+        params = _gnn_image_cl(_f32(image[0]), _f32(image[1]), _f32(image[2]), cl)
+        with torch.cuda.device(dev):
+            z_pred = torch.empty(B, num, N, D + 2, dtype=torch.float32, device=dev)
+            zstd = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if want_std else None
+            pred = torch.empty(B, num, N, cl, dtype=torch.float32, device=dev) if want_pred else None
+            check(lib.stove_rollout_fwd_cl(ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred), cl, B, num, A, N, sd,
+                                           int(lim_enc), int(elu), *[float(c) for c in consts], stream()), 'stove_rollout_fwd_cl')
+        return z_pred, zstd, pred
     sd = 16 + (extra.shape[-1] if extra is not None else 0)
     dev = z_last.device
     params = _gnn_image(_f32(image[0]), _f32(image[1]), _f32(image[2]))

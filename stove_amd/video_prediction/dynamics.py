@@ -15,14 +15,16 @@ from .. import ops
 
 
 class Dynamics(nn.Module):
+    SUPPORTED_CL = (16, 32, 64)      # 32: the tuned kernels (csrc/gnn.hip, gnn_small*.hip); 16 / 64: the width-generic ones (gnn_cl.hip)
+
     def __init__(self, config, enc_input_size=None):
         super().__init__()
         self.c = config
         self.step_counter = 0
         self.prop_dict = {}
         cl = self.c.cl
-        if cl != 32:
-            raise NotImplementedError('the GNN kernel is built for cl = 32')
+        if cl not in self.SUPPORTED_CL:
+            raise NotImplementedError('the GNN kernels are built for cl in %s, got cl = %d' % (self.SUPPORTED_CL, cl))
         if enc_input_size is None:
             enc_input_size = cl // 2
 
@@ -59,6 +61,10 @@ class Dynamics(nn.Module):
         self.nonlinear = F.elu if self.use_elu else F.leaky_relu
 
         std = list(self.c.transition_lik_std)
+        if cl != 32 and len(std) != cl // 2:
+            # (the reference pads its 4-entry default to 16 entries, which only fits cl = 32)
+            raise ValueError('cl = %d needs a transition_lik_std with cl // 2 = %d entries, got %d: set e.g. '
+                             'config.transition_lik_std = [0.01] * %d' % (cl, cl // 2, len(std), cl // 2))
         if len(std) == 4:
             std = std + 12 * [0.01]
         elif len(std) != cl // 2:
@@ -161,7 +167,7 @@ class Dynamics(nn.Module):
         if s.shape[-1] != self.enc_input_size:
             raise ValueError('core input has %d dims, the encoder expects %d' % (s.shape[-1], self.enc_input_size))
         image, sink = self.kernel_params(core_idx)
-        result, dynamic_pred = ops.gnn_step(s, image, lim_enc, self.use_elu, sink)
+        result, dynamic_pred = ops.gnn_step(s, image, lim_enc, self.use_elu, sink, cl=self.c.cl)
         if self.c.action_conditioned:
             return result, self.reward_from_pred(dynamic_pred).view(-1, 1)
         return result, 0

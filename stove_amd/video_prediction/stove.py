@@ -198,7 +198,8 @@ class Stove(nn.Module):
         # recursion / ELBO kernels, which implement the default q(z)
         ablated = bool(c.debug_no_latents or c.debug_no_velocity)
         fused_dyn = bool(getattr(c, 'fused_dynamics', True)) and not ablated
-        fused_elbo = bool(getattr(c, 'fused_elbo', True)) and not ablated
+        # (the zall / ELBO kernels of csrc/state.hip are 18 / 16 wide: at cl != 32 those two stages run as the PyTorch chains below)
+        fused_elbo = bool(getattr(c, 'fused_elbo', True)) and not ablated and cl == 32
         arena = getattr(self.dyn, '_arena', None)
         if arena is not None and torch.is_grad_enabled() and fused_dyn:
             arena.prefetch_images()          # parameter-only launches, off the critical path (second stream)
@@ -298,7 +299,7 @@ class Stove(nn.Module):
         # 3. ELBO: image likelihood (SPNs), q(z|x) and the generative transition likelihood.
         # The reference scores frames skip..T-1 (sampled z) and frame 1..skip-1 (SuPAIR mean) in two
         # likelihood calls (stove.py:731-736); here both go through ONE fused scene launch.
-        if fused_state:
+        if fused_state and cl == 32:
             z_all, z_s = ops.zall(zfix, z_s, n, T, o, skip)        # (z_s handed through: its ELBO gradient is added by zall's backward kernel)
         else:
             z_all = torch.cat([z_sup[:, 1:skip], z_s[..., :4]], 1)             # (n, T-1, o, 4) [sx, sy/sx, x, y]
