@@ -257,11 +257,7 @@ class ParamArena:
         self._gnn = {}
         for k in range(3):
             w, v, wt = dyn.param_image(k, leaf=index_of, pad_value=-1.0)
-            if dyn.c.cl == 32:
-                pf, pt = ops.gnn_pack_perms(torch.device('cpu'))        # + the packed sections the small-graph kernels copy into LDS
-                image = torch.cat([w, wt, v, w[pf], wt[pt]])
-            else:
-                image = torch.cat([w, wt, v])                           # the width-generic kernels (csrc/gnn_cl.hip) read no packed sections
+            image = ops.gnn_width(dyn.c.cl).layout(w, v, wt)             # the image's layout, applied to the arena indices
             self._gnn[k] = (image.to(torch.int32).to(dev), torch.cat([w, v]).to(torch.int32).to(dev))
         self._gnn_params = [p for n, p in dyn.named_parameters()
                             if n.split('.')[0] in ('state_enc', 'self_cores', 'rel_cores', 'att_net', 'affector', 'out')]

@@ -114,6 +114,28 @@ static int with_nmax(int n, F f) {
   return (int)hipErrorInvalidValue;
 }
 
+// The other run-time choices that are template parameters of kernels (the GNN dynamics core), handed over the same way.  A ladder
+// names exactly the instantiations that exist: what it passes to f is compiled.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class F>
+static int with_flag(bool b, F f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(NMX, ELU, NT) for a small graph of N objects: NMX = 4 / 6, the kernels built for up to four objects and up to six, NT = N where the count is a compile-time constant of the kernel
+// (three objects; six where the kernel has that instantiation, SIX, and the call can use it, `six`), else 0.
+template <bool SIX, class F>
+static int with_small_graph(int N, bool elu, bool six, F f) {
+  return with_flag(elu, [&](auto e) {
+    if (N == 3) return f(Int<4>{}, e, Int<3>{});
+    if (N <= 4) return f(Int<4>{}, e, Int<0>{});
+    if constexpr (SIX) {
+      if (N == 6 && six) return f(Int<6>{}, e, Int<6>{});
+    }
+    return f(Int<6>{}, e, Int<0>{});
+  });
+}
+
 __global__ void fill_words_k(uint32_t* __restrict__ p, uint32_t v, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
@@ -820,9 +842,9 @@ int stove_scene_glimpses(const float* frames, const float* z, int n_frames, int 
 }
 
 // ---------------------------------------------------------------- GNN dynamics core
-static int gnn_lds_attr(const void* fn) {
-  return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kGnnLdsFloats * sizeof(float)));
-}
+// The small-graph recursion (gnn_small*.hip): kernels built for up to four objects (one node row per wave) and for up to six (two).
+static bool small_graph(int N) { return N >= 2 && N <= 6; }
+constexpr size_t kGnnLdsBytes = kGnnLdsFloats * sizeof(float);
 
 size_t stove_gnn_param_floats(void) { return kGnnParams; }
 size_t stove_gnn_grad_floats(void) { return kGnnGrads; }
@@ -835,12 +857,8 @@ int stove_gnn_fwd(const float* s_in, const float* params, float* result, float* 
                   int lim_enc, int elu, void* stream) {
   STOVE_VALIDATE(gnn_fwd(s_in, params, result, B, N, sin_dim));
   if (B == 0) return 0;
-  int rc = gnn_lds_attr((const void*)gnn_step_fwd_k);
-  if (rc) return rc;
-  STOVE_LAUNCH(gnn_step_fwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsFloats * sizeof(float), (hipStream_t)stream,
-                     s_in, params, result, pred, B, N, gnn_group_for(B, N), sin_dim, lim_enc, elu);
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  return STOVE_LAUNCH_LDS(gnn_step_fwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsBytes, (hipStream_t)stream,
+                          s_in, params, result, pred, B, N, gnn_group_for(B, N), sin_dim, lim_enc, elu);
 }
 
 size_t stove_gnn_bwd_ws_bytes(int B, int N) { return (size_t)stove_gnn_blocks(B, N) * kGnnGrads * sizeof(float); }
@@ -854,13 +872,10 @@ int stove_gnn_bwd(const float* s_in, const float* params, const float* d_result,
     hipMemsetAsync(g_params, 0, kGnnGrads * sizeof(float), st);
     return 0;
   }
-  if (N < 1 || N > 8 || sin_dim < 16 || sin_dim > 32) return (int)hipErrorInvalidValue;
-  int rc = gnn_lds_attr((const void*)gnn_step_bwd_k);
-  if (rc) return rc;
   const int nb = stove_gnn_blocks(B, N);
-  STOVE_LAUNCH(gnn_step_bwd_k, dim3(nb), dim3(256), kGnnLdsFloats * sizeof(float), st, s_in, params, d_result, d_pred,
-                     d_s_in, (float*)ws, B, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, (long long*)nullptr);
-  STOVE_LAUNCH_CHECK();
+  int rc = STOVE_LAUNCH_LDS(gnn_step_bwd_k, dim3(nb), dim3(256), kGnnLdsBytes, st, s_in, params, d_result, d_pred,
+                            d_s_in, (float*)ws, B, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, (long long*)nullptr);
+  if (rc) return rc;
   STOVE_LAUNCH(reduce_chunks_k, dim3((kGnnGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, kGnnGrads, nb, 0);
   STOVE_LAUNCH_CHECK();
   return 0;
@@ -869,21 +884,14 @@ int stove_gnn_bwd(const float* s_in, const float* params, const float* d_result,
 // debug: one fwd+bwd step with per-stage cycle stamps of block 0 (stamps: 64 int64 on the device)
 int stove_gnn_debug_stamps(const float* s_in, const float* params, const float* d_result, float* d_s_in, void* ws,
                            long long* stamps, int B, int N, int sin_dim, int lim_enc, int elu, void* stream) {
-  int rc = gnn_lds_attr((const void*)gnn_step_bwd_k);
-  if (rc) return rc;
-  STOVE_LAUNCH(gnn_step_bwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsFloats * sizeof(float), (hipStream_t)stream, s_in, params,
-               d_result, (const float*)nullptr, d_s_in, (float*)ws, B, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, stamps);
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  return STOVE_LAUNCH_LDS(gnn_step_bwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsBytes, (hipStream_t)stream, s_in, params,
+                          d_result, (const float*)nullptr, d_s_in, (float*)ws, B, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, stamps);
 }
 
 // debug: device buffer ([4 waves][16] int64) that the small-graph time loops stamp their phases into (last step,
 // workgroup 0); null = off.  Set by the measurement tools only.
 static long long* g_sm_stamps = nullptr;
 void stove_debug_set_stamps(long long* device_buffer) { g_sm_stamps = device_buffer; }
-
-// The small-graph recursion (gnn_small*.hip): kernels built for up to four objects (one node row per wave) and for up to six (two).
-static bool small_graph(int N) { return N >= 2 && N <= 6; }
 
 size_t stove_dynloop_act_floats(int B, int Ts, int N) {
   const int g = gnn_group_for(B, N);
@@ -904,65 +912,29 @@ int stove_dynloop_fwd(const float* z1, const float* zsup, const float* zsstd, co
                       void* stream) {
   STOVE_VALIDATE(dynloop_fwd(z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, B, Ts, N, sin_dim));
   if (B == 0 || Ts == 0) return 0;
-  if (N < 1 || N > 8 || sin_dim < 16 || sin_dim > 32 || (sin_dim > 16 && extra == nullptr)) return (int)hipErrorInvalidValue;
   LoopConst kc{pos_var, vel_std, lat_std};
   if (small_graph(N)) {      // small graphs: (half-)wave-per-node-row formulation, two barriers per step (gnn_small.hip)
-#define STOVE_LOOP_LAUNCH_N(SAVE_, NMX_, ELU_, NT_)                                                                             \
-  do {                                                                                                                          \
-    int rc = (int)hipFuncSetAttribute((const void*)dyn_loop_fwd_small_k<SAVE_, NMX_, ELU_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)(SmShape<NMX_>::kLdsFloats * sizeof(float)));                                        \
-    if (rc) return rc;                                                                                                          \
-    STOVE_LAUNCH((dyn_loop_fwd_small_k<SAVE_, NMX_, ELU_, NT_>), dim3(B), dim3(64 * kSmWaves), SmShape<NMX_>::kLdsFloats * sizeof(float), \
-                 (hipStream_t)stream, z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, \
-                 elu, kc, g_sm_stamps, 0, Ts);                                                                                  \
-  } while (0)
-#define STOVE_LOOP_LAUNCH_E(SAVE_, ELU_)                          \
-  do {                                                            \
-    if (N == 3) STOVE_LOOP_LAUNCH_N(SAVE_, 4, ELU_, 3);           \
-    else if (N <= 4) STOVE_LOOP_LAUNCH_N(SAVE_, 4, ELU_, 0);      \
-    else if (N == 6) STOVE_LOOP_LAUNCH_N(SAVE_, 6, ELU_, 6);      \
-    else STOVE_LOOP_LAUNCH_N(SAVE_, 6, ELU_, 0);                  \
-  } while (0)
-#define STOVE_LOOP_LAUNCH(SAVE_)                      \
-  do {                                                \
-    if (elu) STOVE_LOOP_LAUNCH_E(SAVE_, true);        \
-    else STOVE_LOOP_LAUNCH_E(SAVE_, false);           \
-  } while (0)
-    if (g_sm_stamps != nullptr && act != nullptr && !elu && N == 3) {      // tools/loop_stamps.py
-      int rc = (int)hipFuncSetAttribute((const void*)dyn_loop_fwd_small_k<2, 4, false, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(SmShape<4>::kLdsFloats * sizeof(float)));
-      if (rc) return rc;
-      STOVE_LAUNCH((dyn_loop_fwd_small_k<2, 4, false, 3, true>), dim3(B), dim3(64 * kSmWaves), SmShape<4>::kLdsFloats * sizeof(float), (hipStream_t)stream,
-                   z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, elu, kc, g_sm_stamps,
-                   0, Ts);
-    } else if (act != nullptr) {
-      STOVE_LOOP_LAUNCH(2);
-    } else {
-      STOVE_LOOP_LAUNCH(0);
-    }
-#undef STOVE_LOOP_LAUNCH
-#undef STOVE_LOOP_LAUNCH_E
-#undef STOVE_LOOP_LAUNCH_N
-    STOVE_LAUNCH_CHECK();
-    return 0;
+    auto launch = [&](auto save, auto nmx, auto e, auto nt, auto stamp) {
+      constexpr int NMX = decltype(nmx)::value;
+      return STOVE_LAUNCH_LDS((dyn_loop_fwd_small_k<decltype(save)::value, NMX, decltype(e)::value, decltype(nt)::value, decltype(stamp)::value>),
+                              dim3(B), dim3(64 * kSmWaves), SmShape<NMX>::kLdsFloats * sizeof(float), (hipStream_t)stream, z1, zsup, zsstd, eps,
+                              extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, elu, kc, g_sm_stamps, 0, Ts);
+    };
+    if (g_sm_stamps != nullptr && act != nullptr && !elu && N == 3)      // tools/loop_stamps.py: the one instantiation that stamps its phases
+      return launch(Int<2>{}, Int<4>{}, std::false_type{}, Int<3>{}, std::true_type{});
+    auto run = [&](auto save) {           // SAVE: 2 = keep the activations for the backward, 0 = none
+      return with_small_graph<true>(N, elu, true, [&](auto nmx, auto e, auto nt) { return launch(save, nmx, e, nt, std::false_type{}); });
+    };
+    return act != nullptr ? run(Int<2>{}) : run(Int<0>{});
   }
   const int G = gnn_group_for(B, N);
-  int rc = 0;
-#define STOVE_MLOOP_LAUNCH(ELU_, N6_)                                                                                                  \
-  do {                                                                                                                                 \
-    rc = gnn_lds_attr((const void*)dyn_loop_fwd_k<ELU_, N6_>);                                                                         \
-    if (rc) return rc;                                                                                                                 \
-    STOVE_LAUNCH((dyn_loop_fwd_k<ELU_, N6_>), dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsFloats * sizeof(float), (hipStream_t)stream, \
-                 z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, G, sin_dim, lim_enc, elu, kc);  \
-  } while (0)
-  const bool n6 = N == 6 && G == 1;
-  if (elu && n6) STOVE_MLOOP_LAUNCH(true, true);
-  else if (elu) STOVE_MLOOP_LAUNCH(true, false);
-  else if (n6) STOVE_MLOOP_LAUNCH(false, true);
-  else STOVE_MLOOP_LAUNCH(false, false);
-#undef STOVE_MLOOP_LAUNCH
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  return with_flag(elu, [&](auto e) {
+    return with_flag(N == 6 && G == 1, [&](auto n6) {
+      return STOVE_LAUNCH_LDS((dyn_loop_fwd_k<decltype(e)::value, decltype(n6)::value>), dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsBytes,
+                              (hipStream_t)stream, z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, G,
+                              sin_dim, lim_enc, elu, kc);
+    });
+  });
 }
 
 size_t stove_dynloop_bwd_ws_bytes(int B, int N) { return stove_gnn_bwd_ws_bytes(B, N); }
@@ -993,71 +965,53 @@ int stove_dynloop_bwd_overlap(const float* z1, const float* zsup, const float* z
   STOVE_VALIDATE(dynloop_bwd(z1, zsup, zsstd, eps, extra, params, z, dz1, dzsup, dzsstd, dextra, g_params, ws, B, Ts, N, sin_dim));
   hipStream_t st = (hipStream_t)stream;
   hipStream_t sp = param_stream != nullptr ? (hipStream_t)param_stream : st;
-  if (B == 0 || Ts == 0) return (int)hipErrorInvalidValue;
-  if (N < 1 || N > 8 || sin_dim < 16 || sin_dim > 32 || (sin_dim > 16 && (extra == nullptr || dextra == nullptr)))
-    return (int)hipErrorInvalidValue;
   LoopConst kc{pos_var, vel_std, lat_std};
   if (small_bwd_path(N, act)) {
     // small graphs: T-serial data-gradient chain (gnn_small_bwd.hip), then the weight gradients as a throughput pass
     float* gpart = (float*)ws;
     float* dy = gpart + (size_t)B * kGnnGrads;
-    int rc = 0;
-#define STOVE_LOOPB_LAUNCH_H(NMX_, ELU_, NT_, HD_)                                                                                    \
-  do {                                                                                                                                \
-    rc = (int)hipFuncSetAttribute((const void*)dyn_loop_bwd_small_k<NMX_, ELU_, NT_, HD_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)(smb_lds_floats<NMX_>() * sizeof(float)));                                                     \
-    if (rc) return rc;                                                                                                                \
-    STOVE_LAUNCH((dyn_loop_bwd_small_k<NMX_, ELU_, NT_, HD_>), dim3(B), dim3(64 * kSmWaves), smb_lds_floats<NMX_>() * sizeof(float), st, zsup, \
-                 zsstd, eps, params, const_cast<float*>(act), dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, dy, B, Ts, N, \
-                 sin_dim, lim_enc, elu, kc, g_sm_stamps, 0, Ts, (float*)nullptr);                                                     \
-  } while (0)
+    // HEAD: the instantiations for the gradients the training step hands over; only three and six objects have them
     const bool head = dz != nullptr && dzdyn != nullptr && dmean != nullptr && dstd != nullptr && dpred == nullptr && sin_dim == 16 && lim_enc == 2;
-#define STOVE_LOOPB_LAUNCH(ELU_)                                          \
-  do {                                                                    \
-    if (N == 3 && head) STOVE_LOOPB_LAUNCH_H(4, ELU_, 3, true);           \
-    else if (N == 3) STOVE_LOOPB_LAUNCH_H(4, ELU_, 3, false);             \
-    else if (N <= 4) STOVE_LOOPB_LAUNCH_H(4, ELU_, 0, false);             \
-    else if (N == 6 && head) STOVE_LOOPB_LAUNCH_H(6, ELU_, 6, true);      \
-    else STOVE_LOOPB_LAUNCH_H(6, ELU_, 0, false);                         \
-  } while (0)
-    if (g_sm_stamps != nullptr && !elu && N == 3 && head) {       // tools/loop_stamps.py
-      rc = (int)hipFuncSetAttribute((const void*)dyn_loop_bwd_small_k<4, false, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(smb_lds_floats<4>() * sizeof(float)));
-      if (rc) return rc;
-      STOVE_LAUNCH((dyn_loop_bwd_small_k<4, false, 3, true, true>), dim3(B), dim3(64 * kSmWaves), smb_lds_floats<4>() * sizeof(float), st, zsup, zsstd,
-                   eps, params, const_cast<float*>(act), dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, dy, B, Ts, N, sin_dim,
-                   lim_enc, elu, kc, g_sm_stamps, 0, Ts, (float*)nullptr);
-    } else if (elu) STOVE_LOOPB_LAUNCH(true);
-    else STOVE_LOOPB_LAUNCH(false);
-#undef STOVE_LOOPB_LAUNCH
-#undef STOVE_LOOPB_LAUNCH_H
-    STOVE_LAUNCH_CHECK();
-    rc = (int)hipFuncSetAttribute((const void*)gnn_dw_small_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDwLdsFloats * sizeof(float)));
+    auto launch = [&](auto nmx, auto e, auto nt, auto hd, auto stamp) {
+      constexpr int NMX = decltype(nmx)::value;
+      return STOVE_LAUNCH_LDS((dyn_loop_bwd_small_k<NMX, decltype(e)::value, decltype(nt)::value, decltype(hd)::value, decltype(stamp)::value>),
+                              dim3(B), dim3(64 * kSmWaves), smb_lds_floats<NMX>() * sizeof(float), st, zsup, zsstd, eps, params,
+                              const_cast<float*>(act), dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, dy, B, Ts, N, sin_dim, lim_enc,
+                              elu, kc, g_sm_stamps, 0, Ts, (float*)nullptr);
+    };
+    int rc;
+    if (g_sm_stamps != nullptr && !elu && N == 3 && head) {       // tools/loop_stamps.py: the one instantiation that stamps its phases
+      rc = launch(Int<4>{}, std::false_type{}, Int<3>{}, std::true_type{}, std::true_type{});
+    } else {
+      rc = with_small_graph<true>(N, elu, head, [&](auto nmx, auto e, auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if constexpr (NT == 6) {          // (reached with `head` only)
+          return launch(nmx, e, nt, std::true_type{}, std::false_type{});
+        } else {
+          if constexpr (NT == 3) {
+            if (head) return launch(nmx, e, nt, std::true_type{}, std::false_type{});
+          }
+          return launch(nmx, e, nt, std::false_type{}, std::false_type{});
+        }
+      });
+    }
     if (rc) return rc;
     STOVE_TRY(stream_after(sp, st));        // the weight-gradient pass reads the dY streams; it only feeds the optimiser (second stream)
-    STOVE_LAUNCH(gnn_dw_small_k, dim3(B), dim3(256), kDwLdsFloats * sizeof(float), sp, act, (const float*)dy, gpart, B, Ts, N);
-    STOVE_LAUNCH_CHECK();
+    rc = STOVE_LAUNCH_LDS(gnn_dw_small_k, dim3(B), dim3(256), kDwLdsFloats * sizeof(float), sp, act, (const float*)dy, gpart, B, Ts, N);
+    if (rc) return rc;
     STOVE_LAUNCH(reduce_chunks_k, dim3((kGnnGrads + 31) / 32), dim3(256), 0, sp, (const float*)gpart, g_params, kGnnGrads, B, 0);
     STOVE_LAUNCH_CHECK();
     return 0;
   }
   const int nb = stove_gnn_blocks(B, N), G = gnn_group_for(B, N);
-  int rc = 0;
-#define STOVE_MLOOPB_LAUNCH(ELU_, N6_)                                                                                                 \
-  do {                                                                                                                                 \
-    rc = gnn_lds_attr((const void*)dyn_loop_bwd_k<ELU_, N6_>);                                                                         \
-    if (rc) return rc;                                                                                                                 \
-    STOVE_LAUNCH((dyn_loop_bwd_k<ELU_, N6_>), dim3(nb), dim3(256), kGnnLdsFloats * sizeof(float), st, z1, zsup, zsstd, eps, extra,     \
-                 params, z, act, dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, (float*)ws, B, Ts, N, G, sin_dim, lim_enc, \
-                 elu, kc);                                                                                                             \
-  } while (0)
-  const bool n6 = N == 6 && G == 1;
-  if (elu && n6) STOVE_MLOOPB_LAUNCH(true, true);
-  else if (elu) STOVE_MLOOPB_LAUNCH(true, false);
-  else if (n6) STOVE_MLOOPB_LAUNCH(false, true);
-  else STOVE_MLOOPB_LAUNCH(false, false);
-#undef STOVE_MLOOPB_LAUNCH
-  STOVE_LAUNCH_CHECK();
+  int rc = with_flag(elu, [&](auto e) {
+    return with_flag(N == 6 && G == 1, [&](auto n6) {
+      return STOVE_LAUNCH_LDS((dyn_loop_bwd_k<decltype(e)::value, decltype(n6)::value>), dim3(nb), dim3(256), kGnnLdsBytes, st, z1, zsup, zsstd,
+                              eps, extra, params, z, act, dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, (float*)ws, B, Ts, N, G,
+                              sin_dim, lim_enc, elu, kc);
+    });
+  });
+  if (rc) return rc;
   STOVE_TRY(stream_after(sp, st));
   STOVE_LAUNCH(reduce_chunks_k, dim3((kGnnGrads + 31) / 32), dim3(256), 0, sp, (const float*)ws, g_params, kGnnGrads, nb, 0);
   STOVE_LAUNCH_CHECK();
@@ -1069,37 +1023,17 @@ int stove_rollout_fwd(const float* z_last, const float* extra, const float* para
                       float lat_std, void* stream) {
   STOVE_VALIDATE(rollout_fwd(z_last, extra, params, z_pred, B, num, A, N, sin_dim));
   if (B == 0 || num == 0) return 0;
-  if (N < 1 || N > 8 || sin_dim < 16 || sin_dim > 32 || (sin_dim > 16 && (extra == nullptr || A < 1))) return (int)hipErrorInvalidValue;
   LoopConst kc{pos_var, vel_std, lat_std};
-  if (N >= 2 && N <= 6) {
-    int rc;
-#define STOVE_ROLL_LAUNCH_N(NMX_, ELU_, NT_)                                                                                         \
-  do {                                                                                                                               \
-    rc = (int)hipFuncSetAttribute((const void*)rollout_fwd_small_k<NMX_, ELU_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                  (int)(SmShape<NMX_>::kLdsFloats * sizeof(float)));                                                 \
-    if (rc) return rc;                                                                                                               \
-    STOVE_LAUNCH((rollout_fwd_small_k<NMX_, ELU_, NT_>), dim3(B), dim3(64 * kSmWaves), SmShape<NMX_>::kLdsFloats * sizeof(float), (hipStream_t)stream, \
-                 z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, sin_dim, lim_enc, elu, kc);                    \
-  } while (0)
-#define STOVE_ROLL_LAUNCH(ELU_)                         \
-  do {                                                  \
-    if (N == 3) STOVE_ROLL_LAUNCH_N(4, ELU_, 3);        \
-    else if (N <= 4) STOVE_ROLL_LAUNCH_N(4, ELU_, 0);   \
-    else STOVE_ROLL_LAUNCH_N(6, ELU_, 0);               \
-  } while (0)
-    if (elu) STOVE_ROLL_LAUNCH(true);
-    else STOVE_ROLL_LAUNCH(false);
-#undef STOVE_ROLL_LAUNCH
-#undef STOVE_ROLL_LAUNCH_N
-    STOVE_LAUNCH_CHECK();
-    return 0;
+  if (small_graph(N)) {      // (no instantiation for six objects of its own)
+    return with_small_graph<false>(N, elu, false, [&](auto nmx, auto e, auto nt) {
+      constexpr int NMX = decltype(nmx)::value;
+      return STOVE_LAUNCH_LDS((rollout_fwd_small_k<NMX, decltype(e)::value, decltype(nt)::value>), dim3(B), dim3(64 * kSmWaves),
+                              SmShape<NMX>::kLdsFloats * sizeof(float), (hipStream_t)stream, z_last, extra, params, z_pred, zstd, pred, B, num,
+                              A < 1 ? 1 : A, N, sin_dim, lim_enc, elu, kc);
+    });
   }
-  int rc = gnn_lds_attr((const void*)rollout_fwd_k);
-  if (rc) return rc;
-  STOVE_LAUNCH(rollout_fwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsFloats * sizeof(float), (hipStream_t)stream,
-                     z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
-  STOVE_LAUNCH_CHECK();
-  return 0;
+  return STOVE_LAUNCH_LDS(rollout_fwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsBytes, (hipStream_t)stream, z_last, extra, params,
+                          z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
 }
 
 // ---------------------------------------------------------------- GNN dynamics core at state-code lengths 16 / 64 (gnn_cl.hip)
@@ -1114,32 +1048,26 @@ size_t stove_gnn_bwd_ws_bytes_cl(int cl, int B, int N) {
 
 int stove_gnn_fwd_cl(const float* s_in, const float* params, float* result, float* pred, int cl, int B, int N, int sin_dim,
                      int lim_enc, int elu, void* stream) {
-  STOVE_VALIDATE(gnn_fwd_cl(s_in, params, result, cl, B, N, sin_dim));
+  STOVE_VALIDATE(gnn_fwd(s_in, params, result, B, N, sin_dim, stove_validate::gnn_limits_cl(cl)));
   if (B == 0) return 0;
   return with_cl(cl, [&](auto w) {
     constexpr int CL = decltype(w)::value;
-    int rc = cl_lds_attr<CL>((const void*)gnn_cl_step_fwd_k<CL>);
-    if (rc) return rc;
-    STOVE_LAUNCH(gnn_cl_step_fwd_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
-                 s_in, params, result, pred, B, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu);
-    STOVE_LAUNCH_CHECK();
-    return 0;
+    return STOVE_LAUNCH_LDS(gnn_cl_step_fwd_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                            s_in, params, result, pred, B, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu);
   });
 }
 
 int stove_gnn_bwd_cl(const float* s_in, const float* params, const float* d_result, const float* d_pred, float* d_s_in,
                      float* g_params, void* ws, int cl, int B, int N, int sin_dim, int lim_enc, int elu, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  STOVE_VALIDATE(gnn_bwd_cl(s_in, params, d_result, d_s_in, g_params, ws, cl, B, N, sin_dim));
+  STOVE_VALIDATE(gnn_bwd(s_in, params, d_result, d_s_in, g_params, ws, B, N, sin_dim, stove_validate::gnn_limits_cl(cl)));
   return with_cl(cl, [&](auto w) {
     constexpr int CL = decltype(w)::value;
     if (B == 0) return (int)hipMemsetAsync(g_params, 0, GC<CL>::kGrads * sizeof(float), st);
-    int rc = cl_lds_attr<CL>((const void*)gnn_cl_step_bwd_k<CL>);
-    if (rc) return rc;
     const int nb = cl_blocks<CL>(B, N);
-    STOVE_LAUNCH(gnn_cl_step_bwd_k<CL>, dim3(nb), dim3(256), GC<CL>::kLdsFloats * sizeof(float), st, s_in, params, d_result, d_pred,
-                 d_s_in, (float*)ws, B, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu);
-    STOVE_LAUNCH_CHECK();
+    int rc = STOVE_LAUNCH_LDS(gnn_cl_step_bwd_k<CL>, dim3(nb), dim3(256), GC<CL>::kLdsFloats * sizeof(float), st, s_in, params, d_result, d_pred,
+                              d_s_in, (float*)ws, B, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu);
+    if (rc) return rc;
     STOVE_LAUNCH(reduce_chunks_k, dim3((GC<CL>::kGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, GC<CL>::kGrads, nb, 0);
     STOVE_LAUNCH_CHECK();
     return 0;
@@ -1150,18 +1078,14 @@ int stove_dynloop_fwd_cl(const float* z1, const float* zsup, const float* zsstd,
                          const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred,
                          int cl, int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
                          void* stream) {
-  STOVE_VALIDATE(dynloop_fwd_cl(z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, cl, B, Ts, N, sin_dim));
+  STOVE_VALIDATE(dynloop_fwd(z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, B, Ts, N, sin_dim, stove_validate::gnn_limits_cl(cl)));
   if (B == 0 || Ts == 0) return 0;
   LoopConst kc{pos_var, vel_std, lat_std};
   return with_cl(cl, [&](auto w) {
     constexpr int CL = decltype(w)::value;
-    int rc = cl_lds_attr<CL>((const void*)gnn_cl_loop_fwd_k<CL>);
-    if (rc) return rc;
-    STOVE_LAUNCH(gnn_cl_loop_fwd_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
-                 z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, B, Ts, N, cl_group_for<CL>(B, N), sin_dim, lim_enc,
-                 elu, kc);
-    STOVE_LAUNCH_CHECK();
-    return 0;
+    return STOVE_LAUNCH_LDS(gnn_cl_loop_fwd_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                            z1, zsup, zsstd, eps, extra, params, z, zdyn, zdstd, mean, std_, pred, B, Ts, N, cl_group_for<CL>(B, N), sin_dim,
+                            lim_enc, elu, kc);
   });
 }
 
@@ -1171,18 +1095,17 @@ int stove_dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd,
                          float* g_params, void* ws, int cl, int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var,
                          float vel_std, float lat_std, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  STOVE_VALIDATE(dynloop_bwd_cl(z1, zsup, zsstd, eps, extra, params, z, dz1, dzsup, dzsstd, dextra, g_params, ws, cl, B, Ts, N, sin_dim));
+  STOVE_VALIDATE(dynloop_bwd(z1, zsup, zsstd, eps, extra, params, z, dz1, dzsup, dzsstd, dextra, g_params, ws, B, Ts, N, sin_dim,
+                             stove_validate::gnn_limits_cl(cl)));
   LoopConst kc{pos_var, vel_std, lat_std};
   return with_cl(cl, [&](auto w) {
     constexpr int CL = decltype(w)::value;
     if (B == 0 || Ts == 0) return (int)hipMemsetAsync(g_params, 0, GC<CL>::kGrads * sizeof(float), st);
-    int rc = cl_lds_attr<CL>((const void*)gnn_cl_loop_bwd_k<CL>);
-    if (rc) return rc;
     const int nb = cl_blocks<CL>(B, N);
-    STOVE_LAUNCH(gnn_cl_loop_bwd_k<CL>, dim3(nb), dim3(256), GC<CL>::kLdsFloats * sizeof(float), st, z1, zsup, zsstd, eps, extra, params, z,
-                 dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, (float*)ws, B, Ts, N, cl_group_for<CL>(B, N), sin_dim, lim_enc,
-                 elu, kc);
-    STOVE_LAUNCH_CHECK();
+    int rc = STOVE_LAUNCH_LDS(gnn_cl_loop_bwd_k<CL>, dim3(nb), dim3(256), GC<CL>::kLdsFloats * sizeof(float), st, z1, zsup, zsstd, eps, extra,
+                              params, z, dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, (float*)ws, B, Ts, N,
+                              cl_group_for<CL>(B, N), sin_dim, lim_enc, elu, kc);
+    if (rc) return rc;
     STOVE_LAUNCH(reduce_chunks_k, dim3((GC<CL>::kGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, GC<CL>::kGrads, nb, 0);
     STOVE_LAUNCH_CHECK();
     return 0;
@@ -1192,17 +1115,14 @@ int stove_dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd,
 int stove_rollout_fwd_cl(const float* z_last, const float* extra, const float* params, float* z_pred, float* zstd, float* pred,
                          int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std,
                          float lat_std, void* stream) {
-  STOVE_VALIDATE(rollout_fwd_cl(z_last, extra, params, z_pred, cl, B, num, A, N, sin_dim));
+  STOVE_VALIDATE(rollout_fwd(z_last, extra, params, z_pred, B, num, A, N, sin_dim, stove_validate::gnn_limits_cl(cl)));
   if (B == 0 || num == 0) return 0;
   LoopConst kc{pos_var, vel_std, lat_std};
   return with_cl(cl, [&](auto w) {
     constexpr int CL = decltype(w)::value;
-    int rc = cl_lds_attr<CL>((const void*)gnn_cl_rollout_k<CL>);
-    if (rc) return rc;
-    STOVE_LAUNCH(gnn_cl_rollout_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
-                 z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu, kc);
-    STOVE_LAUNCH_CHECK();
-    return 0;
+    return STOVE_LAUNCH_LDS(gnn_cl_rollout_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                            z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu,
+                            kc);
   });
 }
 

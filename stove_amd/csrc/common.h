@@ -268,3 +268,17 @@ struct ProfScope {
     hipError_t e__ = hipGetLastError();               \
     if (e__ != hipSuccess) return (int)e__;           \
   } while (0)
+
+// A launch with `lds` bytes of dynamic LDS, more than a kernel gets unasked: its limit is raised first.  -> the error code
+namespace stove {
+template <class... P, class... A>
+static int launch_lds(const char* name, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  STOVE_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  {
+    ProfScope ps(name, st);
+    hipLaunchKernelGGL(kern, grid, block, lds, st, (P)args...);
+  }
+  return (int)hipGetLastError();
+}
+}  // namespace stove
+#define STOVE_LAUNCH_LDS(kern, ...) stove::launch_lds(#kern, kern, __VA_ARGS__)

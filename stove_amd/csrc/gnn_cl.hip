@@ -896,10 +896,6 @@ static inline int with_cl(int cl, F f) {
   return (int)hipErrorInvalidValue;
 }
 template <int CL>
-static inline int cl_lds_attr(const void* fn) {
-  return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GC<CL>::kLdsFloats * sizeof(float)));
-}
-template <int CL>
 static inline int cl_blocks(int B, int N) {
   const int g = cl_group_for<CL>(B, N);
   return (B + g - 1) / g;

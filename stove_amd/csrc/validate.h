@@ -123,88 +123,55 @@ inline int scene_ch_bwd(const int32_t* lscope, const int32_t* slot, const float*
   return 0;
 }
 
-// ---- Dynamics.forward (stove_gnn_*), the recursion (stove_dynloop_*), Stove.rollout
-inline int gnn_shape(int B, int N, int sin_dim) {
-  if (B < 0 || N < 1 || N > kMaxObjects || sin_dim < 16 || sin_dim > 32) return kStoveInvalidValue;
-  return 0;
-}
-inline int gnn_fwd(const float* s_in, const float* params, const float* result, int B, int N, int sin_dim) {
-  if (gnn_shape(B, N, sin_dim)) return kStoveInvalidValue;
+// ---- Dynamics.forward (stove_gnn_*), the recursion (stove_dynloop_*), Stove.rollout: one check per operation, run with the limits
+// of the kernels that serve the state-code length -- cl = 32 (csrc/gnn.hip, gnn_small*.hip) or 16 / 64 (stove_*_cl, csrc/gnn_cl.hip)
+constexpr int kMaxObjectsCl = 6;
+struct GnnLimits {
+  int lo, hi, max_obj;        // state width cl / 2 <= sin_dim <= cl, N <= max_obj; hi == 0: no kernels for this width
+  bool empty_bwd;             // an empty backward (B == 0 or Ts == 0) is checked here as the call that zeroes g_params; false: see gnn_bwd, dynloop_bwd
+  bool bad(int B, int N, int sin_dim) const { return hi == 0 || B < 0 || N < 1 || N > max_obj || sin_dim < lo || sin_dim > hi; }
+};
+constexpr GnnLimits kGnn32{16, 32, kMaxObjects, false};
+inline GnnLimits gnn_limits_cl(int cl) { return (cl == 16 || cl == 64) ? GnnLimits{cl / 2, cl, kMaxObjectsCl, true} : GnnLimits{0, 0, 0, true}; }
+
+inline int gnn_fwd(const float* s_in, const float* params, const float* result, int B, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (k.bad(B, N, sin_dim)) return kStoveInvalidValue;
   if (B == 0) return 0;
   return null_any(s_in, params, result) ? kStoveInvalidValue : 0;
 }
-inline int gnn_bwd(const float* s_in, const float* params, const float* d_result, const float* d_s_in, const float* g_params, const void* ws,
-                   int B, int N, int sin_dim) {
-  if (gnn_shape(B, N, sin_dim)) return kStoveInvalidValue;
+// (B == 0 zeroes g_params at every width; stove_gnn_bwd tests that pointer itself, ahead of this check)
+inline int gnn_bwd(const float* s_in, const float* params, const float* d_result, const float* d_s_in, const float* g_params,
+                   const void* ws, int B, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (k.bad(B, N, sin_dim) || (k.empty_bwd && g_params == nullptr)) return kStoveInvalidValue;
   if (B == 0) return 0;
   return (null_any(s_in, params, d_result, d_s_in, g_params) || ws == nullptr) ? kStoveInvalidValue : 0;
 }
-inline int dynloop_fwd(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra, const float* params,
-                       const float* z, const float* zdyn, const float* zdstd, const float* mean, const float* std_, int B, int Ts, int N,
-                       int sin_dim) {
-  if (gnn_shape(B, N, sin_dim) || Ts < 0) return kStoveInvalidValue;
+inline int dynloop_fwd(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
+                       const float* params, const float* z, const float* zdyn, const float* zdstd, const float* mean, const float* std_, int B,
+                       int Ts, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (k.bad(B, N, sin_dim) || Ts < 0) return kStoveInvalidValue;
   if (B == 0 || Ts == 0) return 0;
   if (null_any(z1, zsup, zsstd, eps, params, z, zdyn, zdstd, mean, std_)) return kStoveInvalidValue;
-  if (sin_dim > 16 && extra == nullptr) return kStoveInvalidValue;
+  if (sin_dim > k.lo && extra == nullptr) return kStoveInvalidValue;
   return 0;
 }
-inline int dynloop_bwd(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra, const float* params,
-                       const float* z, const float* dz1, const float* dzsup, const float* dzsstd, const float* dextra, const float* g_params,
-                       const void* ws, int B, int Ts, int N, int sin_dim) {
-  if (gnn_shape(B, N, sin_dim) || B == 0 || Ts <= 0) return kStoveInvalidValue;       // (an empty backward has nothing to overwrite g_params with)
-  if (null_any(z1, zsup, zsstd, eps, params, z, dz1, dzsup, dzsstd, g_params) || ws == nullptr) return kStoveInvalidValue;
-  if (sin_dim > 16 && (extra == nullptr || dextra == nullptr)) return kStoveInvalidValue;
-  return 0;
-}
-inline int rollout_fwd(const float* z_last, const float* extra, const float* params, const float* z_pred, int B, int num, int A, int N,
-                       int sin_dim) {
-  if (gnn_shape(B, N, sin_dim) || num < 0) return kStoveInvalidValue;
-  if (B == 0 || num == 0) return 0;
-  if (null_any(z_last, params, z_pred)) return kStoveInvalidValue;
-  if (sin_dim > 16 && (extra == nullptr || A < 1)) return kStoveInvalidValue;
-  return 0;
-}
-
-// ---- the same at state-code lengths other than 32 (stove_*_cl, csrc/gnn_cl.hip): cl 16 or 64, N <= 6, cl/2 <= sin_dim <= cl
-constexpr int kMaxObjectsCl = 6;
-inline bool gnn_cl_bad(int cl, int B, int N, int sin_dim) {
-  return (cl != 16 && cl != 64) || B < 0 || N < 1 || N > kMaxObjectsCl || sin_dim < cl / 2 || sin_dim > cl;
-}
-inline int gnn_fwd_cl(const float* s_in, const float* params, const float* result, int cl, int B, int N, int sin_dim) {
-  if (gnn_cl_bad(cl, B, N, sin_dim)) return kStoveInvalidValue;
-  if (B == 0) return 0;
-  return null_any(s_in, params, result) ? kStoveInvalidValue : 0;
-}
-inline int gnn_bwd_cl(const float* s_in, const float* params, const float* d_result, const float* d_s_in, const float* g_params,
-                      const void* ws, int cl, int B, int N, int sin_dim) {
-  if (gnn_cl_bad(cl, B, N, sin_dim) || g_params == nullptr) return kStoveInvalidValue;
-  if (B == 0) return 0;
-  return (null_any(s_in, params, d_result, d_s_in) || ws == nullptr) ? kStoveInvalidValue : 0;
-}
-inline int dynloop_fwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra, const float* params,
-                          const float* z, const float* zdyn, const float* zdstd, const float* mean, const float* std_, int cl, int B, int Ts,
-                          int N, int sin_dim) {
-  if (gnn_cl_bad(cl, B, N, sin_dim) || Ts < 0) return kStoveInvalidValue;
-  if (B == 0 || Ts == 0) return 0;
-  if (null_any(z1, zsup, zsstd, eps, params, z, zdyn, zdstd, mean, std_)) return kStoveInvalidValue;
-  if (sin_dim > cl / 2 && extra == nullptr) return kStoveInvalidValue;
-  return 0;
-}
-inline int dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra, const float* params,
-                          const float* z, const float* dz1, const float* dzsup, const float* dzsstd, const float* dextra,
-                          const float* g_params, const void* ws, int cl, int B, int Ts, int N, int sin_dim) {
-  if (gnn_cl_bad(cl, B, N, sin_dim) || Ts < 0 || g_params == nullptr) return kStoveInvalidValue;
-  if (B == 0 || Ts == 0) return 0;                    // an empty backward zeroes g_params, as stove_gnn_bwd_cl does
+// An empty backward (B == 0 or Ts == 0): stove_dynloop_bwd has nothing to overwrite g_params with and refuses it; stove_dynloop_bwd_cl
+// zeroes g_params, as stove_gnn_bwd_cl does.
+inline int dynloop_bwd(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
+                       const float* params, const float* z, const float* dz1, const float* dzsup, const float* dzsstd, const float* dextra,
+                       const float* g_params, const void* ws, int B, int Ts, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (k.bad(B, N, sin_dim) || Ts < 0 || g_params == nullptr) return kStoveInvalidValue;
+  if (B == 0 || Ts == 0) return k.empty_bwd ? 0 : kStoveInvalidValue;
   if (null_any(z1, zsup, zsstd, eps, params, z, dz1, dzsup, dzsstd) || ws == nullptr) return kStoveInvalidValue;
-  if (sin_dim > cl / 2 && (extra == nullptr || dextra == nullptr)) return kStoveInvalidValue;
+  if (sin_dim > k.lo && (extra == nullptr || dextra == nullptr)) return kStoveInvalidValue;
   return 0;
 }
-inline int rollout_fwd_cl(const float* z_last, const float* extra, const float* params, const float* z_pred, int cl, int B, int num, int A,
-                          int N, int sin_dim) {
-  if (gnn_cl_bad(cl, B, N, sin_dim) || num < 0) return kStoveInvalidValue;
+inline int rollout_fwd(const float* z_last, const float* extra, const float* params, const float* z_pred, int B, int num,
+                       int A, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (k.bad(B, N, sin_dim) || num < 0) return kStoveInvalidValue;
   if (B == 0 || num == 0) return 0;
   if (null_any(z_last, params, z_pred)) return kStoveInvalidValue;
-  if (sin_dim > cl / 2 && (extra == nullptr || A < 1)) return kStoveInvalidValue;
+  if (sin_dim > k.lo && (extra == nullptr || A < 1)) return kStoveInvalidValue;
   return 0;
 }
 

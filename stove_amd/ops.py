@@ -566,10 +566,18 @@ def wave_sum_selftest(x):
 
 
 # ------------------------------------------------------------------------------------------------
-# GNN dynamics core and the fused inference recursion (csrc/gnn.hip)
+# GNN dynamics core and the fused inference recursion: the tuned kernels for the state-code length cl = 32 (csrc/gnn.hip,
+# csrc/gnn_small*.hip) and the width-generic ones for cl = 16 / 64 (csrc/gnn_cl.hip)
 # ------------------------------------------------------------------------------------------------
-GNN_W_FLOATS = 22528
-GNN_V_FLOATS = 672
+GNN_CL_WIDTHS = (16, 64)
+
+
+def gnn_w_floats(cl):
+    return 22 * cl * cl
+
+
+GNN_W_FLOATS = gnn_w_floats(32)
+GNN_V_FLOATS = 21 * 32
 
 
 # layers of the W image: (offset, OUT, K) as the forward uses them; the W^T image holds the same layers transposed (K, OUT swapped)
@@ -596,85 +604,141 @@ def gnn_pack_perms(device):
     return _GNN_PERMS[key]
 
 
-def _gnn_image(w_img, v_img, wt_img):
-    if v_img is None:                          # prebuilt [W | W^T | vectors | W packed | W^T packed] image (ParamArena.gnn_image)
-        need = _lib.load().stove_gnn_param_floats()
-        if w_img.numel() != need:              # an image in an older layout would be read past its end by the kernels
-            raise ValueError('GNN parameter image has %d floats, libstove_hip.so expects %d (stove_gnn_param_floats)' % (w_img.numel(), need))
-        return w_img
-    pf, pt = gnn_pack_perms(w_img.device)
-    with torch.no_grad():
-        packed = torch.cat([w_img.detach()[pf], wt_img.detach()[pt]])
-    return torch.cat([w_img, wt_img, v_img, packed]).contiguous()
+class _GnnWidth:
+    """What depends on the state-code length in the dynamics ops: the sizes, the parameter image and the entry points.  The entry
+    points of cl = 16 / 64 are those of cl = 32 with `_cl` appended and `cl` passed between the pointers and B; what only the tuned
+    kernels of cl = 32 have is `tuned`: the packed sections of the image, the recursion's saved activations (so its backward has a
+    workspace query of its own) and the backward that puts the weight gradients on a second stream."""
+
+    def __init__(self, cl):
+        self.cl, self.D = cl, cl // 2                       # states are D + 2 wide
+        self.w_floats, self.v_floats = gnn_w_floats(cl), 21 * cl    # the gradient image is [dW | dvectors]
+        self.tuned = cl == 32
+        self.sfx, self.at = ('', ()) if self.tuned else ('_cl', (cl,))
+
+    def layout(self, w_img, v_img, wt_img):
+        """THE layout of the parameter image: [W | W^T | vectors], for the tuned kernels followed by [W packed | W^T packed] (both
+        weight sections again in the order the small-graph kernels copy into LDS; no gradient comes back through them).  Also run
+        on tensors of arena indices: ParamArena's gather table."""
+        if not self.tuned:
+            return torch.cat([w_img, wt_img, v_img]).contiguous()
+        pf, pt = gnn_pack_perms(w_img.device)
+        with torch.no_grad():
+            packed = torch.cat([w_img.detach()[pf], wt_img.detach()[pt]])
+        return torch.cat([w_img, wt_img, v_img, packed]).contiguous()
+
+    def image(self, w_img, v_img, wt_img):
+        """The image the kernels read, from (w_img, v_img, wt_img) of Dynamics.param_image or from (prebuilt image, None, None) of
+        ParamArena.gnn_image; one of another size than the kernels' would be read past its end."""
+        if self.tuned:
+            if v_img is not None:
+                return self.layout(w_img, v_img, wt_img)
+            need = self.size('stove_gnn_param_floats')
+            if w_img.numel() != need:
+                raise ValueError('GNN parameter image has %d floats, libstove_hip.so expects %d (stove_gnn_param_floats)' % (w_img.numel(), need))
+            return w_img
+        have = w_img.numel() if v_img is None else w_img.numel() + v_img.numel() + wt_img.numel()
+        need = 2 * self.w_floats + self.v_floats
+        if have != need:
+            raise ValueError('GNN parameter image has %d floats, cl = %d needs %d' % (have, self.cl, need))
+        return w_img if v_img is None else self.layout(w_img, v_img, wt_img)
+
+    def size(self, query, *dims):
+        """stove_gnn_param_floats / stove_gnn_grad_floats / stove_gnn_bwd_ws_bytes (B, N) of this width"""
+        return getattr(_lib.load(), query + self.sfx)(*self.at, *dims)
+
+    def loop_bwd_ws_bytes(self, B, Ts, N):
+        if self.tuned:
+            return _lib.load().stove_dynloop_bwd_ws_bytes_ts(B, Ts, N)
+        return self.size('stove_gnn_bwd_ws_bytes', B, N)
+
+    def call(self, entry, ptrs, *rest):
+        """entry(*ptrs, [cl,] *rest) of this width"""
+        check(getattr(_lib.load(), entry + self.sfx)(*ptrs, *self.at, *rest), entry + self.sfx)
+
+    def split(self, g):
+        return g[:self.w_floats], g[self.w_floats:]
+
+
+_GNN_WIDTHS = {cl: _GnnWidth(cl) for cl in (32,) + GNN_CL_WIDTHS}
+
+
+def gnn_width(cl):
+    if cl not in _GNN_WIDTHS:
+        raise NotImplementedError('the GNN kernels are built for cl in (16, 32, 64), got %d' % cl)
+    return _GNN_WIDTHS[cl]
+
+
+def _gnn_image(w_img, v_img, wt_img, cl=32):
+    return gnn_width(cl).image(w_img, v_img, wt_img)
 
 
 class _GnnStepFn(torch.autograd.Function):
-    """Dynamics.forward core (reference dynamics.py:181-265): s_in (B,N,sin_dim) -> result, dynamic_pred (B,N,32)."""
+    """Dynamics.forward core (reference dynamics.py:181-265): s_in (B,N,sin_dim) -> result, dynamic_pred (B,N,cl)."""
 
     @staticmethod
-    def forward(ctx, s_in, w_img, v_img, wt_img, lim_enc, elu, sink=None):
-        lib = _lib.load()
+    def forward(ctx, s_in, w_img, v_img, wt_img, width, lim_enc, elu, sink=None):
         s_in = _f32(s_in)
         B, N, sd = s_in.shape
         dev = s_in.device
-        params = _gnn_image(_f32(w_img), _f32(v_img), _f32(wt_img))
+        params = width.image(_f32(w_img), _f32(v_img), _f32(wt_img))
         ctx.sink = sink
         with torch.cuda.device(dev):
-            res = torch.empty(B, N, 32, dtype=torch.float32, device=dev)
-            pred = torch.empty(B, N, 32, dtype=torch.float32, device=dev)
-            check(lib.stove_gnn_fwd(ptr(s_in), ptr(params), ptr(res), ptr(pred), B, N, sd, int(lim_enc), int(elu), stream()),
-                  'stove_gnn_fwd')
+            res = torch.empty(B, N, width.cl, dtype=torch.float32, device=dev)
+            pred = torch.empty(B, N, width.cl, dtype=torch.float32, device=dev)
+            width.call('stove_gnn_fwd', (ptr(s_in), ptr(params), ptr(res), ptr(pred)), B, N, sd, int(lim_enc), int(elu), stream())
         ctx.save_for_backward(s_in, params)
-        ctx.cfg = (int(lim_enc), int(elu))
+        ctx.cfg = (width, int(lim_enc), int(elu))
         return res, pred
 
     @staticmethod
     def backward(ctx, dres, dpred):
-        lib = _lib.load()
         s_in, params = ctx.saved_tensors
         B, N, sd = s_in.shape
         dev = s_in.device
-        lim_enc, elu = ctx.cfg
+        width, lim_enc, elu = ctx.cfg
         with torch.cuda.device(dev):
-            dres = _f32(dres) if dres is not None else torch.zeros(B, N, 32, device=dev)
+            dres = _f32(dres) if dres is not None else torch.zeros(B, N, width.cl, device=dev)
             dpred = _f32(dpred) if dpred is not None else None
             d_s = torch.empty_like(s_in)
-            g = torch.empty(lib.stove_gnn_grad_floats(), dtype=torch.float32, device=dev)
-            ws = _ws(lib.stove_gnn_bwd_ws_bytes(B, N), dev)
-            check(lib.stove_gnn_bwd(ptr(s_in), ptr(params), ptr(dres), ptr(dpred), ptr(d_s), ptr(g), ptr(ws), B, N, sd,
-                                    lim_enc, elu, stream()), 'stove_gnn_bwd')
+            g = torch.empty(width.size('stove_gnn_grad_floats'), dtype=torch.float32, device=dev)
+            ws = _ws(width.size('stove_gnn_bwd_ws_bytes', B, N), dev)
+            width.call('stove_gnn_bwd', (ptr(s_in), ptr(params), ptr(dres), ptr(dpred), ptr(d_s), ptr(g), ptr(ws)), B, N, sd,
+                       lim_enc, elu, stream())
         if ctx.sink is not None:
             ctx.sink(g)
-            return d_s, None, None, None, None, None, None
-        return d_s, g[:GNN_W_FLOATS], g[GNN_W_FLOATS:], None, None, None, None
+            return (d_s,) + (None,) * 7
+        return (d_s, *width.split(g)) + (None,) * 5
 
 
 class _DynLoopFn(torch.autograd.Function):
-    """The T-serial inference recursion of Stove.stove_forward in one persistent kernel."""
+    """The T-serial inference recursion of Stove.stove_forward in one persistent kernel each way.  The tuned kernels save their
+    activations for the backward; the width-generic backward recomputes each step's forward."""
 
     @staticmethod
-    def forward(ctx, z1, zsup, zsstd, eps, extra, w_img, v_img, wt_img, lim_enc, elu, consts, want_pred, sink=None):
+    def forward(ctx, z1, zsup, zsstd, eps, extra, w_img, v_img, wt_img, width, lim_enc, elu, consts, want_pred, sink=None):
         lib = _lib.load()
         z1, zsup, zsstd, eps = _f32(z1), _f32(zsup), _f32(zsstd), _f32(eps)
         extra = _f32(extra)
         B, Ts, N = zsup.shape[:3]
-        sd = 16 + (extra.shape[-1] if extra is not None else 0)
+        D = width.D
+        sd = D + (extra.shape[-1] if extra is not None else 0)
         dev = z1.device
-        params = _gnn_image(_f32(w_img), _f32(v_img), _f32(wt_img))
+        params = width.image(_f32(w_img), _f32(v_img), _f32(wt_img))
         with torch.cuda.device(dev):
             def out(d):
                 return torch.empty(B, Ts, N, d, dtype=torch.float32, device=dev)
-            z, zdyn, zdstd, mean, std = out(18), out(16), out(16), out(18), out(18)
-            pred = out(32) if want_pred else None
+            z, zdyn, zdstd, mean, std = out(D + 2), out(D), out(D), out(D + 2), out(D + 2)
+            pred = out(width.cl) if want_pred else None
             # saved activations (291 MB at B=256, T=100, N=3) so the backward does not recompute the forward
             act = None
-            if any(ctx.needs_input_grad):
+            if width.tuned and any(ctx.needs_input_grad):
                 act = torch.empty(lib.stove_dynloop_act_floats(B, Ts, N) + 1, dtype=torch.float32, device=dev)
-            check(lib.stove_dynloop_fwd(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z), ptr(zdyn),
-                                        ptr(zdstd), ptr(mean), ptr(std), ptr(pred), ptr(act), B, Ts, N, sd, int(lim_enc),
-                                        int(elu), *[float(c) for c in consts], stream()), 'stove_dynloop_fwd')
+            width.call('stove_dynloop_fwd', (ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z), ptr(zdyn),
+                                             ptr(zdstd), ptr(mean), ptr(std), ptr(pred)) + ((ptr(act),) if width.tuned else ()),
+                       B, Ts, N, sd, int(lim_enc), int(elu), *[float(c) for c in consts], stream())
         ctx.save_for_backward(z1, zsup, zsstd, eps, extra, params, z, act)
-        ctx.cfg = (int(lim_enc), int(elu), tuple(float(c) for c in consts), sd)
+        ctx.cfg = (width, int(lim_enc), int(elu), tuple(float(c) for c in consts), sd)
         ctx.sink = sink
         ctx.set_materialize_grads(False)          # no zero tensors (one fill launch each) for the outputs nothing differentiates
         ctx.mark_non_differentiable(zdstd)
@@ -685,150 +749,8 @@ class _DynLoopFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, dzdyn, _dzdstd, dmean, dstd, dpred):
-        lib = _lib.load()
         z1, zsup, zsstd, eps, extra, params, z, act = ctx.saved_tensors
-        lim_enc, elu, consts, sd = ctx.cfg
-        B, Ts, N = zsup.shape[:3]
-        dev = z1.device
-
-        def up(g, shape_like):
-            return None if g is None or g.numel() == 0 else _f32(g)
-        with torch.cuda.device(dev):
-            dz1 = torch.empty_like(z1)
-            dzsup, dzsstd = torch.empty_like(zsup), torch.empty_like(zsstd)
-            dextra = torch.empty_like(extra) if extra is not None else None
-            g = torch.empty(lib.stove_gnn_grad_floats(), dtype=torch.float32, device=dev)
-            ws = _ws(lib.stove_dynloop_bwd_ws_bytes_ts(B, Ts, N), dev)
-            if ctx.sink is not None and _settings.OVERLAP:
-                # weight gradients (only the optimiser reads them) on the second stream, under the encoder's backward GEMMs
-                main, side = torch.cuda.current_stream(dev), _side_stream(dev)
-                check(lib.stove_dynloop_bwd_overlap(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z), ptr(act),
-                                                    ptr(up(dz, z)), ptr(up(dzdyn, z)), ptr(up(dmean, z)), ptr(up(dstd, z)),
-                                                    ptr(up(dpred, z)), ptr(dz1), ptr(dzsup), ptr(dzsstd), ptr(dextra), ptr(g), ptr(ws),
-                                                    B, Ts, N, sd, lim_enc, elu, *consts, main.cuda_stream, side.cuda_stream),
-                      'stove_dynloop_bwd_overlap')
-                run_on_side(dev, lambda: ctx.sink(g), (ws, g, act), after_main=False)
-                join_side_after_backward(dev)
-                return (dz1, dzsup, dzsstd, None, dextra) + (None,) * 8
-            check(lib.stove_dynloop_bwd(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z), ptr(act),
-                                        ptr(up(dz, z)), ptr(up(dzdyn, z)), ptr(up(dmean, z)), ptr(up(dstd, z)),
-                                        ptr(up(dpred, z)), ptr(dz1), ptr(dzsup), ptr(dzsstd), ptr(dextra), ptr(g), ptr(ws),
-                                        B, Ts, N, sd, lim_enc, elu, *consts, stream()), 'stove_dynloop_bwd')
-        if ctx.sink is not None:
-            ctx.sink(g)
-            return (dz1, dzsup, dzsstd, None, dextra) + (None,) * 8
-        return (dz1, dzsup, dzsstd, None, dextra, g[:GNN_W_FLOATS], g[GNN_W_FLOATS:], None, None, None, None, None, None)
-
-
-# ---- state-code lengths other than 32 (csrc/gnn_cl.hip): image [W | W^T | vectors], 22 cl^2 weight and 21 cl vector floats
-GNN_CL_WIDTHS = (16, 64)
-
-
-def gnn_w_floats(cl):
-    return 22 * cl * cl
-
-
-def _check_image_cl(image, cl):
-    """A parameter image -- (w_img, v_img, wt_img) or (flat image, None, None) -- must have the size of its width's layout."""
-    if cl == 32:
-        return                                  # (_gnn_image checks the flat cl = 32 image against stove_gnn_param_floats)
-    if cl not in GNN_CL_WIDTHS:
-        raise NotImplementedError('the GNN kernels are built for cl in (16, 32, 64), got %d' % cl)
-    have = image[0].numel() if image[1] is None else image[0].numel() + image[1].numel() + image[2].numel()
-    need = 2 * gnn_w_floats(cl) + 21 * cl
-    if have != need:
-        raise ValueError('GNN parameter image has %d floats, cl = %d needs %d' % (have, cl, need))
-
-
-def _gnn_image_cl(w_img, v_img, wt_img, cl):
-    if cl not in GNN_CL_WIDTHS:
-        raise NotImplementedError('the GNN kernels are built for cl in (16, 32, 64), got %d' % cl)
-    if v_img is None:                          # prebuilt [W | W^T | vectors] image
-        need = _lib.load().stove_gnn_param_floats_cl(cl)
-        if w_img.numel() != need:
-            raise ValueError('GNN parameter image has %d floats, libstove_hip.so expects %d at cl = %d' % (w_img.numel(), need, cl))
-        return w_img
-    return torch.cat([w_img, wt_img, v_img]).contiguous()
-
-
-class _GnnStepClFn(torch.autograd.Function):
-    """_GnnStepFn at cl = 16 / 64: s_in (B,N,sin_dim) -> result, dynamic_pred (B,N,cl)."""
-
-    @staticmethod
-    def forward(ctx, s_in, w_img, v_img, wt_img, cl, lim_enc, elu, sink=None):
-        lib = _lib.load()
-        s_in = _f32(s_in)
-        B, N, sd = s_in.shape
-        dev = s_in.device
-        params = _gnn_image_cl(_f32(w_img), _f32(v_img), _f32(wt_img), cl)
-        ctx.sink = sink
-        with torch.cuda.device(dev):
-            res = torch.empty(B, N, cl, dtype=torch.float32, device=dev)
-            pred = torch.empty(B, N, cl, dtype=torch.float32, device=dev)
-            check(lib.stove_gnn_fwd_cl(ptr(s_in), ptr(params), ptr(res), ptr(pred), cl, B, N, sd, int(lim_enc), int(elu), stream()),
-                  'stove_gnn_fwd_cl')
-        ctx.save_for_backward(s_in, params)
-        ctx.cfg = (cl, int(lim_enc), int(elu))
-        return res, pred
-
-    @staticmethod
-    def backward(ctx, dres, dpred):
-        lib = _lib.load()
-        s_in, params = ctx.saved_tensors
-        B, N, sd = s_in.shape
-        dev = s_in.device
-        cl, lim_enc, elu = ctx.cfg
-        with torch.cuda.device(dev):
-            dres = _f32(dres) if dres is not None else torch.zeros(B, N, cl, device=dev)
-            dpred = _f32(dpred) if dpred is not None else None
-            d_s = torch.empty_like(s_in)
-            g = torch.empty(lib.stove_gnn_grad_floats_cl(cl), dtype=torch.float32, device=dev)
-            ws = _ws(lib.stove_gnn_bwd_ws_bytes_cl(cl, B, N), dev)
-            check(lib.stove_gnn_bwd_cl(ptr(s_in), ptr(params), ptr(dres), ptr(dpred), ptr(d_s), ptr(g), ptr(ws), cl, B, N, sd,
-                                       lim_enc, elu, stream()), 'stove_gnn_bwd_cl')
-        if ctx.sink is not None:
-            ctx.sink(g)
-            return (d_s,) + (None,) * 7
-        W = gnn_w_floats(cl)
-        return d_s, g[:W], g[W:], None, None, None, None, None
-
-
-class _DynLoopClFn(torch.autograd.Function):
-    """_DynLoopFn at cl = 16 / 64: all Ts steps in one launch each way; the backward recomputes each step's forward."""
-
-    @staticmethod
-    def forward(ctx, z1, zsup, zsstd, eps, extra, w_img, v_img, wt_img, cl, lim_enc, elu, consts, want_pred, sink=None):
-        lib = _lib.load()
-        z1, zsup, zsstd, eps = _f32(z1), _f32(zsup), _f32(zsstd), _f32(eps)
-        extra = _f32(extra)
-        B, Ts, N = zsup.shape[:3]
-        D = cl // 2
-        sd = D + (extra.shape[-1] if extra is not None else 0)
-        dev = z1.device
-        params = _gnn_image_cl(_f32(w_img), _f32(v_img), _f32(wt_img), cl)
-        with torch.cuda.device(dev):
-            def out(d):
-                return torch.empty(B, Ts, N, d, dtype=torch.float32, device=dev)
-            z, zdyn, zdstd, mean, std = out(D + 2), out(D), out(D), out(D + 2), out(D + 2)
-            pred = out(cl) if want_pred else None
-            check(lib.stove_dynloop_fwd_cl(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z), ptr(zdyn),
-                                           ptr(zdstd), ptr(mean), ptr(std), ptr(pred), cl, B, Ts, N, sd, int(lim_enc), int(elu),
-                                           *[float(c) for c in consts], stream()), 'stove_dynloop_fwd_cl')
-        ctx.save_for_backward(z1, zsup, zsstd, eps, extra, params, z)
-        ctx.cfg = (cl, int(lim_enc), int(elu), tuple(float(c) for c in consts), sd)
-        ctx.sink = sink
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(zdstd)
-        if pred is None:
-            pred = z.new_zeros(0)
-            ctx.mark_non_differentiable(pred)
-        return z, zdyn, zdstd, mean, std, pred
-
-    @staticmethod
-    def backward(ctx, dz, dzdyn, _dzdstd, dmean, dstd, dpred):
-        lib = _lib.load()
-        z1, zsup, zsstd, eps, extra, params, z = ctx.saved_tensors
-        cl, lim_enc, elu, consts, sd = ctx.cfg
+        width, lim_enc, elu, consts, sd = ctx.cfg
         B, Ts, N = zsup.shape[:3]
         dev = z1.device
 
@@ -838,17 +760,23 @@ class _DynLoopClFn(torch.autograd.Function):
             dz1 = torch.empty_like(z1)
             dzsup, dzsstd = torch.empty_like(zsup), torch.empty_like(zsstd)
             dextra = torch.empty_like(extra) if extra is not None else None
-            g = torch.empty(lib.stove_gnn_grad_floats_cl(cl), dtype=torch.float32, device=dev)
-            ws = _ws(lib.stove_gnn_bwd_ws_bytes_cl(cl, B, N), dev)
-            check(lib.stove_dynloop_bwd_cl(ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z),
-                                           ptr(up(dz)), ptr(up(dzdyn)), ptr(up(dmean)), ptr(up(dstd)), ptr(up(dpred)),
-                                           ptr(dz1), ptr(dzsup), ptr(dzsstd), ptr(dextra), ptr(g), ptr(ws),
-                                           cl, B, Ts, N, sd, lim_enc, elu, *consts, stream()), 'stove_dynloop_bwd_cl')
+            g = torch.empty(width.size('stove_gnn_grad_floats'), dtype=torch.float32, device=dev)
+            ws = _ws(width.loop_bwd_ws_bytes(B, Ts, N), dev)
+            ptrs = (ptr(z1), ptr(zsup), ptr(zsstd), ptr(eps), ptr(extra), ptr(params), ptr(z)) + ((ptr(act),) if width.tuned else ()) \
+                + (ptr(up(dz)), ptr(up(dzdyn)), ptr(up(dmean)), ptr(up(dstd)), ptr(up(dpred)), ptr(dz1), ptr(dzsup), ptr(dzsstd),
+                   ptr(dextra), ptr(g), ptr(ws))
+            if width.tuned and ctx.sink is not None and _settings.OVERLAP:
+                # weight gradients (only the optimiser reads them) on the second stream, under the encoder's backward GEMMs
+                main, side = torch.cuda.current_stream(dev), _side_stream(dev)
+                width.call('stove_dynloop_bwd_overlap', ptrs, B, Ts, N, sd, lim_enc, elu, *consts, main.cuda_stream, side.cuda_stream)
+                run_on_side(dev, lambda: ctx.sink(g), (ws, g, act), after_main=False)
+                join_side_after_backward(dev)
+                return (dz1, dzsup, dzsstd, None, dextra) + (None,) * 9
+            width.call('stove_dynloop_bwd', ptrs, B, Ts, N, sd, lim_enc, elu, *consts, stream())
         if ctx.sink is not None:
             ctx.sink(g)
             return (dz1, dzsup, dzsstd, None, dextra) + (None,) * 9
-        W = gnn_w_floats(cl)
-        return (dz1, dzsup, dzsstd, None, dextra, g[:W], g[W:]) + (None,) * 7
+        return (dz1, dzsup, dzsstd, None, dextra, *width.split(g)) + (None,) * 7
 
 
 def _sunk(t, sink):
@@ -862,52 +790,32 @@ def gnn_step(s_in, image, lim_enc=2, elu=False, sink=None, cl=32):
     """image = (w_img, v_img, wt_img) from Dynamics.param_image(), or (flat image, None, None) + a gradient sink.
     `cl`: the state-code length the image was built for (Dynamics passes config.cl); 16 and 64 run the width-generic kernels
     (csrc/gnn_cl.hip).  An image of another size than that width's is an error."""
-    _check_image_cl(image, cl)
-    if cl != 32:
-        return _GnnStepClFn.apply(_sunk(s_in, sink), image[0], image[1], image[2], cl, lim_enc, elu, sink)
-    return _GnnStepFn.apply(_sunk(s_in, sink), image[0], image[1], image[2], lim_enc, elu, sink)
+    return _GnnStepFn.apply(_sunk(s_in, sink), image[0], image[1], image[2], gnn_width(cl), lim_enc, elu, sink)
 
 
 def dyn_loop(z1, zsup, zsstd, eps, extra, image, lim_enc, elu, consts, want_pred=False, sink=None):
-    cl = 2 * (z1.shape[-1] - 2)                # states are cl/2 + 2 wide
-    if cl != 32:
-        _check_image_cl(image, cl)
-        return _DynLoopClFn.apply(_sunk(z1, sink), zsup, zsstd, eps, extra, image[0], image[1], image[2], cl, lim_enc, elu, consts,
-                                  want_pred, sink)
-    return _DynLoopFn.apply(_sunk(z1, sink), zsup, zsstd, eps, extra, image[0], image[1], image[2], lim_enc, elu, consts,
+    width = gnn_width(2 * (z1.shape[-1] - 2))                # states are cl/2 + 2 wide
+    return _DynLoopFn.apply(_sunk(z1, sink), zsup, zsstd, eps, extra, image[0], image[1], image[2], width, lim_enc, elu, consts,
                             want_pred, sink)
 
 
 @torch.no_grad()
 def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, want_pred=False):
-    """Generative rollout (forward only): z_last (B,N,18), extra (B,A,N,E) or None -> z_pred (B,num,N,18)."""
-    lib = _lib.load()
+    """Generative rollout (forward only): z_last (B,N,cl/2+2), extra (B,A,N,E) or None -> z_pred (B,num,N,cl/2+2)."""
     z_last, extra = _f32(z_last), _f32(extra)
     B, N = z_last.shape[:2]
     A = extra.shape[1] if extra is not None else 1
-    cl = 2 * (z_last.shape[-1] - 2)
-    if cl != 32:
-        _check_image_cl(image, cl)
-        D = cl // 2
-        sd = D + (extra.shape[-1] if extra is not None else 0)
-        dev = z_last.device
-        params = _gnn_image_cl(_f32(image[0]), _f32(image[1]), _f32(image[2]), cl)
-        with torch.cuda.device(dev):
-            z_pred = torch.empty(B, num, N, D + 2, dtype=torch.float32, device=dev)
-            zstd = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if want_std else None
-            pred = torch.empty(B, num, N, cl, dtype=torch.float32, device=dev) if want_pred else None
-            check(lib.stove_rollout_fwd_cl(ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred), cl, B, num, A, N, sd,
-                                           int(lim_enc), int(elu), *[float(c) for c in consts], stream()), 'stove_rollout_fwd_cl')
-        return z_pred, zstd, pred
-    sd = 16 + (extra.shape[-1] if extra is not None else 0)
+    width = gnn_width(2 * (z_last.shape[-1] - 2))
+    D = width.D
+    sd = D + (extra.shape[-1] if extra is not None else 0)
     dev = z_last.device
-    params = _gnn_image(_f32(image[0]), _f32(image[1]), _f32(image[2]))
+    params = width.image(_f32(image[0]), _f32(image[1]), _f32(image[2]))
     with torch.cuda.device(dev):
-        z_pred = torch.empty(B, num, N, 18, dtype=torch.float32, device=dev)
-        zstd = torch.empty(B, num, N, 16, dtype=torch.float32, device=dev) if want_std else None
-        pred = torch.empty(B, num, N, 32, dtype=torch.float32, device=dev) if want_pred else None
-        check(lib.stove_rollout_fwd(ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred), B, num, A, N, sd,
-                                    int(lim_enc), int(elu), *[float(c) for c in consts], stream()), 'stove_rollout_fwd')
+        z_pred = torch.empty(B, num, N, D + 2, dtype=torch.float32, device=dev)
+        zstd = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if want_std else None
+        pred = torch.empty(B, num, N, width.cl, dtype=torch.float32, device=dev) if want_pred else None
+        width.call('stove_rollout_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred)), B, num, A, N, sd,
+                   int(lim_enc), int(elu), *[float(c) for c in consts], stream())
     return z_pred, zstd, pred
 
 

@@ -534,7 +534,11 @@ def test_small_graph_recursion_matches_step_kernels(n_obj, ac, nonlinear):
     run two node rows per wave and two tiles of edge columns).  N = 7, 8: the workgroup-wide MFMA loops of csrc/gnn.hip
     (dyn_loop_fwd_k / dyn_loop_bwd_k / rollout_fwd_k), which no BASELINE configuration reaches since six objects moved to the
     small-graph path -- this test is what keeps them honest.  `ac`: action-conditioned, 23 inputs per node and the reward head."""
-    from stove_amd.video_prediction.stove import Stove
+    recursion_against_step_kernels(n_obj, ac, nonlinear)
+
+
+def recursion_inputs(ac):
+    """-> frames x (3, 6, 3, 32, 32), one-hot actions or None, the configuration entries of `ac`, a repeatable noise_fn"""
     n, T = 3, 6
     g = torch.Generator(device='cpu').manual_seed(11)
     x = (torch.rand(n, T, 3, 32, 32, generator=g) < 0.04).float().to(DEV)
@@ -547,6 +551,12 @@ def test_small_graph_recursion_matches_step_kernels(n_obj, ac, nonlinear):
         if key not in noise:
             noise[key] = torch.randn(*shape, generator=g)
         return noise[key]
+    return x, actions, extra, noise_fn
+
+
+def recursion_against_step_kernels(n_obj, ac, nonlinear):
+    from stove_amd.video_prediction.stove import Stove
+    x, actions, extra, noise_fn = recursion_inputs(ac)
     res = []
     for fused in (True, False):
         st = fill_analytic(Stove(make_cfg(num_obj=n_obj, fused_dynamics=fused, debug_match_objects='greedy', debug_nonlinear=nonlinear, **extra))).to(DEV)
@@ -566,6 +576,35 @@ def test_small_graph_recursion_matches_step_kernels(n_obj, ac, nonlinear):
     for k in g1:
         assert err(g1[k], g2[k]) < 2e-3 or float(g2[k].abs().max()) < 1e-9, k
     assert err(z1, z2) < 1e-4
+
+
+@pytest.mark.parametrize('nonlinear', ['relu', 'leaky_relu'])
+@pytest.mark.parametrize('n_obj', [2, 3, 4, 5, 6, 7])
+def test_recursion_without_saved_activations_and_general_backward(n_obj, nonlinear, monkeypatch):
+    """What test_small_graph_recursion_matches_step_kernels leaves to chance in the choice of the recursion's instantiations, on
+    its inputs.  The forward that saves nothing (torch.no_grad) returns bit for bit what the one that keeps the activations for
+    the backward returns.  At three and six objects, the backward of the action-conditioned model (23 inputs per node, a gradient
+    for `pred`: not the instantiations for the plain training step, which three objects otherwise always run) holds the bars of
+    that test against the step kernels."""
+    from stove_amd import ops
+    from stove_amd.video_prediction.stove import Stove
+    x, actions, extra, noise_fn = recursion_inputs(False)
+    st = fill_analytic(Stove(make_cfg(num_obj=n_obj, fused_dynamics=True, debug_match_objects='greedy', debug_nonlinear=nonlinear, **extra))).to(DEV)
+    st.noise_fn = noise_fn
+    calls, dyn_loop = [], ops.dyn_loop
+    monkeypatch.setattr(ops, 'dyn_loop', lambda *a, **kw: calls.append((a, kw)) or dyn_loop(*a, **kw))
+    st(x, 0, actions)
+    monkeypatch.undo()
+    (a, kw), = calls
+    assert a[0].requires_grad and a[0].shape[-1] == 18 and a[1].shape[0] == 3 and a[1].shape[2] == n_obj
+    saving = dyn_loop(*a, **kw)
+    with torch.no_grad():
+        plain = dyn_loop(*a, **kw)
+    assert saving[0].grad_fn is not None and plain[0].grad_fn is None
+    for name, u, v in zip(('z', 'zdyn', 'zdstd', 'mean', 'std'), saving, plain):
+        assert torch.equal(u, v), name
+    if n_obj in (3, 6):
+        recursion_against_step_kernels(n_obj, True, nonlinear)
 
 
 def test_object_embedding_kernel_against_grid_sample():
