@@ -304,6 +304,15 @@ int stove_rollout_fwd(const float* z_last, const float* extra, const float* para
                       int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std,
                       float lat_std, void* stream);
 
+/* ---- Stove.rollout(sample=True) (stove.py:836-841), all steps in one launch: eps (B,num,N,16) standard-normal draws;
+ * per step z = mean + sd eps with mean the mean rollout's prediction from the DRAWN previous state and sd = zstd; z_pred receives
+ * [scale, z] and z feeds the next step; log_q (B,num,N,16) = log N(z; mean, sd) = -eps^2/2 - log sd - log(2 pi)/2.  eps and log_q are
+ * required (NULL: hipErrorInvalidValue, nothing launched), zstd and pred optional; everything else as stove_rollout_fwd, whose
+ * z_pred this call reproduces bit for bit at eps = 0. */
+int stove_rollout_sample_fwd(const float* z_last, const float* extra, const float* params, const float* eps, float* z_pred,
+                             float* log_q, float* zstd, float* pred, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
+                             float pos_var, float vel_std, float lat_std, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),
@@ -330,6 +339,9 @@ int stove_dynloop_bwd_cl(const float* z1, const float* zsup, const float* zsstd,
 int stove_rollout_fwd_cl(const float* z_last, const float* extra, const float* params, float* z_pred, float* zstd, float* pred,
                          int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std,
                          float lat_std, void* stream);
+int stove_rollout_sample_fwd_cl(const float* z_last, const float* extra, const float* params, const float* eps, float* z_pred,
+                                float* log_q, float* zstd, float* pred, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc,
+                                int elu, float pos_var, float vel_std, float lat_std, void* stream);
 
 /* ---- Stove._3_only_match_objects / _greedy_match_objects / _volatile_match_objects
  * (stove.py:200-329, 432-514, 331-430): the T-serial nearest-neighbour re-ordering of objects.

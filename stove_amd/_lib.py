@@ -82,6 +82,7 @@ def _declare(lib):
         'stove_dynloop_bwd': (I, [P] * 19 + [I] * 6 + [F] * 3 + [P]),
         'stove_dynloop_bwd_overlap': (I, [P] * 19 + [I] * 6 + [F] * 3 + [P, P]),
         'stove_rollout_fwd': (I, [P] * 6 + [I] * 7 + [F] * 3 + [P]),
+        'stove_rollout_sample_fwd': (I, [P] * 8 + [I] * 7 + [F] * 3 + [P]),
         'stove_gnn_param_floats_cl': (S, [I]),
         'stove_gnn_grad_floats_cl': (S, [I]),
         'stove_gnn_bwd_ws_bytes_cl': (S, [I, I, I]),
@@ -90,6 +91,7 @@ def _declare(lib):
         'stove_dynloop_fwd_cl': (I, [P] * 12 + [I] * 7 + [F] * 3 + [P]),
         'stove_dynloop_bwd_cl': (I, [P] * 18 + [I] * 7 + [F] * 3 + [P]),
         'stove_rollout_fwd_cl': (I, [P] * 6 + [I] * 8 + [F] * 3 + [P]),
+        'stove_rollout_sample_fwd_cl': (I, [P] * 8 + [I] * 8 + [F] * 3 + [P]),
         'stove_match_objects': (I, [P, P, P, I, I, I, I, I, P]),
         'stove_profile_enable': (None, [I]),
         'stove_lstm_cell_fwd': (I, [P, P, P, P, P, I, I, I, P]),

@@ -162,6 +162,7 @@ extern "C" {
 // 7: the GNN step, the inference recursion and the rollout at state-code lengths 16 and 64 (stove_gnn_param_floats_cl,
 //    stove_gnn_grad_floats_cl, stove_gnn_bwd_ws_bytes_cl, stove_gnn_fwd_cl, stove_gnn_bwd_cl, stove_dynloop_fwd_cl, stove_dynloop_bwd_cl,
 //    stove_rollout_fwd_cl).
+//    (added since, nothing changed: stove_rollout_sample_fwd, stove_rollout_sample_fwd_cl -- the sampling rollout)
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1036,6 +1037,24 @@ int stove_rollout_fwd(const float* z_last, const float* extra, const float* para
                           z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
 }
 
+int stove_rollout_sample_fwd(const float* z_last, const float* extra, const float* params, const float* eps, float* z_pred,
+                             float* log_q, float* zstd, float* pred, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
+                             float pos_var, float vel_std, float lat_std, void* stream) {
+  STOVE_VALIDATE(rollout_sample_fwd(z_last, extra, params, eps, z_pred, log_q, B, num, A, N, sin_dim));
+  if (B == 0 || num == 0) return 0;
+  LoopConst kc{pos_var, vel_std, lat_std};
+  if (small_graph(N)) {      // the mean rollout's ladder
+    return with_small_graph<false>(N, elu, false, [&](auto nmx, auto e, auto nt) {
+      constexpr int NMX = decltype(nmx)::value;
+      return STOVE_LAUNCH_LDS((rollout_sample_fwd_small_k<NMX, decltype(e)::value, decltype(nt)::value>), dim3(B), dim3(64 * kSmWaves),
+                              SmShape<NMX>::kLdsFloats * sizeof(float), (hipStream_t)stream, z_last, extra, params, eps, z_pred, log_q, zstd,
+                              pred, B, num, A < 1 ? 1 : A, N, sin_dim, lim_enc, elu, kc);
+    });
+  }
+  return STOVE_LAUNCH_LDS(rollout_sample_fwd_k, dim3(stove_gnn_blocks(B, N)), dim3(256), kGnnLdsBytes, (hipStream_t)stream, z_last, extra,
+                          params, eps, z_pred, log_q, zstd, pred, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
+}
+
 // ---------------------------------------------------------------- GNN dynamics core at state-code lengths 16 / 64 (gnn_cl.hip)
 size_t stove_gnn_param_floats_cl(int cl) { return cl == 16 ? GC<16>::kParams : (cl == 64 ? GC<64>::kParams : 0); }
 size_t stove_gnn_grad_floats_cl(int cl) { return cl == 16 ? GC<16>::kGrads : (cl == 64 ? GC<64>::kGrads : 0); }
@@ -1123,6 +1142,20 @@ int stove_rollout_fwd_cl(const float* z_last, const float* extra, const float* p
     return STOVE_LAUNCH_LDS(gnn_cl_rollout_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
                             z_last, extra, params, z_pred, zstd, pred, B, num, A < 1 ? 1 : A, N, cl_group_for<CL>(B, N), sin_dim, lim_enc, elu,
                             kc);
+  });
+}
+
+int stove_rollout_sample_fwd_cl(const float* z_last, const float* extra, const float* params, const float* eps, float* z_pred,
+                                float* log_q, float* zstd, float* pred, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc,
+                                int elu, float pos_var, float vel_std, float lat_std, void* stream) {
+  STOVE_VALIDATE(rollout_sample_fwd(z_last, extra, params, eps, z_pred, log_q, B, num, A, N, sin_dim, stove_validate::gnn_limits_cl(cl)));
+  if (B == 0 || num == 0) return 0;
+  LoopConst kc{pos_var, vel_std, lat_std};
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    return STOVE_LAUNCH_LDS(gnn_cl_rollout_sample_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float),
+                            (hipStream_t)stream, z_last, extra, params, eps, z_pred, log_q, zstd, pred, B, num, A < 1 ? 1 : A, N,
+                            cl_group_for<CL>(B, N), sin_dim, lim_enc, elu, kc);
   });
 }
 

@@ -1268,4 +1268,75 @@ __global__ __launch_bounds__(256) void rollout_fwd_k(const float* __restrict__ z
   }
 }
 
+// =================================================================================================
+// sampling rollout (stove.py:836-841), forward only: rollout_fwd_k with a draw per step
+//   eps (B,num,N,16) standard normals; per step z = mean + sd eps with `mean` what rollout_fwd_k predicts from the DRAWN previous
+//   state and sd its zstd; z_pred receives [scale, z], z goes back into the state row Z; log_q (B,num,N,16) = log N(z; mean, sd)
+// A kernel of its own, not a flag of rollout_fwd_k: the mean rollout keeps its code to the instruction (sharing one body through a
+// device function changed how the compiler addresses LDS in the mean kernel too).  The thread that owns (row, d) reads RES, SIN
+// and eps of that element only, so the step has the mean rollout's barriers and no other.
+// =================================================================================================
+// log N(z; mean, sd) of z = mean + sd eps, written in eps: -eps^2 / 2 - log sd - log(2 pi) / 2.  The form in z, -((z - mean) / sd)^2 / 2,
+// is the same algebra, but float32 keeps z to 2^-24 |z|, so (z - mean) / sd is 6e-8 |z| / sd away from eps -- all of eps at the
+// sd = 1e-7 of a saturated model -- while the float64 oracle's quotient returns eps to 1e-9 there: the eps form is the one that lands
+// on the oracle.  logf, not __logf: at eps = 0 log sd is all of log q.
+constexpr float kHalfLog2Pi = 0.91893853320467274178f;
+__device__ __forceinline__ float sample_log_q(float ep, float sd) { return -0.5f * ep * ep - logf(sd) - kHalfLog2Pi; }
+
+__global__ __launch_bounds__(256) void rollout_sample_fwd_k(const float* __restrict__ z_last, const float* __restrict__ extra,
+                                                            const float* __restrict__ P, const float* __restrict__ eps,
+                                                            float* __restrict__ z_pred, float* __restrict__ log_q,
+                                                            float* __restrict__ zstd, float* __restrict__ pred,
+                                                            int B, int num, int A, int N, int G, int sin_dim, int lim_enc, int elu, LoopConst kc) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const GnnLds L = carve(lds);
+  const int b0 = blockIdx.x * G;
+  const GnnShape sh = make_shape(N, G, b0, B, sin_dim, lim_enc, elu);
+  const int E = sin_dim - 16;
+  lds_zero(lds, kGnnLdsFloats);
+  WG_SYNC();
+  gnn_setup(L, sh, P + 2 * W_END);
+  WG_SYNC();
+  float* Z = L.X;
+  for (int i = threadIdx.x; i < sh.NR * 18; i += blockDim.x) Z[(i / 18) * 20 + i % 18] = z_last[(size_t)b0 * N * 18 + i];
+  const FwdW fw = gnn_fwdw_load(P);
+  WG_SYNC();
+  for (int t = 0; t < num; ++t) {
+    for (int i = threadIdx.x; i < sh.NR * sin_dim; i += blockDim.x) {
+      const int r = i / sin_dim, c = i % sin_dim;
+      float v;
+      if (c < 16) v = Z[r * 20 + 2 + c];
+      else v = extra[(((size_t)(b0 + r / N) * A + (t % A)) * N + r % N) * E + (c - 16)];
+      L.SIN[r * LDN + c] = v;
+    }
+    WG_SYNC();
+    gnn_forward(L, sh, P, fw);
+    for (int idx = threadIdx.x; idx < sh.NR * 18; idx += blockDim.x) {
+      const int r = idx / 18, q = idx % 18;
+      const size_t o = ((size_t)(b0 + r / N) * num + t) * N + r % N;
+      float v;
+      if (q < 2) {
+        v = Z[r * 20 + q];                                  // scale stays constant
+      } else {
+        const int d = q - 2;
+        const float mean = 2.0f * sigmoidf_(L.RES[r * LDN + d]) - 1.0f + (d < 2 ? L.SIN[r * LDN + d] : 0.0f);
+        const float sd = std_scale(d, kc) * sigmoidf_(L.RES[r * LDN + 16 + d]);
+        const float ep = eps[o * 16 + d];
+        v = fmaf(sd, ep, mean);
+        log_q[o * 16 + d] = sample_log_q(ep, sd);
+        if (zstd != nullptr) zstd[o * 16 + d] = sd;
+      }
+      z_pred[o * 18 + q] = v;
+      Z[r * 20 + q] = v;                                  // the drawn state is the next step's input
+    }
+    if (pred != nullptr) {
+      for (int i = threadIdx.x; i < sh.NR * 32; i += blockDim.x) {
+        const int r = i >> 5, c = i & 31;
+        pred[(((size_t)(b0 + r / N) * num + t) * N + r % N) * 32 + c] = L.PRED[r * LDN + c];
+      }
+    }
+    WG_SYNC();
+  }
+}
+
 }  // namespace stove

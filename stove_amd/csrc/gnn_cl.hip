@@ -887,6 +887,67 @@ __global__ __launch_bounds__(256) void gnn_cl_rollout_k(const float* __restrict_
   }
 }
 
+// =================================================================================================
+// sampling rollout, forward only: gnn_cl_rollout_k with a draw per step, as rollout_sample_fwd_k (gnn.hip) is to rollout_fwd_k --
+//   eps, log_q (B,num,N,D); z = mean + sd eps goes to z_pred and back into Z; no barrier the mean rollout does not have
+// =================================================================================================
+template <int CL>
+__global__ __launch_bounds__(256) void gnn_cl_rollout_sample_k(const float* __restrict__ z_last, const float* __restrict__ extra,
+                                                               const float* __restrict__ P, const float* __restrict__ eps,
+                                                               float* __restrict__ z_pred, float* __restrict__ log_q,
+                                                               float* __restrict__ zstd, float* __restrict__ pred,
+                                                               int B, int num, int A, int N, int G, int sin_dim, int lim_enc, int elu, LoopConst kc) {
+  using K = GC<CL>;
+  constexpr int D = K::D, ZW = K::ZW, LDN = K::LDN, LDZ = K::LDZ;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const ClLds<CL> L = cl_carve<CL>(lds);
+  const int b0 = blockIdx.x * G;
+  const GnnShape sh = make_shape(N, G, b0, B, sin_dim, lim_enc, elu);
+  const int E = sin_dim - D;
+  lds_zero(lds, K::kLdsFloats);
+  WG_SYNC();
+  cl_setup<CL>(L, sh, P + 2 * K::W_END);
+  float* Z = L.X;
+  for (int i = threadIdx.x; i < sh.NR * ZW; i += blockDim.x) Z[(i / ZW) * LDZ + i % ZW] = z_last[(size_t)b0 * N * ZW + i];
+  WG_SYNC();
+  for (int t = 0; t < num; ++t) {
+    for (int i = threadIdx.x; i < sh.NR * sin_dim; i += blockDim.x) {
+      const int r = i / sin_dim, c = i % sin_dim;
+      float v;
+      if (c < D) v = Z[r * LDZ + 2 + c];
+      else v = extra[(((size_t)(b0 + r / N) * A + (t % A)) * N + r % N) * E + (c - D)];
+      L.SIN[r * LDN + c] = v;
+    }
+    WG_SYNC();
+    cl_forward<CL>(L, sh, P);
+    for (int idx = threadIdx.x; idx < sh.NR * ZW; idx += blockDim.x) {
+      const int r = idx / ZW, q = idx % ZW;
+      const size_t o = ((size_t)(b0 + r / N) * num + t) * N + r % N;
+      float v;
+      if (q < 2) {
+        v = Z[r * LDZ + q];                                  // scale stays constant
+      } else {
+        const int d = q - 2;
+        const float mean = 2.0f * sigmoidf_(L.RES[r * LDN + d]) - 1.0f + (d < 2 ? L.SIN[r * LDN + d] : 0.0f);
+        const float sd = std_scale(d, kc) * sigmoidf_(L.RES[r * LDN + D + d]);
+        const float ep = eps[o * D + d];
+        v = fmaf(sd, ep, mean);
+        log_q[o * D + d] = sample_log_q(ep, sd);
+        if (zstd != nullptr) zstd[o * D + d] = sd;
+      }
+      z_pred[o * ZW + q] = v;
+      Z[r * LDZ + q] = v;                                  // the drawn state is the next step's input
+    }
+    if (pred != nullptr) {
+      for (int i = threadIdx.x; i < sh.NR * CL; i += blockDim.x) {
+        const int r = i / CL, c = i % CL;
+        pred[(((size_t)(b0 + r / N) * num + t) * N + r % N) * CL + c] = L.PRED[r * LDN + c];
+      }
+    }
+    WG_SYNC();
+  }
+}
+
 // ---- host side of the entry points in capi.hip
 // f(std::integral_constant<int, CL>) for a supported width
 template <class F>

@@ -943,4 +943,73 @@ __global__ __launch_bounds__(64 * kSmWaves) void rollout_fwd_small_k(const float
   }
 }
 
+// =================================================================================================
+// sampling rollout, same contract as rollout_sample_fwd_k (gnn.hip) with G = 1: rollout_fwd_small_k with a draw per step.
+// Lane d < 16 of a node row draws z[d] = mean + sd eps, writes log_q and keeps z[d] as its s_in of the next step: the state never
+// leaves the lane, so the draw adds no barrier and no LDS traffic.  Every lane of a row's wave loads its eps, not only the half that
+// stores: with one wave per row both halves carry s_in.
+// =================================================================================================
+template <int NMX, bool ELU, int NT>
+__global__ __launch_bounds__(64 * kSmWaves) void rollout_sample_fwd_small_k(const float* __restrict__ z_last, const float* __restrict__ extra,
+                                                                  const float* __restrict__ P, const float* __restrict__ eps,
+                                                                  float* __restrict__ z_pred, float* __restrict__ log_q,
+                                                                  float* __restrict__ zstd, float* __restrict__ pred,
+                                                                  int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, LoopConst kc) {
+  constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET;
+  static_assert(NT <= NMX, "object count beyond what the kernel is built for");
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const SmLds L = sm_carve<NMX>(lds);
+  const int b = blockIdx.x;
+  const int wv = wave_id(), lane = lane_id(), l = lane & 31;
+  elu = ELU ? 1 : 0;      // compile-time activation: with a run-time flag every phi carried the ocml expm1f path (code, registers, branches)
+  if (NT > 0) N = NT;       // loops over the objects unroll, their LDS reads go out together
+  SmCfg cf{N, sin_dim, lim_enc, elu};
+  cf.stamps = nullptr;
+  const int E = sin_dim - 16;
+  SmEdgeLane el[ET];
+#pragma unroll
+  for (int t = 0; t < ET; ++t) el[t] = sm_edge_lane(N, 0, t);
+  sm_setup(L, P);
+  float sinv = 0.0f, scale = 0.0f;
+  const int r = RP == 2 ? wv + 4 * (lane >> 5) : wv;
+  const bool row = r < N;
+  const bool own = RP == 2 ? row : (lane < 32 && row);
+  if (row) {
+    if (l < 16) sinv = z_last[((size_t)b * N + r) * 18 + 2 + l];
+    else if (l < sin_dim) sinv = extra[(((size_t)b * A + 0) * N + r) * E + (l - 16)];
+    if (l >= 16 && l < 18) scale = z_last[((size_t)b * N + r) * 18 + (l - 16)];       // sx, sy stay constant
+  }
+  WG_SYNC();
+  SmChainW cw;
+  sm_chain_wbuild(L, cw);
+  for (int t = 0; t < num; ++t) {
+    const size_t o = ((size_t)b * num + t) * N + r;
+    float xnext = 0.0f;
+    if (row && l >= 16 && l < sin_dim && t + 1 < num) xnext = extra[(((size_t)b * A + ((t + 1) % A)) * N + r) * E + (l - 16)];
+    const float ep = (row && l < 16) ? eps[o * 16 + l] : 0.0f;       // ahead of the step, off its serial chain
+    SmAct a{};
+    float res = 0.0f, prd = 0.0f;
+    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw);
+    if (wv < N) {
+      const float res_s = from_xor16(res);
+      float zv;
+      if (l < 16) {
+        const float mean = 2.0f * sigmoidf_(res) - 1.0f + (l < 2 ? sinv : 0.0f);
+        const float sd = std_scale(l, kc) * sigmoidf_(res_s);
+        zv = fmaf(sd, ep, mean);
+        if (own) {
+          z_pred[o * 18 + 2 + l] = zv;
+          log_q[o * 16 + l] = sample_log_q(ep, sd);
+          if (zstd != nullptr) zstd[o * 16 + l] = sd;
+        }
+      } else {
+        zv = xnext;
+        if (l < 18 && own) z_pred[o * 18 + (l - 16)] = scale;
+      }
+      if (pred != nullptr && own) pred[o * 32 + l] = prd;
+      sinv = zv;
+    }
+  }
+}
+
 }  // namespace stove

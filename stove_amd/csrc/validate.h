@@ -174,6 +174,13 @@ inline int rollout_fwd(const float* z_last, const float* extra, const float* par
   if (sin_dim > k.lo && (extra == nullptr || A < 1)) return kStoveInvalidValue;
   return 0;
 }
+// the sampling rollout: the mean rollout's contract plus the draws and their log-density, both required
+inline int rollout_sample_fwd(const float* z_last, const float* extra, const float* params, const float* eps, const float* z_pred,
+                              const float* log_q, int B, int num, int A, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (const int rc = rollout_fwd(z_last, extra, params, z_pred, B, num, A, N, sin_dim, k)) return rc;
+  if (B == 0 || num == 0) return 0;
+  return null_any(eps, log_q) ? kStoveInvalidValue : 0;
+}
 
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,

@@ -800,8 +800,13 @@ def dyn_loop(z1, zsup, zsstd, eps, extra, image, lim_enc, elu, consts, want_pred
 
 
 @torch.no_grad()
-def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, want_pred=False):
-    """Generative rollout (forward only): z_last (B,N,cl/2+2), extra (B,A,N,E) or None -> z_pred (B,num,N,cl/2+2)."""
+def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, want_pred=False, eps=None, want_logq=False):
+    """Generative rollout (forward only): z_last (B,N,cl/2+2), extra (B,A,N,E) or None -> z_pred (B,num,N,cl/2+2), zstd, pred.
+    With eps (B,num,N,cl/2) standard normals, or a NoiseSource to draw them from: the sampling branch in one launch (stove_rollout_sample_fwd) -- every step draws
+    z = mean + sd eps, which feeds the next one -> (z_pred, zstd, pred, log_q) with log_q (B,num,N,cl/2) the draws' log-density.
+    `want_logq` asks for the log-density of a sampling call; without eps there is nothing it could be of."""
+    if want_logq and eps is None:
+        raise ValueError('ops.rollout: want_logq needs eps (the mean rollout draws nothing)')
     z_last, extra = _f32(z_last), _f32(extra)
     B, N = z_last.shape[:2]
     A = extra.shape[1] if extra is not None else 1
@@ -810,13 +815,24 @@ def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, wan
     sd = D + (extra.shape[-1] if extra is not None else 0)
     dev = z_last.device
     params = width.image(_f32(image[0]), _f32(image[1]), _f32(image[2]))
+    if isinstance(eps, NoiseSource):                 # one draw for all the steps, on the stream the rollout follows on
+        eps = eps.normal(B * num * N * D).view(B, num, N, D)
+    if eps is not None:
+        eps = _f32(eps)
+        if tuple(eps.shape) != (B, num, N, D):
+            raise ValueError('ops.rollout: eps is %s, the rollout needs %s' % (tuple(eps.shape), (B, num, N, D)))
     with torch.cuda.device(dev):
         z_pred = torch.empty(B, num, N, D + 2, dtype=torch.float32, device=dev)
         zstd = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if want_std else None
         pred = torch.empty(B, num, N, width.cl, dtype=torch.float32, device=dev) if want_pred else None
-        width.call('stove_rollout_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred)), B, num, A, N, sd,
-                   int(lim_enc), int(elu), *[float(c) for c in consts], stream())
-    return z_pred, zstd, pred
+        tail = (B, num, A, N, sd, int(lim_enc), int(elu), *[float(c) for c in consts], stream())
+        if eps is None:
+            width.call('stove_rollout_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred)), *tail)
+            return z_pred, zstd, pred
+        log_q = torch.empty(B, num, N, D, dtype=torch.float32, device=dev)
+        width.call('stove_rollout_sample_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(eps), ptr(z_pred), ptr(log_q), ptr(zstd),
+                                                ptr(pred)), *tail)
+    return z_pred, zstd, pred, log_q
 
 
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}

@@ -72,12 +72,17 @@ class Stove(nn.Module):
             return self.noise_fn(kind, shape).to(device=like.device, dtype=like.dtype)
         return torch.randn(shape, device=like.device, dtype=like.dtype)
 
-    def _draw_ahead(self, numel, dev):
-        """All of a step's standard-normal draws from the library's generator, on the parameter stream (ops 'pre'), behind nothing:
-        -> (tensor, event to wait for before reading it)."""
+    def _noise_src(self, dev):
+        """The library's generator on `dev` (ops.NoiseSource, shadowing torch's): one per model and device."""
         src = getattr(self, '_noise_source', None)
         if src is None or src.device != dev:
             src = self._noise_source = ops.NoiseSource(dev)
+        return src
+
+    def _draw_ahead(self, numel, dev):
+        """All of a step's standard-normal draws from the library's generator, on the parameter stream (ops 'pre'), behind nothing:
+        -> (tensor, event to wait for before reading it)."""
+        src = self._noise_src(dev)
         main, side = torch.cuda.current_stream(dev), ops._side_stream(dev, 'pre')
         if not _settings.OVERLAP:
             return src.normal(numel), None
@@ -339,13 +344,20 @@ class Stove(nn.Module):
     # ------------------------------------------------------------------ generative rollout
     def rollout(self, z_last, num=None, sample=False, return_std=False, actions=None, appearance=None):
         """Roll the dynamics forward from z_last (n, o, cl//2+2) with [sx, sy, ...]; scales stay fixed.
-        -> z_pred (n, num, o, cl//2+2), rewards   (plus stds / log-probs for return_std / sample)."""
+        -> z_pred (n, num, o, cl//2+2), rewards   (plus stds for return_std).
+        sample=True: every step draws its state from N(mean, std) and the drawn state feeds the next one
+        -> z_pred, log_q (n, num, o, cl//2), rewards -- also with return_std (reference stove.py:855-856).
+        With autograd off the whole sampling rollout is one launch (ops.rollout with eps): the draws come from noise_fn, called
+        once per step in order with ('rollout', (n, o, cl//2)), or else as ONE draw of n num o cl//2 normals from the library's
+        generator.  With autograd on it is a host loop of single differentiable steps (Dynamics.forward) -- the fused kernels are
+        forward only, and gradients through sampled futures are what that loop is kept for."""
         c = self.c
         cl = c.cl
         if num is None:
             num = c.num_rollout
         n, o = z_last.shape[:2]
-        if not sample:
+        fused_sample = sample and not torch.is_grad_enabled()
+        if not sample or fused_sample:
             extra = []
             if actions is not None:
                 emb = self.dyn.embed_actions(actions)
@@ -354,6 +366,16 @@ class Stove(nn.Module):
                 a_len = actions.shape[1] if actions is not None else 1
                 extra.append(appearance.unsqueeze(1).expand(-1, a_len, -1, -1))
             extra = torch.cat(extra, -1).contiguous() if extra else None
+            if fused_sample:
+                if self.noise_fn is not None:
+                    eps = torch.stack([self._noise('rollout', (n, o, cl // 2), z_last) for _ in range(num)], 1)
+                else:
+                    eps = self._noise_src(z_last.device)
+                z_full, _, pred, log_qs = ops.rollout(z_last, extra, self.dyn.kernel_params(0)[0], num, 2, self.dyn.use_elu,
+                                                      self.dyn.loop_consts(), want_pred=bool(c.action_conditioned), eps=eps,
+                                                      want_logq=True)
+                rewards = self.dyn.reward_from_pred(pred) if c.action_conditioned else torch.zeros(num)
+                return z_full, log_qs, rewards
             z_full, z_stds, pred = ops.rollout(z_last, extra, self.dyn.kernel_params(0)[0], num, 2, self.dyn.use_elu,
                                               self.dyn.loop_consts(), want_std=return_std,
                                               want_pred=bool(c.action_conditioned))
@@ -362,7 +384,7 @@ class Stove(nn.Module):
                 return z_full, z_stds.detach(), rewards
             return z_full, rewards
 
-        # sampling rollout: the sampled state feeds back, so this stays a host loop of single steps
+        # sampling rollout under autograd: the sampled state feeds back through differentiable single steps
         scale = z_last[..., :2]
         z, log_qs, rew = [z_last], [], []
         a_len = actions.shape[1] if actions is not None else 1
