@@ -313,6 +313,28 @@ int stove_rollout_sample_fwd(const float* z_last, const float* extra, const floa
                              float* log_q, float* zstd, float* pred, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
                              float pos_var, float vel_std, float lat_std, void* stream);
 
+/* ---- One expansion of M search trees on the learned model (reference mcts/mcts_stove.py:95-137, 186-196; csrc/plan.hip), cl = 32,
+ * action-conditioned.  z_pool (M, cap, N, 18): the trees' node states, resident on the device.  Per tree m: leaf[m] the pool slot of
+ * the selected leaf, child[m] the first of A consecutive slots that receive its children, len_s[m] the reference's key length of the
+ * leaf (the root counts 1; 1 <= len_s <= D).  app (M, N, app_dim) per-tree appearance (NULL with app_dim = 0); acts (M A, L) action
+ * indices in [0, A) of the random rollout; emb_w (4 N, A), emb_b (4 N): the action-embedding nn.Linear; gnn_params: the image
+ * stove_rollout_fwd takes; rh_params: the reward head's stove_reward_head_param_floats() floats.
+ * Row (m, a) runs the mean rollout 1 + L steps from z_pool[m, leaf[m]]: action a, then acts[m A + a, k] at step 1 + k; a step's extra
+ * inputs are column `action` of emb_w plus emb_b, viewed (N, 4), followed by the tree's appearance.  The state after step 0 goes to
+ * z_pool[m, child[m] + a] (bit for bit stove_rollout_fwd's); with r0, rk the reward head on steps 0 and 1 + k,
+ *   q[m,a] = (r0 - 1) gamma^len_s + (sum_{k < min(2 D - len_s + 1, L)} (rk - 1)) (sum_{j = len_s}^{D - 1} gamma^j)
+ * in a fixed summation order.  Outputs q (M, A), r_first (M, A), r_roll (M, A, L); the last two may be NULL.
+ * Three launches on `stream`, no host synchronisation (the call can be captured).  ws: stove_plan_expand_ws_bytes() bytes (0 for
+ * dimensions the call rejects).  Host-checkable arguments (NULL pointers, M, A, L, N, D < 1, N > 8, 20 + app_dim > 32, A > 64,
+ * cap < 1 + A): hipErrorInvalidValue, nothing launched.  A tree with leaf, child .. child + A - 1, len_s or any of its action indices
+ * out of range reads and writes nothing out of bounds: its q / r_first / r_roll rows are NaN and the pool is not written for it. */
+size_t stove_plan_expand_ws_bytes(int M, int A, int L, int N, int app_dim);
+int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app,
+                      const int* acts, const float* emb_w, const float* emb_b, const float* gnn_params,
+                      const float* rh_params, float* q, float* r_first, float* r_roll, void* ws,
+                      int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                      float pos_var, float vel_std, float lat_std, float gamma, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

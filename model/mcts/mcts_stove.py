@@ -1,0 +1,2 @@
+from stove_amd.mcts.mcts_stove import *  # noqa: F401,F403
+from stove_amd.mcts.mcts_stove import MCTS, BatchedMCTSHandler, run_mcts_model  # noqa: F401

@@ -35,6 +35,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "gemm_bf16.hip"
 #include "head_fused.hip"
 #include "reward_head.hip"
+#include "plan.hip"
 
 namespace stove {
 
@@ -162,7 +163,8 @@ extern "C" {
 // 7: the GNN step, the inference recursion and the rollout at state-code lengths 16 and 64 (stove_gnn_param_floats_cl,
 //    stove_gnn_grad_floats_cl, stove_gnn_bwd_ws_bytes_cl, stove_gnn_fwd_cl, stove_gnn_bwd_cl, stove_dynloop_fwd_cl, stove_dynloop_bwd_cl,
 //    stove_rollout_fwd_cl).
-//    (added since, nothing changed: stove_rollout_sample_fwd, stove_rollout_sample_fwd_cl -- the sampling rollout)
+//    (added since, nothing changed: stove_rollout_sample_fwd, stove_rollout_sample_fwd_cl -- the sampling rollout;
+//     stove_plan_expand_ws_bytes, stove_plan_expand -- one expansion of a batch of search trees)
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1338,6 +1340,52 @@ int stove_small_linear(const float* x, const float* W, const float* b, float* y,
   const size_t total = (size_t)rows * out_dim;
   if ((total + 255) / 256 > 0x7fffffffULL) return (int)hipErrorInvalidValue;
   STOVE_LAUNCH(small_linear_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, W, b, y, rows, in_dim, out_dim, w_transposed);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- planning: one expansion of M search trees (plan.hip)
+namespace {
+struct PlanWs {
+  size_t z_in, extra, z_pred, pred, ok, bytes;          // byte offsets
+  PlanWs(int M, int A, int L, int N, int app_dim) {
+    const size_t rows = (size_t)M * A, steps = 1 + (size_t)L;
+    z_in = 0;
+    extra = z_in + align64(rows * N * 18 * sizeof(float));
+    z_pred = extra + align64(rows * steps * N * (4 + app_dim) * sizeof(float));
+    pred = z_pred + align64(rows * steps * N * 18 * sizeof(float));
+    ok = pred + align64(rows * steps * N * 32 * sizeof(float));
+    bytes = ok + align64((size_t)M * sizeof(int));
+  }
+};
+}  // namespace
+
+size_t stove_plan_expand_ws_bytes(int M, int A, int L, int N, int app_dim) {
+  return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanWs(M, A, L, N, app_dim).bytes;
+}
+
+int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
+                      const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, float* q, float* r_first,
+                      float* r_roll, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu, float pos_var,
+                      float vel_std, float lat_std, float gamma, void* stream) {
+  STOVE_VALIDATE(plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, ws, M, cap, A, L, D, N, app_dim));
+  hipStream_t st = (hipStream_t)stream;
+  const PlanWs w(M, A, L, N, app_dim);
+  char* base = (char*)ws;
+  float* z_in = (float*)(base + w.z_in);
+  float* extra = (float*)(base + w.extra);
+  float* z_pred = (float*)(base + w.z_pred);
+  float* pred = (float*)(base + w.pred);
+  int* ok = (int*)(base + w.ok);
+  const int rows = M * A;
+  STOVE_LAUNCH(plan_prep_k, dim3(M), dim3(kPlanPrepThreads), 0, st, (const float*)z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, z_in, extra,
+               ok, cap, A, L, D, N, app_dim);
+  STOVE_LAUNCH_CHECK();
+  const int rc = stove_rollout_fwd(z_in, extra, gnn_params, z_pred, nullptr, pred, rows, 1 + L, 1 + L, N, 20 + app_dim, lim_enc, elu, pos_var,
+                                   vel_std, lat_std, stream);
+  if (rc) return rc;
+  STOVE_LAUNCH(plan_finish_k, dim3(reward_head_blocks(rows)), dim3(64 * kRhWaves), 0, st, (const float*)pred, (const float*)z_pred, rh_params,
+               (const int*)ok, child, len_s, z_pool, q, r_first, r_roll, rows, cap, A, L, D, N, gamma);
   STOVE_LAUNCH_CHECK();
   return 0;
 }

@@ -182,6 +182,22 @@ inline int rollout_sample_fwd(const float* z_last, const float* extra, const flo
   return null_any(eps, log_q) ? kStoveInvalidValue : 0;
 }
 
+// ---- stove_plan_expand: one expansion of M search trees (csrc/plan.hip).  Everything the host can see; the indices themselves
+// (leaf, child, len_s, acts) are device memory and are checked by the kernels.  The rollout behind it is the cl = 32 one.
+constexpr int kPlanMaxActions = 64;
+inline bool plan_dims_bad(int M, int A, int L, int N, int app_dim) {
+  if (M < 1 || A < 1 || L < 1 || A > kPlanMaxActions || app_dim < 0 || kGnn32.bad(1, N, 20 + app_dim)) return true;
+  return (long long)M * A * (1 + (long long)L) > 0x7fffffffLL / (8 * 32);        // rows x steps x objects x 32 stays an int
+}
+inline int plan_expand(const float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
+                       const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, const float* q,
+                       const void* ws, int M, int cap, int A, int L, int D, int N, int app_dim) {
+  if (plan_dims_bad(M, A, L, N, app_dim) || D < 1 || cap < 1 + A) return kStoveInvalidValue;
+  if (null_any(z_pool, emb_w, emb_b, gnn_params, rh_params, q) || null_any(leaf, child, len_s, acts) || ws == nullptr) return kStoveInvalidValue;
+  if (app_dim > 0 && app == nullptr) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

@@ -835,6 +835,44 @@ def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, wan
     return z_pred, zstd, pred, log_q
 
 
+def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, depth, lim_enc, elu, consts, gamma=0.95,
+                want_rewards=False):
+    """One expansion of M search trees (stove_plan_expand, csrc/plan.hip; forward only).  z_pool (M, cap, N, 18) float32 is updated
+    in place: row (m, a) rolls the mean model 1 + L steps from z_pool[m, leaf[m]] -- action a, then acts[m A + a, :] -- and the state
+    after the first step lands in z_pool[m, child[m] + a].  leaf, child, len_s (M,) and acts (M A, L) are int32 device tensors; app
+    (M, N, app_dim) or None; emb_w (4 N, A), emb_b (4 N) the action embedding; gnn_params the cl = 32 image (gnn_width(32).image(...));
+    rh_params the reward head's 2785 floats; `depth` the search's maximal rollout depth D.
+    -> q (M, A) [, r_first (M, A), r_roll (M, A, L) with want_rewards]: the reference's backpropagate value of every child."""
+    tensors = (z_pool, app, emb_w, emb_b, gnn_params, rh_params)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError('ops.plan_expand is forward only: call it under torch.no_grad() or with detached inputs')
+    lib = _lib.load()
+    z_pool, app, emb_w, emb_b, gnn_params, rh_params = [_f32(t) for t in tensors]
+    for name, t in (('leaf', leaf), ('child', child), ('len_s', len_s), ('acts', acts)):
+        if t.dtype != torch.int32 or not t.is_cuda:
+            raise RuntimeError('ops.plan_expand: %s must be an int32 tensor on the GPU' % name)
+    M, cap, N = z_pool.shape[:3]
+    A = emb_w.shape[1]
+    L = acts.shape[-1]
+    app_dim = app.shape[-1] if app is not None else 0
+    if z_pool.data_ptr() != tensors[0].data_ptr():
+        raise RuntimeError('ops.plan_expand writes the child states into z_pool: it must be contiguous')
+    if (z_pool.shape[3] != 18 or tuple(emb_w.shape) != (4 * N, A) or emb_b.numel() != 4 * N or acts.numel() != M * A * L
+            or leaf.numel() != M or child.numel() != M or len_s.numel() != M or (app is not None and tuple(app.shape) != (M, N, app_dim))
+            or gnn_params.numel() != lib.stove_gnn_param_floats() or rh_params.numel() != lib.stove_reward_head_param_floats()):
+        raise ValueError('ops.plan_expand: argument shapes do not fit M = %d trees, N = %d objects, A = %d actions, L = %d' % (M, N, A, L))
+    dev = z_pool.device
+    with torch.cuda.device(dev):
+        q = torch.empty(M, A, dtype=torch.float32, device=dev)
+        r_first = torch.empty(M, A, dtype=torch.float32, device=dev) if want_rewards else None
+        r_roll = torch.empty(M, A, L, dtype=torch.float32, device=dev) if want_rewards else None
+        ws = _ws(lib.stove_plan_expand_ws_bytes(M, A, L, N, app_dim), dev)
+        check(lib.stove_plan_expand(ptr(z_pool), ptr(leaf), ptr(child), ptr(len_s), ptr(app), ptr(acts), ptr(emb_w), ptr(emb_b),
+                                    ptr(gnn_params), ptr(rh_params), ptr(q), ptr(r_first), ptr(r_roll), ptr(ws), M, cap, A, L, int(depth), N,
+                                    app_dim, int(lim_enc), int(elu), *[float(c) for c in consts], float(gamma), stream()), 'stove_plan_expand')
+    return (q, r_first, r_roll) if want_rewards else q
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 
