@@ -612,6 +612,51 @@ def object_embedding(c, z, x_color):
     return pat.mean((-1, -2)).view(*z.shape[:-1], 3)
 
 
+def recursion(c, params, z_init, zs_full, zs_std_full, eps_steps, actions=None, app=None, lim_enc=2):
+    """The inference recursion of Stove.stove_forward on its own, stove.py:687-729: for every step dynamics -> constrain_z_dyn ->
+    full_state (the fusion with SuPAIR's estimate, stove.py:103-170) -> draw -> log q, the drawn state feeding the next step.
+      z_init (B,N,cl/2+2)            the state at skip - 1, [sx, sy, x, y, vx, vy, latents]
+      zs_full, zs_std_full (B,Ts,N,6) SuPAIR means / stds of the Ts frames skip .. T-1
+      eps_steps                      Ts standard-normal draws (B,N,>= cl/2+2), a list or a tensor (Ts, ...)
+      actions (B,Ts,A), app (B,Ts,N,E)  what step k of the Ts feeds the core next to the state (frame skip-1+k's), or None
+    -> dict: z, mean, std (B,Ts,N,cl/2+2; six wide with debug_no_latents but for z), z_dyn, z_dyn_std (B,Ts,N,cl/2), log_q per
+    element, dynamic_pred (B,Ts,N,cl) and `rewards`, the list of the Ts per-step rewards as dynamics_forward returns them."""
+    cl = c.cl
+    z_prev = z_init
+    z_l, zdyn_l, zdyn_std_l, logq_l, mean_l, zstd_l, pred_l, rewards = [], [], [], [], [], [], [], []
+    for k in range(zs_full.shape[1]):
+        act = actions[:, k] if actions is not None else None
+        ap = app[:, k] if app is not None else None
+        out, rew, pred = dynamics_forward(c, params, z_prev[..., 2:], act, ap, lim_enc=lim_enc, with_pred=True)
+        rewards.append(rew)
+        m, sd = constrain_z_dyn(c, out[..., :cl // 2], out[..., cl // 2:])
+        zdyn = torch.cat([z_prev[..., 2:4] + m[..., :2], m[..., 2:]], -1)
+        # full_state, stove.py:103-170 (default flags)
+        ms, ss = zs_full[:, k], zs_std_full[:, k]
+        s_d, s_s = sd[..., :4], ss[..., 2:6]
+        mean_xv = (s_s ** 2 * zdyn[..., :4] + s_d ** 2 * ms[..., 2:6]) / (s_d ** 2 + s_s ** 2)
+        std_xv = s_d * s_s / torch.sqrt(s_d ** 2 + s_s ** 2)
+        if c.debug_no_latents:                 # stove.py:140-148: q(z) over the six SuPAIR dimensions only, latents are zeros
+            mean = torch.cat([ms[..., :2], mean_xv], -1)
+            std = torch.cat([ss[..., :2], std_xv], -1)
+        elif c.debug_no_velocity:              # stove.py:154-160: velocities ~ N(0, 1) instead of the fused estimate
+            mean = torch.cat([ms[..., :2], mean_xv[..., :2], torch.zeros_like(mean_xv[..., 2:]), zdyn[..., 4:]], -1)
+            std = torch.cat([ss[..., :2], std_xv[..., :2], torch.ones_like(std_xv[..., 2:]), sd[..., 4:]], -1)
+        else:                                  # (debug_no_reuse, stove.py:151-153, is overwritten by the if / else that follows it
+            mean = torch.cat([ms[..., :2], mean_xv, zdyn[..., 4:]], -1)          # in the reference: the flag changes nothing)
+            std = torch.cat([ss[..., :2], std_xv, sd[..., 4:]], -1)
+        zt = mean + std * eps_steps[k][..., :mean.shape[-1]]
+        lq_t = normal_log_prob(zt, mean, std)
+        if c.debug_no_latents:
+            zt = torch.cat([zt, torch.zeros_like(zdyn[..., 4:])], -1)
+        z_prev = zt
+        z_l.append(zt); zdyn_l.append(zdyn); zdyn_std_l.append(sd); mean_l.append(mean); zstd_l.append(std)
+        logq_l.append(lq_t); pred_l.append(pred)
+    st = lambda l: torch.stack(l, 1)          # noqa: E731
+    return {'z': st(z_l), 'z_dyn': st(zdyn_l), 'z_dyn_std': st(zdyn_std_l), 'mean': st(mean_l), 'std': st(zstd_l),
+            'log_q': st(logq_l), 'dynamic_pred': st(pred_l), 'rewards': rewards}
+
+
 def stove_forward(c, params, structs, x_color, eps, actions=None, detail=False, code_values=None):
     """Stove.forward -> stove_forward.  x_color (B,T,3,H,W) in [0,1]; eps from draw_eps.
     code_values (BT, N, 8): evaluate everything behind the recognition network AT these codes (the gradient still flows into the
@@ -646,39 +691,14 @@ def stove_forward(c, params, structs, x_color, eps, actions=None, detail=False, 
     dyn_std0 = torch.cat([zs_std_full[:, skip - 1, :, 2:], std0], -1)
     tstd = torch.tensor(transition_std(c), dtype=x.dtype).view(1, 1, -1)
 
-    z_l, zdyn_l, zdyn_std_l, logq_l, zstd_l, rewards = [], [], [], [], [], []
-    for t in range(skip, T):
-        act = actions[:, t - 1] if actions is not None else None
-        ap = app[:, t - 1] if (app is not None and c.debug_core_appearance) else None
-        out, rew = dynamics_forward(c, params, z[t - 1][..., 2:], act, ap)
-        rewards.append(rew)
-        m, sd = constrain_z_dyn(c, out[..., :cl // 2], out[..., cl // 2:])
-        zdyn = torch.cat([z[t - 1][..., 2:4] + m[..., :2], m[..., 2:]], -1)
-        # full_state, stove.py:103-170 (default flags)
-        ms, ss = zs_full[:, t], zs_std_full[:, t]
-        s_d, s_s = sd[..., :4], ss[..., 2:6]
-        mean_xv = (s_s ** 2 * zdyn[..., :4] + s_d ** 2 * ms[..., 2:6]) / (s_d ** 2 + s_s ** 2)
-        std_xv = s_d * s_s / torch.sqrt(s_d ** 2 + s_s ** 2)
-        if c.debug_no_latents:                 # stove.py:140-148: q(z) over the six SuPAIR dimensions only, latents are zeros
-            mean = torch.cat([ms[..., :2], mean_xv], -1)
-            std = torch.cat([ss[..., :2], std_xv], -1)
-        elif c.debug_no_velocity:              # stove.py:154-160: velocities ~ N(0, 1) instead of the fused estimate
-            mean = torch.cat([ms[..., :2], mean_xv[..., :2], torch.zeros_like(mean_xv[..., 2:]), zdyn[..., 4:]], -1)
-            std = torch.cat([ss[..., :2], std_xv[..., :2], torch.ones_like(std_xv[..., 2:]), sd[..., 4:]], -1)
-        else:                                  # (debug_no_reuse, stove.py:151-153, is overwritten by the if / else that follows it
-            mean = torch.cat([ms[..., :2], mean_xv, zdyn[..., 4:]], -1)          # in the reference: the flag changes nothing)
-            std = torch.cat([ss[..., :2], std_xv, sd[..., 4:]], -1)
-        zt = mean + std * eps['steps'][t - skip][..., :mean.shape[-1]]
-        lq_t = normal_log_prob(zt, mean, std)
-        if c.debug_no_latents:
-            zt = torch.cat([zt, torch.zeros_like(zdyn[..., 4:])], -1)
-        z[t] = zt
-        z_l.append(zt); zdyn_l.append(zdyn); zdyn_std_l.append(sd); zstd_l.append(std)
-        logq_l.append(lq_t)
+    act = actions[:, skip - 1:T - 1] if actions is not None else None
+    ap = app[:, skip - 1:T - 1] if (app is not None and c.debug_core_appearance) else None
+    rec = recursion(c, params, z[skip - 1], zs_full[:, skip:], zs_std_full[:, skip:], eps['steps'], act, ap)
+    rewards = rec['rewards']
 
-    z_s = torch.stack(z_l, 1)                                       # (B,T-2,N,18)
-    zdyn_s = torch.stack(zdyn_l, 1)
-    logq = torch.stack(logq_l, 1).sum((-2, -1)).flatten()
+    z_s = rec['z']                                                  # (B,T-2,N,18)
+    zdyn_s = rec['z_dyn']
+    logq = rec['log_q'].sum((-2, -1)).flatten()
     z_f = sy_from_quotient(z_s.flatten(0, 2))
     img_lik = scene_likelihood(c, params, structs, x[:, skip:], z_f[..., :4])
     z_sup1 = sy_from_quotient(zs[:, 1:skip])
@@ -695,8 +715,8 @@ def stove_forward(c, params, structs, x_color, eps, actions=None, detail=False, 
     info = {
         'z': sy_from_quotient(z_s), 'z_dyn': zdyn_s,
         'z_sup': sy_from_quotient(zs_full[:, skip:]),
-        'z_std': torch.stack(zstd_l, 1).mean((0, 1, 2)),
-        'z_dyn_std': torch.stack(zdyn_std_l, 1)[..., :4].mean((0, 1, 2)),
+        'z_std': rec['std'].mean((0, 1, 2)),
+        'z_dyn_std': rec['z_dyn_std'][..., :4].mean((0, 1, 2)),
         'z_sup_std': zs_std_full[:, skip:].mean((0, 1, 2)),
         'log_q': logq.mean(), 'translik': trans.mean(),
         'img_lik': img_lik, 'img_lik_sup': img_lik_sup,

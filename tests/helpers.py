@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (oracle side)."""
+import copy
 import os
 
 import numpy as np
@@ -123,3 +124,67 @@ def replicate_eps(eps, src):
     """the oracle's noise draws (O.draw_eps) of K sequences, row b of the result = row src[b]"""
     idx = torch.as_tensor(np.asarray(src))
     return {'latent': eps['latent'][idx], 'std': eps['std'][idx], 'steps': [e[idx] for e in eps['steps']]}
+
+
+# ------------------------------------------------------------------------------------------------ dynamics at every object count
+# Inputs of tests/test_oracle_counts_cpu.py and tests/test_gpu_dynamics_counts.py: drawn in float64 from a seeded CPU generator, nothing
+# symmetric between the objects (every object its own position, scale and appearance row: a swapped or dropped edge changes the numbers).
+DYN_VARIANTS = {
+    'plain': {},                                                                            # cl/2 inputs per node
+    'act': dict(action_conditioned=True, action_space=9),                                   # cl/2 + 4: actions without appearance
+    'actapp': dict(action_conditioned=True, action_space=9, debug_core_appearance=True),    # cl/2 + 7
+}
+
+
+def dyn_width_cfg(cl):
+    return {} if cl == 32 else dict(cl=cl, transition_lik_std=[0.01] * (cl // 2))
+
+
+_DYN_ORACLES = {}
+
+
+def dyn_oracle(cl, n_obj, variant, regime='analytic', dtype=torch.float64, nonlinear='relu'):
+    """(config, the 'dyn.' parameters) of the oracle at one width / object count / input variant / weight regime: the parameters are
+    built once and shared (they carry requires_grad; whoever differentiates clears their .grad first), the config is the caller's."""
+    key = (cl, n_obj, variant, regime, dtype)
+    if key not in _DYN_ORACLES:
+        c, _, params = oracle_setup(dtype, regime=regime, num_obj=n_obj, **DYN_VARIANTS[variant], **dyn_width_cfg(cl))
+        _DYN_ORACLES[key] = (c, {k: v for k, v in params.items() if k.startswith('dyn.')})
+    c, params = _DYN_ORACLES[key]
+    c = copy.copy(c)
+    c.debug_nonlinear = nonlinear
+    return c, params
+
+
+def embed_actions(params, actions, n_obj):
+    """one-hot actions (..., A) -> the action embedding's rows (..., n_obj, 4), as dynamics_forward appends them to the state"""
+    return O._lin(params, 'dyn.action_embedding_layer', actions).view(*actions.shape[:-1], n_obj, 4)
+
+
+def dyn_state(g, B, n_obj, cl, lo=-0.8, hi=0.8):
+    """(B, N, cl/2) core inputs [x, y, vx, vy, latents] in [lo, hi]"""
+    return torch.rand(B, n_obj, cl // 2, generator=g, dtype=torch.float64) * (hi - lo) + lo
+
+
+def dyn_actions(g, variant, *lead):
+    """one-hot actions (*lead, 9) in float64, or None for the plain variant"""
+    if variant == 'plain':
+        return None
+    return torch.nn.functional.one_hot(torch.randint(0, 9, lead, generator=g), 9).double()
+
+
+def dyn_appearance(g, variant, *lead):
+    """appearance rows (*lead, 3) in [0, 1], or None"""
+    return torch.rand(*lead, 3, generator=g, dtype=torch.float64) if variant == 'actapp' else None
+
+
+def dyn_recursion_inputs(g, B, Ts, n_obj, cl):
+    """-> z1 (B,N,cl/2+2), zsup, zsstd (B,Ts,N,6), eps (B,Ts,N,cl/2+2): scales in [0.15, 0.6], z1's positions in [-0.8, 0.8] (its
+    velocities and latents in [-0.3, 0.3]), SuPAIR means in [-0.9, 0.9] with scales in [0.15, 0.6], stds in [0.02, 0.3]"""
+    D = cl // 2
+    r = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64)          # noqa: E731
+    z1 = torch.cat([r(B, n_obj, 2) * 0.45 + 0.15, r(B, n_obj, 2) * 1.6 - 0.8, r(B, n_obj, D - 2) * 0.6 - 0.3], -1)
+    zsup = torch.cat([r(B, Ts, n_obj, 2) * 0.45 + 0.15, r(B, Ts, n_obj, 4) * 1.8 - 0.9], -1)
+    zsstd = r(B, Ts, n_obj, 6) * 0.28 + 0.02
+    eps = torch.randn(B, Ts, n_obj, D + 2, generator=g, dtype=torch.float64)
+    return z1, zsup, zsstd, eps

@@ -530,10 +530,13 @@ def test_elbo_assembly_against_torch():
                                       (7, False), (8, False), (7, True), (8, True)])
 def test_small_graph_recursion_matches_step_kernels(n_obj, ac, nonlinear):
     """The persistent time loops against the host loop over the single-step MFMA kernel + PyTorch autograd: ELBO, every gradient,
-    and the rollout.  N <= 6: the small-graph kernels (csrc/gnn_small*.hip: N = 2, 4 and 5 have no goldens; five and six objects
-    run two node rows per wave and two tiles of edge columns).  N = 7, 8: the workgroup-wide MFMA loops of csrc/gnn.hip
-    (dyn_loop_fwd_k / dyn_loop_bwd_k / rollout_fwd_k), which no BASELINE configuration reaches since six objects moved to the
-    small-graph path -- this test is what keeps them honest.  `ac`: action-conditioned, 23 inputs per node and the reward head."""
+    and the rollout.  N <= 6: the small-graph kernels (csrc/gnn_small*.hip; five and six objects run two node rows per wave and two
+    tiles of edge columns).  N = 7, 8: the workgroup-wide MFMA loops of csrc/gnn.hip (dyn_loop_fwd_k / dyn_loop_bwd_k /
+    rollout_fwd_k), which no BASELINE configuration reaches since six objects moved to the small-graph path.  `ac`:
+    action-conditioned, 23 inputs per node and the reward head.  This is a comparison of one kernel of ours with another, through the
+    whole model; the counts without goldens (2, 4, 5, 7, 8, and one object) are held to the float64 oracle, step, recursion and
+    rollout each on its own, by tests/test_gpu_dynamics_counts.py -- what stays particular to this test is the agreement of the two
+    paths Stove.forward can take."""
     recursion_against_step_kernels(n_obj, ac, nonlinear)
 
 
