@@ -313,6 +313,22 @@ int stove_rollout_sample_fwd(const float* z_last, const float* extra, const floa
                              float* log_q, float* zstd, float* pred, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
                              float pos_var, float vel_std, float lat_std, void* stream);
 
+/* ---- Backward of stove_rollout_fwd (eps NULL) and of stove_rollout_sample_fwd (eps: the draws the forward was given), all steps in
+ * one launch plus the fixed-order reduction of the weight gradients; one stream, no synchronisation (the call can be captured).
+ * z_pred is the forward's output: step t is recomputed from z_pred[:, t-1] (z_last at t = 0; when sampling, the drawn state), so no
+ * activations are stored.  Upstream gradients: d_z_pred (B,num,N,18), d_log_q (B,num,N,16), d_pred (B,num,N,32); each may be NULL
+ * (= zeros), d_log_q only with eps.  zstd and eps get no gradient.  Outputs, every element written by the call: d_z_last (B,N,18)
+ * (the scale columns receive the sum of d_z_pred's over the steps), d_extra (B,A,N,E) (NULL exactly when extra is; row t % A
+ * accumulates its steps in a fixed order, a row no step reads is zero), g_params (stove_gnn_grad_floats() floats, [dW | dvectors]).
+ * B == 0 or num == 0: the outputs are zeros.  ws: stove_rollout_bwd_ws_bytes(B, N) bytes (0 for a B or N the call rejects).
+ * NULL required pointer, d_log_q without eps, NULL ws, N or sin_dim out of range: hipErrorInvalidValue, nothing launched.
+ * No atomics: two calls on the same inputs agree bit for bit. */
+size_t stove_rollout_bwd_ws_bytes(int B, int N);
+int stove_rollout_bwd(const float* z_last, const float* extra, const float* params, const float* eps, const float* z_pred,
+                      const float* d_z_pred, const float* d_log_q, const float* d_pred, float* d_z_last, float* d_extra,
+                      float* g_params, void* ws, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var,
+                      float vel_std, float lat_std, void* stream);
+
 /* ---- One expansion of M search trees on the learned model (reference mcts/mcts_stove.py:95-137, 186-196; csrc/plan.hip), cl = 32,
  * action-conditioned.  z_pool (M, cap, N, 18): the trees' node states, resident on the device.  Per tree m: leaf[m] the pool slot of
  * the selected leaf, child[m] the first of A consecutive slots that receive its children, len_s[m] the reference's key length of the
@@ -364,6 +380,11 @@ int stove_rollout_fwd_cl(const float* z_last, const float* extra, const float* p
 int stove_rollout_sample_fwd_cl(const float* z_last, const float* extra, const float* params, const float* eps, float* z_pred,
                                 float* log_q, float* zstd, float* pred, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc,
                                 int elu, float pos_var, float vel_std, float lat_std, void* stream);
+size_t stove_rollout_bwd_ws_bytes_cl(int cl, int B, int N);
+int stove_rollout_bwd_cl(const float* z_last, const float* extra, const float* params, const float* eps, const float* z_pred,
+                         const float* d_z_pred, const float* d_log_q, const float* d_pred, float* d_z_last, float* d_extra,
+                         float* g_params, void* ws, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
+                         float pos_var, float vel_std, float lat_std, void* stream);
 
 /* ---- Stove._3_only_match_objects / _greedy_match_objects / _volatile_match_objects
  * (stove.py:200-329, 432-514, 331-430): the T-serial nearest-neighbour re-ordering of objects.

@@ -83,6 +83,10 @@ def _declare(lib):
         'stove_dynloop_bwd_overlap': (I, [P] * 19 + [I] * 6 + [F] * 3 + [P, P]),
         'stove_rollout_fwd': (I, [P] * 6 + [I] * 7 + [F] * 3 + [P]),
         'stove_rollout_sample_fwd': (I, [P] * 8 + [I] * 7 + [F] * 3 + [P]),
+        'stove_rollout_bwd_ws_bytes': (S, [I, I]),
+        'stove_rollout_bwd': (I, [P] * 12 + [I] * 7 + [F] * 3 + [P]),
+        'stove_rollout_bwd_ws_bytes_cl': (S, [I, I, I]),
+        'stove_rollout_bwd_cl': (I, [P] * 12 + [I] * 8 + [F] * 3 + [P]),
         'stove_plan_expand_ws_bytes': (S, [I] * 5),
         'stove_plan_expand': (I, [P] * 14 + [I] * 9 + [F] * 4 + [P]),
         'stove_gnn_param_floats_cl': (S, [I]),

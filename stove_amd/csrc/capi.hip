@@ -164,7 +164,8 @@ extern "C" {
 //    stove_gnn_grad_floats_cl, stove_gnn_bwd_ws_bytes_cl, stove_gnn_fwd_cl, stove_gnn_bwd_cl, stove_dynloop_fwd_cl, stove_dynloop_bwd_cl,
 //    stove_rollout_fwd_cl).
 //    (added since, nothing changed: stove_rollout_sample_fwd, stove_rollout_sample_fwd_cl -- the sampling rollout;
-//     stove_plan_expand_ws_bytes, stove_plan_expand -- one expansion of a batch of search trees)
+//     stove_plan_expand_ws_bytes, stove_plan_expand -- one expansion of a batch of search trees;
+//     stove_rollout_bwd_ws_bytes, stove_rollout_bwd and their _cl siblings -- the backward of both rollouts)
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1057,6 +1058,36 @@ int stove_rollout_sample_fwd(const float* z_last, const float* extra, const floa
                           params, eps, z_pred, log_q, zstd, pred, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
 }
 
+// An empty rollout backward (B == 0 or num == 0) on `st`: every output is zeros
+static int rollout_bwd_empty(float* d_z_last, float* d_extra, float* g_params, size_t zw, size_t grads, int B, int A, int N, int E, hipStream_t st) {
+  if (B > 0) STOVE_TRY(hipMemsetAsync(d_z_last, 0, (size_t)B * N * zw * sizeof(float), st));
+  if (B > 0 && d_extra != nullptr && A > 0 && E > 0) STOVE_TRY(hipMemsetAsync(d_extra, 0, (size_t)B * A * N * E * sizeof(float), st));
+  STOVE_TRY(hipMemsetAsync(g_params, 0, grads * sizeof(float), st));
+  return 0;
+}
+
+size_t stove_rollout_bwd_ws_bytes(int B, int N) {
+  if (B < 1 || N < 1 || N > stove_validate::kMaxObjects) return 0;
+  return stove_gnn_bwd_ws_bytes(B, N);
+}
+
+int stove_rollout_bwd(const float* z_last, const float* extra, const float* params, const float* eps, const float* z_pred,
+                      const float* d_z_pred, const float* d_log_q, const float* d_pred, float* d_z_last, float* d_extra,
+                      float* g_params, void* ws, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, float pos_var,
+                      float vel_std, float lat_std, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  STOVE_VALIDATE(rollout_bwd(z_last, extra, params, eps, z_pred, d_log_q, d_z_last, d_extra, g_params, ws, B, num, A, N, sin_dim));
+  if (B == 0 || num == 0) return rollout_bwd_empty(d_z_last, d_extra, g_params, 18, kGnnGrads, B, A, N, sin_dim - 16, st);
+  LoopConst kc{pos_var, vel_std, lat_std};
+  const int nb = stove_gnn_blocks(B, N);
+  int rc = STOVE_LAUNCH_LDS(rollout_bwd_k, dim3(nb), dim3(256), kGnnLdsBytes, st, z_last, extra, params, eps, z_pred, d_z_pred, d_log_q, d_pred,
+                            d_z_last, d_extra, (float*)ws, B, num, A < 1 ? 1 : A, N, gnn_group_for(B, N), sin_dim, lim_enc, elu, kc);
+  if (rc) return rc;
+  STOVE_LAUNCH(reduce_chunks_k, dim3((kGnnGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, kGnnGrads, nb, 0);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---------------------------------------------------------------- GNN dynamics core at state-code lengths 16 / 64 (gnn_cl.hip)
 size_t stove_gnn_param_floats_cl(int cl) { return cl == 16 ? GC<16>::kParams : (cl == 64 ? GC<64>::kParams : 0); }
 size_t stove_gnn_grad_floats_cl(int cl) { return cl == 16 ? GC<16>::kGrads : (cl == 64 ? GC<64>::kGrads : 0); }
@@ -1158,6 +1189,31 @@ int stove_rollout_sample_fwd_cl(const float* z_last, const float* extra, const f
     return STOVE_LAUNCH_LDS(gnn_cl_rollout_sample_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), GC<CL>::kLdsFloats * sizeof(float),
                             (hipStream_t)stream, z_last, extra, params, eps, z_pred, log_q, zstd, pred, B, num, A < 1 ? 1 : A, N,
                             cl_group_for<CL>(B, N), sin_dim, lim_enc, elu, kc);
+  });
+}
+
+size_t stove_rollout_bwd_ws_bytes_cl(int cl, int B, int N) { return stove_gnn_bwd_ws_bytes_cl(cl, B, N); }
+
+int stove_rollout_bwd_cl(const float* z_last, const float* extra, const float* params, const float* eps, const float* z_pred,
+                         const float* d_z_pred, const float* d_log_q, const float* d_pred, float* d_z_last, float* d_extra,
+                         float* g_params, void* ws, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
+                         float pos_var, float vel_std, float lat_std, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  STOVE_VALIDATE(rollout_bwd(z_last, extra, params, eps, z_pred, d_log_q, d_z_last, d_extra, g_params, ws, B, num, A, N, sin_dim,
+                             stove_validate::gnn_limits_cl(cl)));
+  LoopConst kc{pos_var, vel_std, lat_std};
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    using K = GC<CL>;
+    if (B == 0 || num == 0) return rollout_bwd_empty(d_z_last, d_extra, g_params, K::ZW, K::kGrads, B, A, N, sin_dim - K::D, st);
+    const int nb = cl_blocks<CL>(B, N);
+    int rc = STOVE_LAUNCH_LDS(gnn_cl_rollout_bwd_k<CL>, dim3(nb), dim3(256), K::kLdsFloats * sizeof(float), st, z_last, extra, params, eps,
+                              z_pred, d_z_pred, d_log_q, d_pred, d_z_last, d_extra, (float*)ws, B, num, A < 1 ? 1 : A, N,
+                              cl_group_for<CL>(B, N), sin_dim, lim_enc, elu, kc);
+    if (rc) return rc;
+    STOVE_LAUNCH(reduce_chunks_k, dim3((K::kGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, K::kGrads, nb, 0);
+    STOVE_LAUNCH_CHECK();
+    return 0;
   });
 }
 

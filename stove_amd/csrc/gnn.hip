@@ -1339,4 +1339,107 @@ __global__ __launch_bounds__(256) void rollout_sample_fwd_k(const float* __restr
   }
 }
 
+// =================================================================================================
+// backward of both rollouts (rollout_fwd_k / rollout_sample_fwd_k and their small-graph siblings), block-wise at every N:
+// as dyn_loop_bwd_k, the time loop runs backwards, each step's forward is recomputed in LDS from the state the forward fed it --
+// z_pred[:, t-1] (the DRAWN state when sampling), z_last at t = 0 -- and the weight gradients stay in the MFMA accumulators over
+// all steps.  eps null: the mean rollout (zstd carries no gradient, so d sd = 0).
+//   upstream: d_z_pred (B,num,N,18), d_log_q (B,num,N,16), d_pred (B,num,N,32), any may be null (d_log_q only with eps)
+//   outputs : d_z_last (B,N,18), d_extra (B,A,N,E) (every row written: a row no step reads is zero), gpart[block][kGnnGrads]
+// The scale columns of z_pred are copies of z_last's at every step: their gradient is the sum over the steps, kept in columns 0..1 of
+// the carry.  d_extra[b, t % A] is accumulated over the steps that share the row by the thread that owns the element, latest step
+// first: a fixed order, no atomics.
+// =================================================================================================
+__global__ __launch_bounds__(256) void rollout_bwd_k(const float* __restrict__ z_last, const float* __restrict__ extra,
+                                                     const float* __restrict__ P, const float* __restrict__ eps,
+                                                     const float* __restrict__ z_pred, const float* __restrict__ d_z_pred,
+                                                     const float* __restrict__ d_log_q, const float* __restrict__ d_pred,
+                                                     float* __restrict__ d_z_last, float* d_extra, float* __restrict__ gpart,
+                                                     int B, int num, int A, int N, int G, int sin_dim, int lim_enc, int elu, LoopConst kc) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const GnnLds L = carve(lds);
+  const int b0 = blockIdx.x * G;
+  const GnnShape sh = make_shape(N, G, b0, B, sin_dim, lim_enc, elu);
+  const int E = sin_dim - 16;
+  lds_zero(lds, kGnnLdsFloats);
+  f32x4 acc[SL_END], vacc[VSLOTS];
+#pragma unroll
+  for (int k = 0; k < SL_END; ++k) acc[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < VSLOTS; ++k) vacc[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  float* CAR = L.X;   // [16][20] gradient carried into z_pred[t] from step t+1; columns 0..1: the scale gradient summed so far
+  const WFrag<32> o1t = wfrag_load<32>(P + W_END + W_O1 + (wave_id() & 1) * 16 * 32, 32);
+  WG_SYNC();
+  gnn_setup(L, sh, P + 2 * W_END);
+  if (d_extra != nullptr) {      // extra rows past the last step (A > num): nothing reads them
+    for (int a = num; a < A; ++a)
+      for (int i = threadIdx.x; i < sh.NR * E; i += blockDim.x)
+        d_extra[(((size_t)(b0 + (i / E) / N) * A + a) * N + (i / E) % N) * E + i % E] = 0.0f;
+  }
+  WG_SYNC();
+  for (int t = num - 1; t >= 0; --t) {
+    for (int i = threadIdx.x; i < sh.NR * sin_dim; i += blockDim.x) {
+      const int r = i / sin_dim, c = i % sin_dim;
+      const int b = b0 + r / N, n = r % N;
+      float v;
+      if (c < 16) v = (t == 0) ? z_last[((size_t)b * N + n) * 18 + 2 + c] : z_pred[(((size_t)b * num + t - 1) * N + n) * 18 + 2 + c];
+      else v = extra[(((size_t)b * A + (t % A)) * N + n) * E + (c - 16)];
+      L.SIN[r * LDN + c] = v;
+    }
+    {
+      const FwdW fw = gnn_fwdw_load(P);
+      WG_SYNC();
+      gnn_forward(L, sh, P, fw);
+    }
+    // epilogue backward: per (row, q) -> dRES in L.DA, position carry in L.PC
+    for (int idx = threadIdx.x; idx < 16 * 18; idx += blockDim.x) {
+      const int r = idx / 18, q = idx % 18;
+      if (r >= sh.NR) {
+        if (q >= 2) {
+          L.DA[r * LDN + q - 2] = 0.0f;
+          L.DA[r * LDN + 16 + q - 2] = 0.0f;
+        }
+        continue;
+      }
+      const size_t o = ((size_t)(b0 + r / N) * num + t) * N + r % N;
+      const float gz = (d_z_pred != nullptr ? d_z_pred[o * 18 + q] : 0.0f) + CAR[r * 20 + q];
+      if (q < 2) {
+        CAR[r * 20 + q] = gz;                                                // z_pred[:, t, :, :2] = z_last[..., :2]
+        continue;
+      }
+      const int d = q - 2;
+      const float kd = std_scale(d, kc);
+      const float m = 2.0f * sigmoidf_(L.RES[r * LDN + d]) - 1.0f;
+      float gs = 0.0f;                                                       // sd * dL/dsd
+      float sd = 0.0f;
+      if (eps != nullptr) {
+        // z = mean + sd eps, log_q = -eps^2/2 - log sd - const:  dL/dsd = gz eps - d_log_q / sd
+        sd = kd * sigmoidf_(L.RES[r * LDN + 16 + d]);
+        gs = gz * eps[o * 16 + d] * sd - (d_log_q != nullptr ? d_log_q[o * 16 + d] : 0.0f);
+      }
+      if (d < 2) L.PC[r * 2 + d] = gz;                                       // mean position = previous position + m
+      L.DA[r * LDN + d] = gz * 0.5f * (1.0f - m * m);                        // m = 2 sigmoid - 1
+      L.DA[r * LDN + 16 + d] = gs * (1.0f - sd / kd);                        // sd = k sigmoid
+    }
+    WG_SYNC();
+    gnn_backward(L, sh, P + W_END, o1t, acc, vacc,
+                 d_pred != nullptr ? d_pred + ((size_t)b0 * num + t) * N * 32 : nullptr, (size_t)num * N * 32);
+    // new carry into z_pred[t-1]
+    for (int i = threadIdx.x; i < sh.NR * sin_dim; i += blockDim.x) {
+      const int r = i / sin_dim, c = i % sin_dim;
+      const float g = L.DA[r * LDN + c];
+      if (c < 16) {
+        CAR[r * 20 + 2 + c] = g + (c < 2 ? L.PC[r * 2 + c] : 0.0f);
+      } else {
+        float* dst = d_extra + (((size_t)(b0 + r / N) * A + (t % A)) * N + r % N) * E + (c - 16);
+        *dst = (t + A < num) ? *dst + g : g;                                 // a later step of this row has been here: same thread
+      }
+    }
+    WG_SYNC();
+  }
+  for (int i = threadIdx.x; i < sh.NR * 18; i += blockDim.x) d_z_last[(size_t)b0 * N * 18 + i] = CAR[(i / 18) * 20 + i % 18];
+  WG_SYNC();
+  gnn_store_grads(acc, vacc, gpart + (size_t)blockIdx.x * kGnnGrads);
+}
+
 }  // namespace stove

@@ -948,6 +948,104 @@ __global__ __launch_bounds__(256) void gnn_cl_rollout_sample_k(const float* __re
   }
 }
 
+// =================================================================================================
+// backward of both rollouts, as rollout_bwd_k (gnn.hip) with D = CL/2: the time loop backwards, each step's forward recomputed from
+// z_pred[:, t-1] (z_last at t = 0), weight gradients in the MFMA accumulators over all steps.  eps null: the mean rollout.
+//   upstream (any may be null; d_log_q only with eps): d_z_pred (B,num,N,D+2), d_log_q (B,num,N,D), d_pred (B,num,N,CL)
+//   outputs: d_z_last (B,N,D+2), d_extra (B,A,N,E) (every row written), gpart[block][kGrads]
+// The carry lives in L.X (columns 0..1: the scale gradient summed over the steps); no buffer beyond cl_carve's.
+// =================================================================================================
+template <int CL>
+__global__ __launch_bounds__(256) void gnn_cl_rollout_bwd_k(const float* __restrict__ z_last, const float* __restrict__ extra,
+                                                            const float* __restrict__ P, const float* __restrict__ eps,
+                                                            const float* __restrict__ z_pred, const float* __restrict__ d_z_pred,
+                                                            const float* __restrict__ d_log_q, const float* __restrict__ d_pred,
+                                                            float* __restrict__ d_z_last, float* d_extra, float* __restrict__ gpart,
+                                                            int B, int num, int A, int N, int G, int sin_dim, int lim_enc, int elu, LoopConst kc) {
+  using K = GC<CL>;
+  constexpr int D = K::D, ZW = K::ZW, LDN = K::LDN, LDZ = K::LDZ;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const ClLds<CL> L = cl_carve<CL>(lds);
+  const int b0 = blockIdx.x * G;
+  const GnnShape sh = make_shape(N, G, b0, B, sin_dim, lim_enc, elu);
+  const int E = sin_dim - D;
+  lds_zero(lds, K::kLdsFloats);
+  f32x4 acc[K::NSLOT];
+  float vg[K::VQ];
+#pragma unroll
+  for (int k = 0; k < K::NSLOT; ++k) acc[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < K::VQ; ++k) vg[k] = 0.0f;
+  float* CAR = L.X;   // [16][LDZ] gradient carried into z_pred[t] from step t+1; columns 0..1: the scale gradient summed so far
+  WG_SYNC();
+  cl_setup<CL>(L, sh, P + 2 * K::W_END);
+  if (d_extra != nullptr) {      // extra rows past the last step (A > num): nothing reads them
+    for (int a = num; a < A; ++a)
+      for (int i = threadIdx.x; i < sh.NR * E; i += blockDim.x)
+        d_extra[(((size_t)(b0 + (i / E) / N) * A + a) * N + (i / E) % N) * E + i % E] = 0.0f;
+  }
+  WG_SYNC();
+  for (int t = num - 1; t >= 0; --t) {
+    for (int i = threadIdx.x; i < sh.NR * sin_dim; i += blockDim.x) {
+      const int r = i / sin_dim, c = i % sin_dim;
+      const int b = b0 + r / N, n = r % N;
+      float v;
+      if (c < D) v = (t == 0) ? z_last[((size_t)b * N + n) * ZW + 2 + c] : z_pred[(((size_t)b * num + t - 1) * N + n) * ZW + 2 + c];
+      else v = extra[(((size_t)b * A + (t % A)) * N + n) * E + (c - D)];
+      L.SIN[r * LDN + c] = v;
+    }
+    WG_SYNC();
+    cl_forward<CL>(L, sh, P);
+    // epilogue backward: per (row, q) -> dRES in L.DA, position carry in L.PC
+    for (int idx = threadIdx.x; idx < K::NRP * ZW; idx += blockDim.x) {
+      const int r = idx / ZW, q = idx % ZW;
+      if (r >= sh.NR) {
+        if (q >= 2) {
+          L.DA[r * LDN + q - 2] = 0.0f;
+          L.DA[r * LDN + D + q - 2] = 0.0f;
+        }
+        continue;
+      }
+      const size_t o = ((size_t)(b0 + r / N) * num + t) * N + r % N;
+      const float gz = (d_z_pred != nullptr ? d_z_pred[o * ZW + q] : 0.0f) + CAR[r * LDZ + q];
+      if (q < 2) {
+        CAR[r * LDZ + q] = gz;                                               // z_pred[:, t, :, :2] = z_last[..., :2]
+        continue;
+      }
+      const int d = q - 2;
+      const float kd = std_scale(d, kc);
+      const float m = 2.0f * sigmoidf_(L.RES[r * LDN + d]) - 1.0f;
+      float gs = 0.0f;                                                       // sd * dL/dsd
+      float sd = 0.0f;
+      if (eps != nullptr) {
+        // z = mean + sd eps, log_q = -eps^2/2 - log sd - const:  dL/dsd = gz eps - d_log_q / sd
+        sd = kd * sigmoidf_(L.RES[r * LDN + D + d]);
+        gs = gz * eps[o * D + d] * sd - (d_log_q != nullptr ? d_log_q[o * D + d] : 0.0f);
+      }
+      if (d < 2) L.PC[r * 2 + d] = gz;                                       // mean position = previous position + m
+      L.DA[r * LDN + d] = gz * 0.5f * (1.0f - m * m);                        // m = 2 sigmoid - 1
+      L.DA[r * LDN + D + d] = gs * (1.0f - sd / kd);                         // sd = k sigmoid
+    }
+    WG_SYNC();
+    cl_backward<CL>(L, sh, P + K::W_END, acc, vg, d_pred != nullptr ? d_pred + ((size_t)b0 * num + t) * N * CL : nullptr,
+                    (size_t)num * N * CL);
+    // new carry into z_pred[t-1]
+    for (int i = threadIdx.x; i < sh.NR * sin_dim; i += blockDim.x) {
+      const int r = i / sin_dim, c = i % sin_dim;
+      const float g = L.DA[r * LDN + c];
+      if (c < D) {
+        CAR[r * LDZ + 2 + c] = g + (c < 2 ? L.PC[r * 2 + c] : 0.0f);
+      } else {
+        float* dst = d_extra + (((size_t)(b0 + r / N) * A + (t % A)) * N + r % N) * E + (c - D);
+        *dst = (t + A < num) ? *dst + g : g;                                 // a later step of this row has been here: same thread
+      }
+    }
+    WG_SYNC();
+  }
+  for (int i = threadIdx.x; i < sh.NR * ZW; i += blockDim.x) d_z_last[(size_t)b0 * N * ZW + i] = CAR[(i / ZW) * LDZ + i % ZW];
+  cl_store_grads<CL>(acc, vg, gpart + (size_t)blockIdx.x * K::kGrads);
+}
+
 // ---- host side of the entry points in capi.hip
 // f(std::integral_constant<int, CL>) for a supported width
 template <class F>

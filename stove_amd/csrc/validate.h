@@ -181,6 +181,21 @@ inline int rollout_sample_fwd(const float* z_last, const float* extra, const flo
   if (B == 0 || num == 0) return 0;
   return null_any(eps, log_q) ? kStoveInvalidValue : 0;
 }
+// the backward of either rollout (eps == NULL: the mean rollout).  g_params, and d_z_last / d_extra where they have elements, are
+// overwritten even by an empty call (B == 0 or num == 0: zeros), so they are required throughout; of the upstream gradients d_z_pred
+// and d_pred may be NULL, d_log_q too but only a sampling call (eps) can have one.  d_extra is NULL exactly when extra is.
+inline int rollout_bwd(const float* z_last, const float* extra, const float* params, const float* eps, const float* z_pred,
+                       const float* d_log_q, const float* d_z_last, const float* d_extra, const float* g_params, const void* ws, int B,
+                       int num, int A, int N, int sin_dim, const GnnLimits& k = kGnn32) {
+  if (k.bad(B, N, sin_dim) || num < 0 || g_params == nullptr) return kStoveInvalidValue;
+  if (d_log_q != nullptr && eps == nullptr) return kStoveInvalidValue;
+  if ((extra == nullptr) != (d_extra == nullptr)) return kStoveInvalidValue;
+  if (sin_dim > k.lo && (extra == nullptr || A < 1)) return kStoveInvalidValue;
+  if (B == 0) return 0;
+  if (d_z_last == nullptr) return kStoveInvalidValue;
+  if (num == 0) return 0;
+  return (null_any(z_last, params, z_pred) || ws == nullptr) ? kStoveInvalidValue : 0;
+}
 
 // ---- stove_plan_expand: one expansion of M search trees (csrc/plan.hip).  Everything the host can see; the indices themselves
 // (leaf, child, len_s, acts) are device memory and are checked by the kernels.  The rollout behind it is the cl = 32 one.

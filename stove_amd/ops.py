@@ -799,40 +799,83 @@ def dyn_loop(z1, zsup, zsstd, eps, extra, image, lim_enc, elu, consts, want_pred
                             want_pred, sink)
 
 
-@torch.no_grad()
-def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, want_pred=False, eps=None, want_logq=False):
-    """Generative rollout (forward only): z_last (B,N,cl/2+2), extra (B,A,N,E) or None -> z_pred (B,num,N,cl/2+2), zstd, pred.
+class _RolloutFn(torch.autograd.Function):
+    """Both branches of the generative rollout, one launch for all `num` steps each way (eps None: the mean prediction).  The forward
+    is the forward-only entry point, unchanged; nothing but its output is saved: the backward (stove_rollout_bwd) recomputes step t
+    from z_pred[:, t-1].  Differentiable: z_pred, pred, log_q -> z_last, extra, the parameter image.  zstd and eps get no gradient."""
+
+    @staticmethod
+    def forward(ctx, z_last, extra, w_img, v_img, wt_img, eps, width, num, lim_enc, elu, consts, want_std, want_pred, sink=None):
+        z_last, extra, eps = _f32(z_last), _f32(extra), _f32(eps)
+        B, N = z_last.shape[:2]
+        A = extra.shape[1] if extra is not None else 1
+        D = width.D
+        sd = D + (extra.shape[-1] if extra is not None else 0)
+        dev = z_last.device
+        params = width.image(_f32(w_img), _f32(v_img), _f32(wt_img))
+        consts = tuple(float(c) for c in consts)
+        with torch.cuda.device(dev):
+            z_pred = torch.empty(B, num, N, D + 2, dtype=torch.float32, device=dev)
+            zstd = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if want_std else None
+            pred = torch.empty(B, num, N, width.cl, dtype=torch.float32, device=dev) if want_pred else None
+            log_q = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if eps is not None else None
+            tail = (B, num, A, N, sd, int(lim_enc), int(elu), *consts, stream())
+            if eps is None:
+                width.call('stove_rollout_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred)), *tail)
+            else:
+                width.call('stove_rollout_sample_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(eps), ptr(z_pred), ptr(log_q), ptr(zstd),
+                                                        ptr(pred)), *tail)
+        ctx.save_for_backward(z_last, extra, params, eps, z_pred)
+        ctx.cfg = (width, num, int(lim_enc), int(elu), consts, sd, A)
+        ctx.sink, ctx.flat = sink, v_img is None
+        ctx.set_materialize_grads(False)          # a cotangent nothing supplies reaches the kernel as a null pointer, not as zeros
+        if zstd is not None:
+            ctx.mark_non_differentiable(zstd)
+        return z_pred, zstd, pred, log_q
+
+    @staticmethod
+    def backward(ctx, dz, _dzstd, dpred, dlogq):
+        z_last, extra, params, eps, z_pred = ctx.saved_tensors
+        width, num, lim_enc, elu, consts, sd, A = ctx.cfg
+        B, N = z_last.shape[:2]
+        dev = z_last.device
+        with torch.cuda.device(dev):
+            d_z_last = torch.empty_like(z_last)
+            d_extra = torch.empty_like(extra) if extra is not None else None
+            g = torch.empty(width.size('stove_gnn_grad_floats'), dtype=torch.float32, device=dev)
+            ws = _ws(width.size('stove_rollout_bwd_ws_bytes', B, N), dev)
+            width.call('stove_rollout_bwd', (ptr(z_last), ptr(extra), ptr(params), ptr(eps), ptr(z_pred), ptr(_f32(dz)), ptr(_f32(dlogq)),
+                                             ptr(_f32(dpred)), ptr(d_z_last), ptr(d_extra), ptr(g), ptr(ws)),
+                       B, num, A, N, sd, lim_enc, elu, *consts, stream())
+        if ctx.sink is not None:
+            ctx.sink(g)
+        if ctx.sink is not None or ctx.flat:      # (a prebuilt image is not a leaf of the layers' parameters: the sink is its way back)
+            return (d_z_last, d_extra) + (None,) * 12
+        return (d_z_last, d_extra, *width.split(g)) + (None,) * 10
+
+
+def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, want_pred=False, eps=None, want_logq=False, sink=None):
+    """Generative rollout: z_last (B,N,cl/2+2), extra (B,A,N,E) or None -> z_pred (B,num,N,cl/2+2), zstd, pred.
     With eps (B,num,N,cl/2) standard normals, or a NoiseSource to draw them from: the sampling branch in one launch (stove_rollout_sample_fwd) -- every step draws
     z = mean + sd eps, which feeds the next one -> (z_pred, zstd, pred, log_q) with log_q (B,num,N,cl/2) the draws' log-density.
-    `want_logq` asks for the log-density of a sampling call; without eps there is nothing it could be of."""
+    `want_logq` asks for the log-density of a sampling call; without eps there is nothing it could be of.
+    Differentiable in one launch (_RolloutFn): z_pred, pred and log_q carry gradients to z_last, extra and the parameter image -- to
+    `image`'s (w_img, v_img) or, with a prebuilt image, into `sink` as gnn_step / dyn_loop do; zstd and eps get none.  With autograd
+    off, or nothing requiring a gradient, this is the forward-only call it has always been."""
     if want_logq and eps is None:
         raise ValueError('ops.rollout: want_logq needs eps (the mean rollout draws nothing)')
-    z_last, extra = _f32(z_last), _f32(extra)
     B, N = z_last.shape[:2]
-    A = extra.shape[1] if extra is not None else 1
     width = gnn_width(2 * (z_last.shape[-1] - 2))
     D = width.D
-    sd = D + (extra.shape[-1] if extra is not None else 0)
-    dev = z_last.device
-    params = width.image(_f32(image[0]), _f32(image[1]), _f32(image[2]))
     if isinstance(eps, NoiseSource):                 # one draw for all the steps, on the stream the rollout follows on
         eps = eps.normal(B * num * N * D).view(B, num, N, D)
     if eps is not None:
-        eps = _f32(eps)
+        eps = eps.detach()
         if tuple(eps.shape) != (B, num, N, D):
             raise ValueError('ops.rollout: eps is %s, the rollout needs %s' % (tuple(eps.shape), (B, num, N, D)))
-    with torch.cuda.device(dev):
-        z_pred = torch.empty(B, num, N, D + 2, dtype=torch.float32, device=dev)
-        zstd = torch.empty(B, num, N, D, dtype=torch.float32, device=dev) if want_std else None
-        pred = torch.empty(B, num, N, width.cl, dtype=torch.float32, device=dev) if want_pred else None
-        tail = (B, num, A, N, sd, int(lim_enc), int(elu), *[float(c) for c in consts], stream())
-        if eps is None:
-            width.call('stove_rollout_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(z_pred), ptr(zstd), ptr(pred)), *tail)
-            return z_pred, zstd, pred
-        log_q = torch.empty(B, num, N, D, dtype=torch.float32, device=dev)
-        width.call('stove_rollout_sample_fwd', (ptr(z_last), ptr(extra), ptr(params), ptr(eps), ptr(z_pred), ptr(log_q), ptr(zstd),
-                                                ptr(pred)), *tail)
-    return z_pred, zstd, pred, log_q
+    out = _RolloutFn.apply(_sunk(z_last, sink), extra, image[0], image[1], image[2], eps, width, int(num), lim_enc, elu, consts,
+                           bool(want_std), bool(want_pred), sink)
+    return out[:3] if eps is None else out
 
 
 def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, depth, lim_enc, elu, consts, gamma=0.95,

@@ -342,22 +342,26 @@ class Stove(nn.Module):
         return average_elbo, self.prop_dict, rewards
 
     # ------------------------------------------------------------------ generative rollout
-    def rollout(self, z_last, num=None, sample=False, return_std=False, actions=None, appearance=None):
+    def rollout(self, z_last, num=None, sample=False, return_std=False, actions=None, appearance=None, fused=None):
         """Roll the dynamics forward from z_last (n, o, cl//2+2) with [sx, sy, ...]; scales stay fixed.
         -> z_pred (n, num, o, cl//2+2), rewards   (plus stds for return_std).
         sample=True: every step draws its state from N(mean, std) and the drawn state feeds the next one
         -> z_pred, log_q (n, num, o, cl//2), rewards -- also with return_std (reference stove.py:855-856).
-        With autograd off the whole sampling rollout is one launch (ops.rollout with eps): the draws come from noise_fn, called
-        once per step in order with ('rollout', (n, o, cl//2)), or else as ONE draw of n num o cl//2 normals from the library's
-        generator.  With autograd on it is a host loop of single differentiable steps (Dynamics.forward) -- the fused kernels are
-        forward only, and gradients through sampled futures are what that loop is kept for."""
+        The mean rollout is one launch each way (ops.rollout): with autograd on, z_pred and the rewards carry gradients to z_last, the
+        action embedding, the appearance, the reward head and the dynamics parameters; the stds are returned detached.
+        The sampling rollout in one launch draws from noise_fn, called once per step in order with ('rollout', (n, o, cl//2)), or else
+        ONE draw of n num o cl//2 normals from the library's generator.  `fused`: None -- one launch with autograd off, a host loop of
+        single differentiable steps (Dynamics.forward) with autograd on, as before the one-launch backward existed (it becomes the
+        default under autograd once it has been timed against the loop); True -- one launch forward and one backward under
+        autograd, too, on the draws the no-grad path would make (no gradient reaches the draws); False -- always the loop."""
         c = self.c
         cl = c.cl
         if num is None:
             num = c.num_rollout
         n, o = z_last.shape[:2]
-        fused_sample = sample and not torch.is_grad_enabled()
+        fused_sample = sample and (not torch.is_grad_enabled() if fused is None else bool(fused))
         if not sample or fused_sample:
+            image, sink = self.dyn.kernel_params(0)
             extra = []
             if actions is not None:
                 emb = self.dyn.embed_actions(actions)
@@ -371,14 +375,14 @@ class Stove(nn.Module):
                     eps = torch.stack([self._noise('rollout', (n, o, cl // 2), z_last) for _ in range(num)], 1)
                 else:
                     eps = self._noise_src(z_last.device)
-                z_full, _, pred, log_qs = ops.rollout(z_last, extra, self.dyn.kernel_params(0)[0], num, 2, self.dyn.use_elu,
+                z_full, _, pred, log_qs = ops.rollout(z_last, extra, image, num, 2, self.dyn.use_elu,
                                                       self.dyn.loop_consts(), want_pred=bool(c.action_conditioned), eps=eps,
-                                                      want_logq=True)
+                                                      want_logq=True, sink=sink)
                 rewards = self.dyn.reward_from_pred(pred) if c.action_conditioned else torch.zeros(num)
                 return z_full, log_qs, rewards
-            z_full, z_stds, pred = ops.rollout(z_last, extra, self.dyn.kernel_params(0)[0], num, 2, self.dyn.use_elu,
+            z_full, z_stds, pred = ops.rollout(z_last, extra, image, num, 2, self.dyn.use_elu,
                                               self.dyn.loop_consts(), want_std=return_std,
-                                              want_pred=bool(c.action_conditioned))
+                                              want_pred=bool(c.action_conditioned), sink=sink)
             rewards = self.dyn.reward_from_pred(pred) if c.action_conditioned else torch.zeros(num)
             if return_std:
                 return z_full, z_stds.detach(), rewards
