@@ -351,6 +351,27 @@ int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const in
                       int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
                       float pos_var, float vel_std, float lat_std, float gamma, void* stream);
 
+/* ---- A whole search of M trees with the trees on the device (csrc/plan_tree.hip, csrc/plan_tree.h; the host forest of
+ * stove_amd/mcts/mcts_stove.py is the specification).  Per tree `cap` entries, slot 0 the root: first (first child slot or -1), parent,
+ * depth (key length - 1), Ns, Nsa (M, cap) int32, Qsa (M, cap) double; used (M,) the next free slot; z_pool (M, cap, N, 18) as in
+ * stove_plan_expand.  For i = 0 .. R-1, on `stream`, nothing synchronised and nothing read by the host: select (UCT descent with the
+ * reference's carried best value and action, c = 1; the leaf's child slots -- its own if it has them, else A fresh ones from `used`;
+ * sel_trace[i, m] = leaf if sel_trace is given), the three launches of stove_plan_expand with acts + i M A L (acts (R, M A, L)),
+ * backpropagate of the q they wrote; then action[m] = first-index argmax of Nsa over the root's children (0 for a root without).
+ * min_gap (M,) in/out: lowered to the smallest finite gap between the two best UCT candidates of any level walked.  Qsa equals the host
+ * forest's bit for bit (no contraction; log is the only library call, in the exploration term).
+ * status (M,) in/out: 0 fine; 1 the tree ran out of slots (a fresh leaf with used + A > cap); 2 a walk or index check failed (arrays
+ * or action indices out of range).  A tree with non-zero status is frozen: arrays and pool slots as before the offending iteration
+ * (sel_trace -1 from there on), the other trees unaffected; nothing is read or written out of bounds.  No atomics.
+ * ws: stove_plan_search_ws_bytes() bytes (0 for dimensions the call rejects).  What stove_plan_expand rejects, a NULL array, R < 0:
+ * hipErrorInvalidValue, nothing launched.  R == 0 is valid: only `action` is written (acts may then be NULL). */
+size_t stove_plan_search_ws_bytes(int M, int A, int L, int N, int app_dim);
+int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used,
+                      double* min_gap, int* status, int* action, int* sel_trace, const float* app, const int* acts,
+                      const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, void* ws,
+                      int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                      float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

@@ -89,6 +89,8 @@ def _declare(lib):
         'stove_rollout_bwd_cl': (I, [P] * 12 + [I] * 8 + [F] * 3 + [P]),
         'stove_plan_expand_ws_bytes': (S, [I] * 5),
         'stove_plan_expand': (I, [P] * 14 + [I] * 9 + [F] * 4 + [P]),
+        'stove_plan_search_ws_bytes': (S, [I] * 5),
+        'stove_plan_search': (I, [P] * 19 + [I] * 9 + [F] * 4 + [I, P]),
         'stove_gnn_param_floats_cl': (S, [I]),
         'stove_gnn_grad_floats_cl': (S, [I]),
         'stove_gnn_bwd_ws_bytes_cl': (S, [I, I, I]),

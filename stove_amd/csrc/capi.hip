@@ -36,6 +36,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "head_fused.hip"
 #include "reward_head.hip"
 #include "plan.hip"
+#include "plan_tree.hip"
 
 namespace stove {
 
@@ -165,7 +166,8 @@ extern "C" {
 //    stove_rollout_fwd_cl).
 //    (added since, nothing changed: stove_rollout_sample_fwd, stove_rollout_sample_fwd_cl -- the sampling rollout;
 //     stove_plan_expand_ws_bytes, stove_plan_expand -- one expansion of a batch of search trees;
-//     stove_rollout_bwd_ws_bytes, stove_rollout_bwd and their _cl siblings -- the backward of both rollouts)
+//     stove_rollout_bwd_ws_bytes, stove_rollout_bwd and their _cl siblings -- the backward of both rollouts;
+//     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device)
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1420,11 +1422,11 @@ size_t stove_plan_expand_ws_bytes(int M, int A, int L, int N, int app_dim) {
   return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanWs(M, A, L, N, app_dim).bytes;
 }
 
-int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
-                      const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, float* q, float* r_first,
-                      float* r_roll, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu, float pos_var,
-                      float vel_std, float lat_std, float gamma, void* stream) {
-  STOVE_VALIDATE(plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, ws, M, cap, A, L, D, N, app_dim));
+// the three launches of one expansion (arguments validated by the caller)
+static int plan_expand_launch(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
+                              const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, float* q, float* r_first,
+                              float* r_roll, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                              float pos_var, float vel_std, float lat_std, float gamma, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const PlanWs w(M, A, L, N, app_dim);
   char* base = (char*)ws;
@@ -1442,6 +1444,66 @@ int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const in
   if (rc) return rc;
   STOVE_LAUNCH(plan_finish_k, dim3(reward_head_blocks(rows)), dim3(64 * kRhWaves), 0, st, (const float*)pred, (const float*)z_pred, rh_params,
                (const int*)ok, child, len_s, z_pool, q, r_first, r_roll, rows, cap, A, L, D, N, gamma);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
+                      const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, float* q, float* r_first,
+                      float* r_roll, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu, float pos_var,
+                      float vel_std, float lat_std, float gamma, void* stream) {
+  STOVE_VALIDATE(plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, ws, M, cap, A, L, D, N, app_dim));
+  return plan_expand_launch(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, r_first, r_roll, ws, M, cap, A, L, D, N,
+                            app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
+}
+
+// ---------------------------------------------------------------- planning: a whole search, the trees on the device (plan_tree.hip)
+namespace {
+struct PlanSearchWs {          // the expansion's workspace, then q (M, A), the index vectors select writes and its walk's gap (M,) double
+  size_t q, leaf, child, len_s, gap, bytes;
+  PlanSearchWs(int M, int A, int L, int N, int app_dim) {
+    q = PlanWs(M, A, L, N, app_dim).bytes;
+    leaf = q + align64((size_t)M * A * sizeof(float));
+    child = leaf + align64((size_t)M * sizeof(int));
+    len_s = child + align64((size_t)M * sizeof(int));
+    gap = len_s + align64((size_t)M * sizeof(int));
+    bytes = gap + align64((size_t)M * sizeof(double));
+  }
+};
+}  // namespace
+
+size_t stove_plan_search_ws_bytes(int M, int A, int L, int N, int app_dim) {
+  return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanSearchWs(M, A, L, N, app_dim).bytes;
+}
+
+int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap,
+                      int* status, int* action, int* sel_trace, const float* app, const int* acts, const float* emb_w, const float* emb_b,
+                      const float* gnn_params, const float* rh_params, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim,
+                      int lim_enc, int elu, float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream) {
+  STOVE_VALIDATE(plan_search(z_pool, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, app, acts, emb_w, emb_b, gnn_params,
+                             rh_params, ws, M, cap, A, L, D, N, app_dim, R));
+  hipStream_t st = (hipStream_t)stream;
+  const PlanSearchWs w(M, A, L, N, app_dim);
+  char* base = (char*)ws;
+  float* q = (float*)(base + w.q);
+  int* leaf = (int*)(base + w.leaf);
+  int* child = (int*)(base + w.child);
+  int* len_s = (int*)(base + w.len_s);
+  double* gap = (double*)(base + w.gap);
+  const int* ok = (const int*)(base + PlanWs(M, A, L, N, app_dim).ok);
+  const double c = 1.0;          // the reference's exploration constant (MCTS.c)
+  for (int i = 0; i < R; ++i) {
+    STOVE_LAUNCH(plan_tree_select_k, dim3(M), dim3(64), 0, st, first, parent, depth, Ns, Nsa, Qsa, used, gap, status, leaf, child, len_s,
+                 sel_trace != nullptr ? sel_trace + (size_t)i * M : nullptr, c, cap, A, D);
+    STOVE_LAUNCH_CHECK();
+    const int rc = plan_expand_launch(z_pool, leaf, child, len_s, app, acts + (size_t)i * M * A * L, emb_w, emb_b, gnn_params, rh_params, q, nullptr,
+                                      nullptr, ws, M, cap, A, L, D, N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
+    if (rc) return rc;
+    STOVE_LAUNCH(plan_tree_backprop_k, dim3(M), dim3(64), 0, st, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, (const int*)leaf,
+                 (const int*)child, (const double*)gap, (const float*)q, ok, cap, A, D);
+    STOVE_LAUNCH_CHECK();
+  }
+  STOVE_LAUNCH(plan_tree_action_k, dim3((M + 63) / 64), dim3(64), 0, st, first, Nsa, action, M, cap, A);
   STOVE_LAUNCH_CHECK();
   return 0;
 }

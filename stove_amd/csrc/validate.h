@@ -213,6 +213,21 @@ inline int plan_expand(const float* z_pool, const int* leaf, const int* child, c
   return 0;
 }
 
+// ---- stove_plan_search: R iterations of select / expand / backpropagate on device-resident trees (csrc/plan_tree.hip).  What
+// plan_expand rejects, plus the tree arrays; sel_trace is optional, R == 0 a valid call (only `action` is written; acts may be NULL).  The arrays'
+// contents are device memory and are checked by the kernels (status).
+inline int plan_search(const float* z_pool, const int* first, const int* parent, const int* depth, const int* Ns, const int* Nsa,
+                       const double* Qsa, const int* used, const double* min_gap, const int* status, const int* action, const float* app,
+                       const int* acts, const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params,
+                       const void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int R) {
+  if (plan_dims_bad(M, A, L, N, app_dim) || D < 1 || cap < 1 + A || R < 0) return kStoveInvalidValue;
+  if (null_any(z_pool, emb_w, emb_b, gnn_params, rh_params) || null_any(first, parent, depth, Ns, Nsa, used, status, action) ||
+      null_any(Qsa, min_gap) || ws == nullptr || (R > 0 && acts == nullptr))
+    return kStoveInvalidValue;
+  if (app_dim > 0 && app == nullptr) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

@@ -8,7 +8,8 @@ value).  The node states live in a pool tensor (M, cap, N, 18): slot 0 is the ro
 `MCTS` stays the per-tree handle: `tree.Nsa['r3']`, `tree.Qsa`, `tree.Ns`, `tree.Zstate` read the forest by the reference's keys.
 
 `BatchedMCTSHandler.run_mcts` expands with one `ops.plan_expand` call per iteration (fused=True: the states never leave the device)
-or with the reference's sequence of calls on `Stove.rollout` (fused=False)."""
+or with the reference's sequence of calls on `Stove.rollout` (fused=False).  With `handler.device_trees = True` the forest itself goes to the device
+for the length of the search (`Forest.to_device`, one `ops.plan_search` call for all iterations, `Forest.from_device`)."""
 import time
 
 import numpy as np
@@ -16,8 +17,8 @@ import torch
 
 GAMMA = 0.95
 # What run_mcts(fused=None) takes on a model the fused expansion serves (cl = 32, float32, on the GPU, fused reward head).  The fused
-# path may be the default only where tools/plan_bench.py has shown it faster than the composed one beyond the run-to-run spread; no
-# such measurement has been recorded yet, so the composed path is.
+# path may be the default only where tools/plan_bench.py has shown it faster than the composed one beyond the run-to-run spread.
+# profiles/plan_bench.json records 1.10 against 3.68 ms per expansion; the default is the composed path all the same.
 FUSED_WHERE_ELIGIBLE = False
 
 
@@ -115,6 +116,34 @@ class Forest:
                 out.z[row:row + f.M, :f.z.shape[1]] = f.z.to(dev)
                 row += f.M
         return out
+
+    # -------------------------------------------------------------------------------------------- the trees on the device
+    def to_device(self, dev):
+        """-> dict of device tensors for ops.plan_search: the arrays as int32 (Qsa float64), used and a zero status (M,) int32, and
+        min_gap (M,) float64 at +inf (the search lowers it per tree)"""
+        out = {}
+        for name in self._ARRAYS + ('used',):
+            a = getattr(self, name)
+            if name != 'Qsa':
+                if a.size and (a.max() > np.iinfo(np.int32).max or a.min() < np.iinfo(np.int32).min):
+                    raise ValueError('Forest.to_device: %s does not fit int32' % name)
+                a = a.astype(np.int32)
+            out[name] = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        out['status'] = torch.zeros(self.M, dtype=torch.int32, device=dev)
+        out['min_gap'] = torch.full((self.M,), float('inf'), dtype=torch.float64, device=dev)
+        return out
+
+    def from_device(self, tensors):
+        """the arrays of `to_device` after a search, back into this forest (int64 / float64 numpy); min_gap merged with min"""
+        for name in self._ARRAYS + ('used',):
+            a = tensors[name].cpu().numpy()
+            want = (self.M, self.cap) if name != 'used' else (self.M,)
+            if a.shape != want:
+                raise ValueError('Forest.from_device: %s is %s, this forest holds %s' % (name, a.shape, want))
+            setattr(self, name, a.astype(np.float64 if name == 'Qsa' else np.int64))
+        gaps = tensors['min_gap'].cpu().numpy()
+        if gaps.size:
+            self.min_gap = min(self.min_gap, float(gaps.min()))
 
     # -------------------------------------------------------------------------------------------- the reference's select
     def select(self, start=None):
@@ -316,6 +345,7 @@ class BatchedMCTSHandler():
         for m, t in enumerate(trees):
             t._f, t._m = self.forest, m
         self.timing = {'host': 0.0, 'device': 0.0}        # seconds of the last run_mcts: tree arithmetic / waiting for the model
+        self.device_trees = False      # True: run_mcts keeps the trees on the device too, one ops.plan_search call per search
 
     def _fused_default(self, env):
         c = env.c
@@ -329,7 +359,20 @@ class BatchedMCTSHandler():
         go up and q (M, A) comes down; False -- the reference's sequence of calls on Stove.rollout; None -- fused where the model is
         cl = 32, float32, on the GPU with its fused reward head and the fused path was measured faster (FUSED_WHERE_ELIGIBLE), else composed.
         rollout_actions: (runs_per_round, M A, 2 D) action indices of the random rollouts; None draws them as the reference does, one
-        np.random.randint(A, size=(A M 2 D,)) per iteration (drawn ahead of the loop, in that order: the loop draws nothing else)."""
+        np.random.randint(A, size=(A M 2 D,)) per iteration (drawn ahead of the loop, in that order: the loop draws nothing else).
+        self.device_trees (an attribute of the handler, False by default; this method's parameters are the reference's plus `fused`
+        and `rollout_actions` and stay so): True -- the trees go to the device too and all iterations are ONE ops.plan_search call (select and backpropagate
+        as kernels around the fused expansion's launches, nothing synchronised in between); the forest is uploaded before and
+        downloaded after, so it reads as if searched on the host.  Implies the fused expansion; a model that one does not serve is a
+        ValueError."""
+        device_trees = bool(self.device_trees)
+        if device_trees:
+            if fused is False:
+                raise ValueError('device_trees = True searches on the fused expansion: fused=False contradicts it')
+            why = self._fused_unserved(env)
+            if why:
+                raise ValueError('device_trees=True needs the fused expansion, which does not serve this model: ' + why)
+            fused = True
         if fused is None:
             fused = self._fused_default(env)
         if not env.c.action_conditioned:
@@ -344,6 +387,8 @@ class BatchedMCTSHandler():
         f.reserve(int(f.used.max()) + A * runs_per_round)
         f.z = f.z.to(dev).float().contiguous()
         app = self.obj_app.to(dev).float().contiguous() if self.obj_app is not None else None
+        if device_trees:
+            return self._search_on_device(env, acts_all, app)
         expand = self._expand_fused(env, acts_all, app) if fused else self._expand_composed(env, acts_all, app)
         host = device = 0.0
         with torch.no_grad():
@@ -361,15 +406,59 @@ class BatchedMCTSHandler():
         self.timing = {'host': host, 'device': device}
         return [int(np.argmax(f.Nsa[m, f.first[m, 0]:f.first[m, 0] + A])) if f.first[m, 0] >= 0 else 0 for m in range(M)]
 
-    def _expand_fused(self, env, acts_all, app):
+    @staticmethod
+    def _fused_unserved(env):
+        """why the fused expansion (stove_plan_expand) does not serve `env`, or '' if it does"""
+        c = env.c
+        p = next(env.parameters())
+        if not p.is_cuda:
+            return 'it is not on the GPU'
+        if p.dtype != torch.float32:
+            return 'its parameters are %s, not float32' % p.dtype
+        if c.cl != 32:
+            return 'its state code length is %d, not 32' % c.cl
+        return ''
+
+    @staticmethod
+    def _fused_weights(env):
+        """what stove_plan_expand reads of the model: embedding, GNN image, reward-head block"""
         from .. import ops
-        dyn, f = env.dyn, self.forest
-        dev = f.z.device
+        dyn = env.dyn
         lay, h0, h1 = dyn.action_embedding_layer, dyn.reward_head0, dyn.reward_head1
         gnn = ops.gnn_width(32).image(*[t.detach() if t is not None else None for t in dyn.kernel_params(0)[0]]).contiguous()
         rh = torch.cat([p.detach().float().reshape(-1) for p in (h0[0].weight, h0[0].bias, h0[2].weight, h0[2].bias, h1[0].weight, h1[0].bias,
                                                                   h1[2].weight, h1[2].bias, h1[4].weight, h1[4].bias)])
-        emb_w, emb_b = lay.weight.detach().float().contiguous(), lay.bias.detach().float().contiguous()
+        return lay.weight.detach().float().contiguous(), lay.bias.detach().float().contiguous(), gnn, rh
+
+    def _search_on_device(self, env, acts_all, app):
+        """all iterations in one ops.plan_search call: forest up, search, forest down -> the actions"""
+        from .. import ops
+        dyn, f = env.dyn, self.forest
+        dev = f.z.device
+        if f.c != 1.0:
+            raise ValueError('the device search runs the reference\'s exploration constant c = 1, this forest has c = %r' % f.c)
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            emb_w, emb_b, gnn, rh = self._fused_weights(env)
+            acts = torch.from_numpy(acts_all.astype(np.int32)).to(dev)
+            arrays = f.to_device(dev)
+            action = ops.plan_search(f.z, arrays, app, acts, emb_w, emb_b, gnn, rh, self.max_rollout, 2, dyn.use_elu, dyn.loop_consts(), GAMMA)
+            status = arrays['status'].cpu().numpy()
+            action = action.cpu().numpy()
+        if status.any():
+            m = int(np.flatnonzero(status)[0])
+            raise RuntimeError('device search: tree %d stopped with status %d (%s); the host arrays are as before the search, the state '
+                               'pool is not: the iterations that ran have written child states into it' % (
+                                   m, status[m], {1: 'out of slots', 2: 'an index check failed'}.get(int(status[m]), 'unknown')))
+        f.from_device(arrays)
+        self.timing = {'host': 0.0, 'device': time.perf_counter() - t0}
+        return [int(a) for a in action]
+
+    def _expand_fused(self, env, acts_all, app):
+        from .. import ops
+        dyn, f = env.dyn, self.forest
+        dev = f.z.device
+        emb_w, emb_b, gnn, rh = self._fused_weights(env)
         acts = torch.from_numpy(acts_all.astype(np.int32)).to(dev)                    # every iteration's actions, one upload
         consts, elu = dyn.loop_consts(), dyn.use_elu
 
@@ -424,6 +513,12 @@ def update_buffer(img, new_img, action, new_action):
 def run_mcts_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10):
     """img (envs, time, width, height, channels): the last frames of every environment; actions (envs, time, 9) one-hot: the actions
     taken -> the next action of every environment, by `mcts_steps` expansions per tree on `model`."""
+    return plan_on_model(img, model, actions, num_parallel_envs, mcts_steps, max_rollout_depth)
+
+
+def plan_on_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False):
+    """run_mcts_model (the reference's surface, whose parameter list stays the reference's) with the search's switches as arguments:
+    `fused` as BatchedMCTSHandler.run_mcts takes it, `device_trees` as the handler's attribute of that name."""
     dev = next(model.parameters()).device
     with torch.no_grad():
         _, prop_dict, _ = model(encode_img(img).to(dev), 0, actions=actions.to(dev), pretrain=False)
@@ -432,5 +527,6 @@ def run_mcts_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, m
                          max_rollout_depth=max_rollout_depth) for env in range(num_parallel_envs)]
         mcts = BatchedMCTSHandler(all_mcts, apps[:, -1] if apps is not None else None, action_space=9,
                                   max_rollout_depth=max_rollout_depth)
-        all_actions = mcts.run_mcts(model, mcts_steps)
+        mcts.device_trees = device_trees
+        all_actions = mcts.run_mcts(model, mcts_steps, fused=fused)
     return all_actions

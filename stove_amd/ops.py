@@ -916,6 +916,51 @@ def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params,
     return (q, r_first, r_roll) if want_rewards else q
 
 
+def plan_search(z_pool, arrays, app, acts, emb_w, emb_b, gnn_params, rh_params, depth, lim_enc, elu, consts, gamma=0.95, sel_trace=None):
+    """A whole search of M trees with the trees on the device (stove_plan_search, csrc/plan_tree.hip; forward only): acts.shape[0]
+    iterations of select / expand / backpropagate in one C call, nothing synchronised.  z_pool (M, cap, N, 18) float32 and the trees
+    are updated in place.  arrays: dict of contiguous device tensors -- first, parent, depth, Ns, Nsa (M, cap) int32, Qsa (M, cap)
+    float64, used, status (M,) int32, min_gap (M,) float64 (Forest.to_device makes them).  acts (R, M A, L) int32, every iteration's
+    random-rollout actions; sel_trace (R, M) int32 or None receives the selected leaf per iteration; the rest as ops.plan_expand.
+    -> action (M,) int32: the first-index argmax of the root's visit counts.  status[m] != 0 afterwards: tree m was frozen (1 out of
+    slots, 2 an index check failed)."""
+    tensors = (z_pool, app, emb_w, emb_b, gnn_params, rh_params)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError('ops.plan_search is forward only: call it under torch.no_grad() or with detached inputs')
+    lib = _lib.load()
+    z_pool, app, emb_w, emb_b, gnn_params, rh_params = [_f32(t) for t in tensors]
+    if z_pool.data_ptr() != tensors[0].data_ptr():
+        raise RuntimeError('ops.plan_search writes the child states into z_pool: it must be contiguous')
+    if z_pool.dim() != 4 or acts.dim() != 3:
+        raise ValueError('ops.plan_search: z_pool must be (M, cap, N, 18) and acts (R, M A, L)')
+    M, cap, N = z_pool.shape[:3]
+    A = emb_w.shape[1]
+    R, L = acts.shape[0], acts.shape[-1]
+    app_dim = app.shape[-1] if app is not None else 0
+    dev = z_pool.device
+    ints = [('acts', acts, None)] + [(k, arrays[k], (M, cap)) for k in ('first', 'parent', 'depth', 'Ns', 'Nsa')] + \
+        [(k, arrays[k], (M,)) for k in ('used', 'status')] + ([('sel_trace', sel_trace, (R, M))] if sel_trace is not None else [])
+    for name, t, shape in ints + [('Qsa', arrays['Qsa'], (M, cap)), ('min_gap', arrays['min_gap'], (M,))]:
+        want = torch.float64 if name in ('Qsa', 'min_gap') else torch.int32
+        if t.dtype != want or t.device != dev or not t.is_contiguous():
+            raise RuntimeError('ops.plan_search: %s must be a contiguous %s tensor on %s' % (name, str(want).split('.')[-1], dev))
+        if shape is not None and tuple(t.shape) != shape:
+            raise ValueError('ops.plan_search: %s is %s, the forest needs %s' % (name, tuple(t.shape), shape))
+    if (z_pool.shape[3] != 18 or tuple(emb_w.shape) != (4 * N, A) or emb_b.numel() != 4 * N or tuple(acts.shape) != (R, M * A, L)
+            or (app is not None and tuple(app.shape) != (M, N, app_dim))
+            or gnn_params.numel() != lib.stove_gnn_param_floats() or rh_params.numel() != lib.stove_reward_head_param_floats()):
+        raise ValueError('ops.plan_search: argument shapes do not fit M = %d trees, N = %d objects, A = %d actions, L = %d' % (M, N, A, L))
+    a = arrays
+    with torch.cuda.device(dev):
+        action = torch.empty(M, dtype=torch.int32, device=dev)
+        ws = _ws(lib.stove_plan_search_ws_bytes(M, A, L, N, app_dim), dev)
+        check(lib.stove_plan_search(ptr(z_pool), ptr(a['first']), ptr(a['parent']), ptr(a['depth']), ptr(a['Ns']), ptr(a['Nsa']), ptr(a['Qsa']),
+                                    ptr(a['used']), ptr(a['min_gap']), ptr(a['status']), ptr(action), ptr(sel_trace), ptr(app), ptr(acts),
+                                    ptr(emb_w), ptr(emb_b), ptr(gnn_params), ptr(rh_params), ptr(ws), M, cap, A, L, int(depth), N, app_dim,
+                                    int(lim_enc), int(elu), *[float(c) for c in consts], float(gamma), R, stream()), 'stove_plan_search')
+    return action
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 

@@ -1,0 +1,397 @@
+"""GPU tests of the device-resident tree search (stove_plan_search, csrc/plan_tree.hip; ops.plan_search, run_mcts on a handler with device_trees = True)
+against the host forest searching on the same expansion kernel: decisions, integer arrays, Qsa and the state pool bit for bit.
+Shapes and inputs of tests/test_gpu_plan.py: configuration 'ac3', M = 3 trees, A = 9, N = 3, app_dim = 3; the model (init weights),
+root states (generator seed 42) and numpy seed (9) of test_fused_search_equals_composed_search.  The two sides run the same kernels on
+the same inputs in the same order, so q is identical; only `log` in the exploration term may differ between the device library and
+numpy, by an ulp or so.  Every test that compares decisions therefore first asserts the HOST forest's smallest decision gap >= 1e-9
+(a condition on the inputs, far above what one ulp of log can move u; not a tolerance on the result)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_dynamics import make_cfg
+from test_gpu_plan import A, CFG, DEV, GAMMA, N, _inputs, _model, _weights
+
+pytestmark = pytest.mark.gpu
+INT_ARRAYS = ('first', 'parent', 'depth', 'Ns', 'Nsa')
+SEED = 9
+MIN_GAP = 1e-9
+
+
+def _roots(variant='same'):
+    """(z, app) of three trees: the first three roots of test_fused_search_equals_composed_search; 'twins': trees 0 and 2 the same
+    root, tree 1 another; 'twins2': the same twins around yet another tree 1; 'one': the first root alone"""
+    z, app, _ = _inputs(6, trees=4, seed=42)
+    pick = {'same': [0, 1, 2], 'twins': [0, 1, 0], 'twins2': [0, 3, 0], 'one': [0]}[variant]
+    return z[pick].clone(), app[pick].clone()
+
+
+@functools.lru_cache(maxsize=None)
+def _actions(R, M, D, variant='same'):
+    """(R, M A, 2 D) random-rollout actions drawn as run_mcts draws them, numpy seed 9 (shared, never modified)"""
+    rs = np.random.RandomState(SEED)
+    acts = np.stack([rs.randint(A, size=(A * M * D * 2,)) for _ in range(R)]).reshape(R, M, A, 2 * D) if R else np.zeros((0, M, A, 2 * D), dtype=np.int64)
+    if variant.startswith('twins'):
+        acts[:, 2] = acts[:, 0]
+        if variant == 'twins2':
+            acts[:, 1] = acts[::-1, 1]
+    return acts.reshape(R, M * A, 2 * D)
+
+
+def _handler(D, variant='same', device_trees=False):
+    from stove_amd.mcts.mcts_stove import MCTS, BatchedMCTSHandler
+    z, app = _roots(variant)
+    trees = [MCTS(app[m:m + 1], z[m:m + 1], action_space=A, max_rollout_depth=D) for m in range(z.shape[0])]
+    h = BatchedMCTSHandler(trees, app, action_space=A, max_rollout_depth=D)
+    assert h.device_trees is False                    # the default
+    h.device_trees = device_trees
+    return h, trees
+
+
+def _host_search(D, R, variant='same', acts=None):
+    """run_mcts(fused=True) with the leaf of every iteration recorded -> (handler, trees, actions, leaves (R, M))"""
+    h, trees = _handler(D, variant)
+    leaves, select = [], h.forest.select
+
+    def recording_select():
+        leaf = select()
+        leaves.append(leaf.copy())
+        return leaf
+    h.forest.select = recording_select
+    acts = _actions(R, h.num_mcts, D, variant) if acts is None else acts
+    actions = h.run_mcts(_model('init'), R, fused=True, rollout_actions=acts)
+    assert h.forest.min_gap >= MIN_GAP, h.forest.min_gap
+    return h, trees, actions, np.stack(leaves) if leaves else np.zeros((0, h.num_mcts), dtype=np.int64)
+
+
+def _guarded(values, guard, fill):
+    """a contiguous device copy of `values` with `guard` elements of `fill` in front of and behind it -> (view, whole buffer)"""
+    flat = values.reshape(-1)
+    buf = torch.full((flat.numel() + 2 * guard,), fill, dtype=values.dtype)
+    buf[guard:guard + flat.numel()] = flat
+    buf = buf.to(DEV)
+    return buf[guard:guard + flat.numel()].view(values.shape), buf
+
+
+def _direct(D, acts, variant='same', cap=None, used0=None, guard=0, trace=True, damage=None):
+    """ops.plan_search on fresh trees -> dict(action, sel, pool, arrays..., buffers): everything on the host after one synchronise.
+    guard > 0: the pool and every array sit inside larger buffers filled with NaN / a sentinel, returned under 'buffers'.
+    damage: called with the fresh host forest before it is uploaded."""
+    from stove_amd import ops
+    from stove_amd.mcts.mcts_stove import Forest
+    st = _model('init')
+    z, app = _roots(variant)
+    M, R = z.shape[0], acts.shape[0]
+    cap = 1 + A * max(R, 1) if cap is None else cap
+    f = Forest(M, A, D, cap=cap)
+    if used0 is not None:
+        f.used = np.asarray(used0, dtype=np.int64)
+    if damage is not None:
+        damage(f)
+    pool = torch.zeros(M, cap, N, 18)
+    pool[:, 0] = z
+    pool, pool_buf = _guarded(pool, guard * N * 18, float('nan'))
+    arrays, buffers = {}, {'pool': pool_buf}
+    for k, t in f.to_device('cpu').items():
+        arrays[k], buffers[k] = _guarded(t, guard, float('nan') if t.dtype == torch.float64 else -77)
+    sel, buffers['sel'] = _guarded(torch.full((R, M), -5, dtype=torch.int32), guard, -77) if trace else (None, None)
+    emb_w, emb_b, gnn, rh = _weights(st)
+    with torch.no_grad():
+        action = ops.plan_search(pool, arrays, app.to(DEV), torch.from_numpy(acts.astype(np.int32)).to(DEV), emb_w, emb_b, gnn, rh, D, 2,
+                                 st.dyn.use_elu, st.dyn.loop_consts(), GAMMA, sel_trace=sel)
+    torch.cuda.synchronize()
+    out = {k: v.cpu().numpy() for k, v in arrays.items()}
+    out.update(action=action.cpu().numpy(), sel=sel.cpu().numpy() if trace else None, pool=pool.cpu(), guard=guard,
+               buffers={k: v.cpu() for k, v in buffers.items() if v is not None})
+    return out
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _same_outputs(a, b, trees=None, cap=None):
+    """two _direct results agree bit for bit on `trees` (all) over the first `cap` slots (all)"""
+    rows = list(range(a['first'].shape[0])) if trees is None else list(trees)
+    cap = min(a['first'].shape[1], b['first'].shape[1]) if cap is None else cap
+    for k in INT_ARRAYS:
+        assert np.array_equal(a[k][rows, :cap], b[k][rows, :cap]), k
+    assert np.array_equal(a['Qsa'][rows, :cap].view(np.int64), b['Qsa'][rows, :cap].view(np.int64))
+    assert np.array_equal(a['used'][rows], b['used'][rows]) and np.array_equal(a['status'][rows], b['status'][rows])
+    assert np.array_equal(a['action'][rows], b['action'][rows])
+    assert torch.equal(_bits(a['pool'][rows, :cap]), _bits(b['pool'][rows, :cap]))
+
+
+def _same_as_forest(out, f, cap=None, pool=None):
+    """device arrays (dict of numpy) against the host forest: integers equal, Qsa bit for bit, the pool bit for bit"""
+    cap = min(out['first'].shape[1], f.cap) if cap is None else cap
+    for k in INT_ARRAYS:
+        assert np.array_equal(out[k][:, :cap], getattr(f, k)[:, :cap]), k
+    assert np.array_equal(out['used'], f.used)
+    assert np.array_equal(np.ascontiguousarray(out['Qsa'][:, :cap]).view(np.int64), np.ascontiguousarray(f.Qsa[:, :cap]).view(np.int64))
+    if pool is not None:
+        assert torch.equal(_bits(pool[:, :cap].cpu()), _bits(f.z[:, :cap].cpu()))
+
+
+def _forest_arrays(f):
+    out = {k: getattr(f, k) for k in INT_ARRAYS + ('Qsa', 'used')}
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ 1. device search = host search
+# D = 2: every child of the root is a final leaf, re-expanded and overwritten from the third iteration on; D = 5: the tree grows
+# over several levels (the carried cur_best / best_act)
+@pytest.mark.parametrize('D,R', [(2, 12), (5, 40)])
+def test_device_search_equals_host_search(D, R):
+    host, _, act_h, leaves = _host_search(D, R)
+    dev, _ = _handler(D, device_trees=True)
+    act_d = dev.run_mcts(_model('init'), R, fused=True, rollout_actions=_actions(R, 3, D))
+    print(f'plan_search D={D} R={R}: host min_gap {host.forest.min_gap:.3g} device {dev.forest.min_gap:.3g}; actions {act_h} {act_d}; '
+          f'used {host.forest.used.tolist()}')
+    assert act_d == act_h
+    assert dev.forest.cap == host.forest.cap
+    _same_as_forest(_forest_arrays(dev.forest), host.forest, pool=dev.forest.z)
+    assert abs(dev.forest.min_gap - host.forest.min_gap) <= 1e-12
+    assert set(dev.timing) == {'host', 'device'} and dev.timing['device'] > 0
+    if D == 2:            # the re-expansion path ran: fewer slots than one fresh expansion per iteration would take
+        assert host.forest.used.max() < 1 + A * R
+    out = _direct(D, _actions(R, 3, D), cap=host.forest.cap)
+    assert np.array_equal(out['sel'], leaves)
+    assert not out['status'].any()
+    _same_as_forest(out, host.forest, pool=out['pool'])
+    assert out['action'].tolist() == act_h
+    assert abs(float(out['min_gap'].min()) - host.forest.min_gap) <= 1e-12
+
+
+# ------------------------------------------------------------------------------------------------ 2. one tree; trees that diverge
+def test_a_forest_of_one():
+    D, R = 3, 10
+    host, _, act_h, leaves = _host_search(D, R, 'one')
+    dev, _ = _handler(D, 'one', device_trees=True)
+    act_d = dev.run_mcts(_model('init'), R, rollout_actions=_actions(R, 1, D, 'one'))
+    assert act_d == act_h
+    _same_as_forest(_forest_arrays(dev.forest), host.forest, pool=dev.forest.z)
+
+
+def test_trees_do_not_affect_each_other():
+    """trees 0 and 2: the same root and the same actions, around a tree 1 of its own -> identical to each other, and the same whatever
+    tree 1 is"""
+    D, R = 3, 10
+    _host_search(D, R, 'twins')                      # (the decision-gap condition on these inputs)
+    a = _direct(D, _actions(R, 3, D, 'twins'), 'twins')
+    b = _direct(D, _actions(R, 3, D, 'twins2'), 'twins2')
+    assert not a['status'].any() and not b['status'].any()
+    for k in INT_ARRAYS + ('Qsa', 'sel'):
+        assert np.array_equal(a[k][..., 0, :] if k != 'sel' else a[k][:, 0], a[k][..., 2, :] if k != 'sel' else a[k][:, 2]), k
+    assert torch.equal(_bits(a['pool'][0]), _bits(a['pool'][2]))
+    _same_outputs(a, b, trees=(0, 2))
+    assert not np.array_equal(a['Qsa'][1], b['Qsa'][1])
+
+
+# ------------------------------------------------------------------------------------------------ 3. reproducible, forward only, R = 0
+def test_reproducible_forward_only_and_empty():
+    from stove_amd import ops
+    D, R = 3, 10
+    acts = _actions(R, 3, D)
+    a, b = _direct(D, acts), _direct(D, acts)
+    _same_outputs(a, b)
+    assert np.array_equal(a['sel'], b['sel']) and np.array_equal(a['min_gap'].view(np.int64), b['min_gap'].view(np.int64))
+    st = _model('init')
+    z, app = _roots()
+    emb_w, emb_b, gnn, rh = _weights(st)
+    from stove_amd.mcts.mcts_stove import Forest
+    pool = torch.zeros(3, 1 + A, N, 18, device=DEV)
+    with pytest.raises(RuntimeError, match='forward only'):
+        ops.plan_search(pool, Forest(3, A, D).to_device(DEV), app.to(DEV).requires_grad_(), torch.from_numpy(acts.astype(np.int32)).to(DEV), emb_w,
+                        emb_b, gnn, rh, D, 2, st.dyn.use_elu, st.dyn.loop_consts())
+    e = _direct(D, _actions(0, 3, D), guard=64)
+    assert e['action'].tolist() == [0, 0, 0]                     # a root without children
+    fresh = Forest(3, A, D, cap=1 + A)
+    _same_as_forest(e, fresh)
+    want = torch.zeros(3, 1 + A, N, 18)
+    want[:, 0] = z
+    assert torch.equal(_bits(e['pool']), _bits(want))
+    assert not e['status'].any() and bool(np.isinf(e['min_gap']).all())
+
+
+# ------------------------------------------------------------------------------------------------ 4. out of slots on the device
+def _margins_intact(out):
+    g = out['guard']
+    for k, buf in out['buffers'].items():
+        gg = g * N * 18 if k == 'pool' else g
+        for edge in (buf[:gg], buf[-gg:]):
+            if buf.dtype.is_floating_point:
+                assert bool(torch.isnan(edge).all()), k
+            else:
+                assert bool((edge == -77).all()), k
+
+
+def test_a_tree_out_of_slots_on_the_device():
+    """Tree 1's slot cursor starts two expansions ahead and cap is one slot short of what it needs in the end, which still holds trees
+    0 and 2: status [0, 1, 0], tree 1 as before the iteration that found no room, trees 0 and 2 as with room for all, nothing written
+    outside the arrays."""
+    D, R = 5, 12
+    acts = _actions(R, 3, D)
+    _host_search(D, R)                               # (the decision-gap condition on these inputs; used0 does not enter a decision)
+    used0 = (1, 1 + 2 * A, 1)
+    ample = _direct(D, acts, cap=1 + A * (R + 2), used0=used0, guard=64)
+    assert not ample['status'].any()
+    cap = int(ample['used'][1]) - 1
+    assert cap >= max(ample['used'][0], ample['used'][2])                     # the premise: only tree 1 is short
+    short = _direct(D, acts, cap=cap, used0=used0, guard=64)
+    assert short['status'].tolist() == [0, 1, 0]
+    stop = int(np.flatnonzero(short['sel'][:, 1] < 0)[0])
+    assert stop > 0 and (short['sel'][stop:, 1] == -1).all() and np.array_equal(short['sel'][:stop, 1], ample['sel'][:stop, 1])
+    before = _direct(D, acts[:stop], cap=cap, used0=used0)
+    for k in INT_ARRAYS + ('Qsa', 'used'):
+        assert np.array_equal(short[k][1], before[k][1]), k
+    assert torch.equal(_bits(short['pool'][1]), _bits(before['pool'][1]))
+    _same_outputs(short, ample, trees=(0, 2), cap=cap)
+    assert np.array_equal(short['sel'][:, [0, 2]], ample['sel'][:, [0, 2]])
+    _margins_intact(short)
+    _margins_intact(ample)
+    # through run_mcts the condition cannot arise: it reserves one expansion per iteration up front
+    h, _ = _handler(D, device_trees=True)
+    h.run_mcts(_model('init'), 2, rollout_actions=acts[:2])
+    assert h.forest.cap >= 1 + A * 2 and h.forest.z.shape[1] == h.forest.cap
+
+
+def test_status_two_on_the_device():
+    """Tree 1 fails an index check: (a) one of its random actions at iteration 3 is A, which plan_prep_k flags after select has
+    allocated the tree's slots -- plan_tree_backprop_k gives them back; (b) its root's children lie outside the arrays, which select
+    finds itself.  Status [0, 2, 0]; tree 1's arrays, used, min_gap and pool rows as before the offending iteration; trees 0 and 2 as
+    in the clean run; nothing written outside the arrays."""
+    D, R, at = 5, 6, 3
+    acts = _actions(R, 3, D)
+    _host_search(D, R)                               # (the decision-gap condition on these inputs)
+    clean = _direct(D, acts, guard=64)
+    assert not clean['status'].any()
+    bad_acts = acts.copy()
+    bad_acts[at, 1 * A + 4, 2] = A
+    out = _direct(D, bad_acts, guard=64)
+    before = _direct(D, acts[:at], cap=1 + A * R)
+    assert out['status'].tolist() == [0, 2, 0]
+    assert (out['sel'][at + 1:, 1] == -1).all() and np.array_equal(out['sel'][:at + 1, 1], clean['sel'][:at + 1, 1])
+    for k in INT_ARRAYS + ('Qsa', 'used', 'min_gap'):
+        assert np.array_equal(out[k][1], before[k][1]), k
+    assert clean['used'][1] > before['used'][1]                                # (the offending iteration had allocated fresh slots)
+    assert torch.equal(_bits(out['pool'][1]), _bits(before['pool'][1]))
+    _same_outputs(out, clean, trees=(0, 2))
+    assert np.array_equal(out['min_gap'][[0, 2]], clean['min_gap'][[0, 2]])
+    _margins_intact(out)
+
+    def damage(f):
+        f.first[1, 0] = f.cap + 100
+    fresh = _direct(D, acts[:0], cap=1 + A * R)
+    out = _direct(D, acts, guard=64, damage=damage)
+    assert out['status'].tolist() == [0, 2, 0] and (out['sel'][:, 1] == -1).all() and out['action'][1] == 0
+    assert out['first'][1, 0] == out['first'].shape[1] + 100
+    for k in ('parent', 'depth', 'Ns', 'Nsa', 'Qsa', 'used', 'min_gap'):
+        assert np.array_equal(out[k][1], fresh[k][1]), k
+    assert (out['first'][1, 1:] == -1).all()
+    assert torch.equal(_bits(out['pool'][1]), _bits(fresh['pool'][1]))
+    _same_outputs(out, clean, trees=(0, 2))
+    _margins_intact(out)
+
+
+# ------------------------------------------------------------------------------------------------ 5. search after search
+def test_search_after_search():
+    D, R = 5, 12
+    acts = _actions(R, 3, D)
+    host, host_trees, act_h, _ = _host_search(D, R)
+    dev, trees = _handler(D, device_trees=True)
+    dev.run_mcts(_model('init'), 6, rollout_actions=acts[:6])
+    act_d = dev.run_mcts(_model('init'), 6, rollout_actions=acts[6:])
+    assert act_d == act_h
+    cap = int(host.forest.used.max())
+    _same_as_forest(_forest_arrays(dev.forest), host.forest, cap=cap, pool=dev.forest.z)
+    assert abs(dev.forest.min_gap - host.forest.min_gap) <= 1e-12
+    for t, ht in zip(trees, host_trees):
+        assert sorted(t.Qsa.keys()) == sorted(ht.Qsa.keys())
+        key = 'r' + str(act_h[0])
+        assert t.Nsa[key] == ht.Nsa[key] and t.Qsa[key] == ht.Qsa[key] and t.Ns['r'] == ht.Ns['r'] == R
+        assert torch.equal(t.Zstate[key], ht.Zstate[key])
+
+
+# ------------------------------------------------------------------------------------------------ 6. run_mcts_model
+def test_plan_on_model_with_device_trees():
+    from stove_amd.envs import envs
+    from stove_amd.mcts.mcts_stove import MCTS, BatchedMCTSHandler, encode_img, initialize_img, plan_on_model
+    from stove_amd.video_prediction.stove import Stove
+    torch.manual_seed(0)
+    model = Stove(make_cfg(**CFG)).to(DEV)
+    tasks = [envs.AvoidanceTask(envs.make_env('avoidance', 100 + i, 32), 4, greyscale=False, action_force=0.6) for i in range(3)]
+    img, actions = initialize_img(tasks, steps=8, res=32)
+    # the decision-gap condition, on a handler built as run_mcts_model builds its own
+    with torch.no_grad():
+        _, prop, _ = model(encode_img(img).to(DEV), 0, actions=actions.to(DEV), pretrain=False)
+    apps = prop['obj_appearances']
+    h = BatchedMCTSHandler([MCTS(apps[e:e + 1, -1], prop['z'][e:e + 1, -1], max_rollout_depth=3) for e in range(3)], apps[:, -1],
+                           action_space=9, max_rollout_depth=3)
+    np.random.seed(1)
+    want = h.run_mcts(model, 8, fused=True)
+    assert h.forest.min_gap >= MIN_GAP, h.forest.min_gap
+    np.random.seed(1)
+    host = plan_on_model(img, model, actions, num_parallel_envs=3, mcts_steps=8, max_rollout_depth=3, fused=True, device_trees=False)
+    np.random.seed(1)
+    dev = plan_on_model(img, model, actions, num_parallel_envs=3, mcts_steps=8, max_rollout_depth=3, device_trees=True)
+    assert host == want and dev == host and all(isinstance(a, int) and 0 <= a < 9 for a in dev)
+
+
+# ------------------------------------------------------------------------------------------------ 7. refusals
+def test_refusals():
+    from stove_amd import ops
+    from stove_amd.mcts.mcts_stove import MCTS, BatchedMCTSHandler, Forest
+    from stove_amd.video_prediction.stove import Stove
+    D, R = 3, 2
+    z, app = _roots()
+    # a model the fused expansion does not serve
+    torch.manual_seed(0)
+    narrow = Stove(make_cfg(**CFG, cl=16, transition_lik_std=[0.01] * 8)).to(DEV)
+    z16 = z[..., :2 + 8]
+    h = BatchedMCTSHandler([MCTS(app[m:m + 1], z16[m:m + 1], action_space=A, max_rollout_depth=D) for m in range(3)], app, action_space=A,
+                           max_rollout_depth=D)
+    h.device_trees = True
+    with pytest.raises(ValueError, match='state code length is 16'):
+        h.run_mcts(narrow, R, rollout_actions=_actions(R, 3, D))
+    h32, _ = _handler(D, device_trees=True)
+    with pytest.raises(ValueError, match='fused=False'):
+        h32.run_mcts(_model('init'), R, fused=False, rollout_actions=_actions(R, 3, D))
+    # bad host arguments of ops.plan_search: nothing is launched, the pool and the arrays stay as they were
+    st = _model('init')
+    emb_w, emb_b, gnn, rh = _weights(st)
+    cap = 1 + A * R
+    pool = torch.zeros(3, cap, N, 18, device=DEV)
+    pool[:, 0] = z.to(DEV)
+    before = pool.clone()
+    arrays = Forest(3, A, D, cap=cap).to_device(DEV)
+    kept = {k: v.clone() for k, v in arrays.items()}
+    acts = torch.from_numpy(_actions(R, 3, D).astype(np.int32)).to(DEV)
+
+    def call(pool=pool, arrays=arrays, acts=acts, app=app.to(DEV), sel=None):
+        return ops.plan_search(pool, arrays, app, acts, emb_w, emb_b, gnn, rh, D, 2, st.dyn.use_elu, st.dyn.loop_consts(), GAMMA, sel_trace=sel)
+    with torch.no_grad():
+        with pytest.raises(RuntimeError, match='first must be a contiguous int32'):
+            call(arrays=dict(arrays, first=arrays['first'].long()))
+        with pytest.raises(RuntimeError, match='Qsa must be a contiguous float64'):
+            call(arrays=dict(arrays, Qsa=arrays['Qsa'].float()))
+        with pytest.raises(RuntimeError, match='acts must be a contiguous int32'):
+            call(acts=acts.long())
+        with pytest.raises(RuntimeError, match='contiguous'):
+            call(pool=torch.zeros(3, cap, 18, N, device=DEV).transpose(2, 3))
+        with pytest.raises(ValueError, match='Nsa is'):
+            call(arrays=dict(arrays, Nsa=arrays['Nsa'][:, :-1].contiguous()))
+        with pytest.raises(ValueError, match='sel_trace is'):
+            call(sel=torch.zeros(R + 1, 3, dtype=torch.int32, device=DEV))
+        with pytest.raises(ValueError, match='do not fit'):
+            call(acts=acts[:, :-1].contiguous())
+        with pytest.raises(ValueError, match='do not fit'):
+            call(app=app[:2].to(DEV))
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(pool), _bits(before)) and all(torch.equal(arrays[k], kept[k]) for k in kept)
+    with torch.no_grad():
+        assert call().shape == (3,)                              # and the valid call still runs
+    torch.cuda.synchronize()
+    assert int(arrays['used'].min()) == 1 + A * R and not bool(arrays['status'].any())
