@@ -52,6 +52,13 @@ __device__ __forceinline__ int fixed_state(const float* __restrict__ zc, const l
   return hit;
 }
 
+// the rest of the recursion's initial state, row r = (b, k): the unstructured latent = 0.01 x the caller's standard-normal draw
+// (stove.py:663-668), written by the state kernel instead of a scale and a concatenation launch behind it
+__device__ __forceinline__ void init_latent(float* __restrict__ init6, const float* __restrict__ lat_noise, size_t r, int init_ld, int lat_dim) {
+  if (lat_noise != nullptr)
+    for (int d = 0; d < lat_dim; ++d) init6[r * init_ld + 6 + d] = 0.01f * lat_noise[r * lat_dim + d];
+}
+
 // thread (b, t, k): zfix (n,T,o,8), hits (n,T,o) u8, and the recursion's inputs
 //   zl / sl (n,Ts,o,6) = z_sup_full / z_sup_std_full [:, skip:],  init6 (n,o,6) = z_sup_full[:, skip-1]
 __global__ void supair_state_fwd_k(const float* __restrict__ zc, const long long* __restrict__ idx, float* __restrict__ zfix,
@@ -66,6 +73,14 @@ __global__ void supair_state_fwd_k(const float* __restrict__ zc, const long long
   hits[i] = (unsigned char)hit;
 #pragma unroll
   for (int d = 0; d < 8; ++d) zfix[(size_t)i * 8 + d] = cur[d];
+  if (skip == 1 && t == 0) {
+    // skip = 1: the recursion starts from z_sup_full[:, 0], the zero row v_from_state puts in front of frame 1 (stove.py:54-80);
+    // no code feeds it, so the backward leaves the gradient of init6 where it is (g6_at returns zero at t < 1)
+#pragma unroll
+    for (int d = 0; d < 6; ++d) init6[((size_t)b * o + k) * init_ld + d] = 0.0f;
+    init_latent(init6, lat_noise, (size_t)b * o + k, init_ld, lat_dim);
+    return;
+  }
   if (t < skip - 1 || t < 1) return;
   fixed_state(zc, idx, b, t - 1, k, T, o, fix, pv);
   float z6[6], s6[6];
@@ -82,10 +97,7 @@ __global__ void supair_state_fwd_k(const float* __restrict__ zc, const long long
   if (t == skip - 1) {
 #pragma unroll
     for (int d = 0; d < 6; ++d) init6[((size_t)b * o + k) * init_ld + d] = z6[d];
-    // the rest of the recursion's initial state: the unstructured latent = 0.01 x the caller's standard-normal draw (stove.py:663-668),
-    // written here instead of a scale and a concatenation launch behind this kernel
-    if (lat_noise != nullptr)
-      for (int d = 0; d < lat_dim; ++d) init6[((size_t)b * o + k) * init_ld + 6 + d] = 0.01f * lat_noise[((size_t)b * o + k) * lat_dim + d];
+    init_latent(init6, lat_noise, (size_t)b * o + k, init_ld, lat_dim);
   } else {
     const size_t r = (((size_t)b * (T - skip) + (t - skip)) * o + k) * 6;
 #pragma unroll
