@@ -367,8 +367,8 @@ def scene_likelihood(c, params, structs, x, z_obj, parts=False):
 # --------------------------------------------------------------------------
 # SuPAIR recognition side (encoder.py:28-57, supair.py:112-156)
 # --------------------------------------------------------------------------
-def encoder_forward(c, params, frames):
-    """RnnStates.forward: the same flattened frame fed for num_obj LSTM steps."""
+def encoder_forward(c, params, frames, hidden=False):
+    """RnnStates.forward: the same flattened frame fed for num_obj LSTM steps.  hidden: -> (codes, hs (nT, N, 256)) instead of the codes."""
     xf = frames.flatten(1)
     w_ih, w_hh = params['sup.encoder.rnn.weight_ih_l0'], params['sup.encoder.rnn.weight_hh_l0']
     b = params['sup.encoder.rnn.bias_ih_l0'] + params['sup.encoder.rnn.bias_hh_l0']
@@ -385,7 +385,8 @@ def encoder_forward(c, params, frames):
         outs.append(h)
     hs = torch.stack(outs, 1)                                       # (nT, N, 256)
     y = torch.sigmoid(hs @ params['sup.encoder.fc1.weight'].t() + params['sup.encoder.fc1.bias'])
-    return y @ params['sup.encoder.fc2.weight'].t() + params['sup.encoder.fc2.bias']
+    codes = y @ params['sup.encoder.fc2.weight'].t() + params['sup.encoder.fc2.bias']
+    return (codes, hs) if hidden else codes
 
 
 def constrain_zp(c, zp):
@@ -685,8 +686,8 @@ def stove_forward(c, params, structs, x_color, eps, actions=None, detail=False, 
     zs_std_full = v_std_from_pos(zs_std)
 
     # initial state, stove.py:663-685
-    lat0 = (0.0 + 0.01 * eps['latent']).squeeze()
-    std0 = (0.1 + 0.01 * eps['std']).squeeze()
+    lat0 = (0.0 + 0.01 * eps['latent'])[..., 0]                       # (B,N,cl/2-4): one object and one sequence keep their axes
+    std0 = (0.1 + 0.01 * eps['std'])[..., 0]
     z = {skip - 1: torch.cat([zs_full[:, skip - 1], lat0], -1)}
     dyn_std0 = torch.cat([zs_std_full[:, skip - 1, :, 2:], std0], -1)
     tstd = torch.tensor(transition_std(c), dtype=x.dtype).view(1, 1, -1)

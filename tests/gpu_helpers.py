@@ -96,3 +96,13 @@ def check(key, value, bar):
     if w is None or value > w[0]:
         _WORST[key] = (value, float(bar))
     assert value < bar, (key, value, bar)
+
+
+def check_ratio(key, value, bar):
+    """assert value < bar like check(), for keys whose bar changes from case to case (regime_bar): what is remembered per key is the
+    call with the worst value / bar, not the largest value, so that the recorded pair gives the worst ratio."""
+    value, bar = float(value), float(bar)
+    w = _WORST.get(key)
+    if w is None or not value / bar <= w[0] / w[1]:
+        _WORST[key] = (value, bar)
+    assert value < bar, (key, value, bar)

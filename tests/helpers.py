@@ -495,3 +495,246 @@ def assert_state_coverage(cov):
     assert cov['masks'] >= {0, 1, 2, 3}, cov['masks']
     assert cov['adjacent'] and cov['at_skip_m1'] and cov['at_skip'], cov
     assert cov['volatile_nonperm'] >= set(STATE_COUNTS[1:]), cov['volatile_nonperm']
+
+
+# ------------------------------------------------------------------------------------------------ recognition network at every count
+# The float64 restatement of what csrc/lstm.hip computes and the inputs / case lists of tests/test_encoder_counts_cpu.py and
+# tests/test_gpu_encoder_counts.py.
+def lstm_cell(pre, rec=None, c_prev=None):
+    """One LSTM cell step in the dtype of `pre`, the lines of O.encoder_forward's loop: pre (n,4H) the pre-activation sum (gate order
+    i, f, g, o), rec (n,4H) an optional recurrent term added to it, c_prev (n,H) the previous cell or None (zero) -> (c, h)"""
+    gates = pre if rec is None else pre + rec
+    i, f, g, o = gates.chunk(4, 1)
+    cell = gates.new_zeros(i.shape) if c_prev is None else c_prev
+    cell = torch.sigmoid(f) * cell + torch.sigmoid(i) * torch.tanh(g)
+    return cell, torch.sigmoid(o) * torch.tanh(cell)
+
+
+def lstm_cell_grads(pre, rec, c_prev, dh, dc_in=None):
+    """lstm_cell and its backward through autograd, in the dtype of `pre`: dh (n,H) the gradient of h, dc_in (n,H) the gradient flowing
+    into c from the next step or None -> dict(c, h, dg (n,4H) the gradient of the gate sum, dc_prev (n,H) the gradient of c_prev)"""
+    gates = (pre if rec is None else pre + rec).detach().clone().requires_grad_()
+    # no previous cell = a zero one: the same c and h, and its gradient dc sigmoid(f) exists either way (the kernel writes it either way)
+    cp = (torch.zeros_like(dh) if c_prev is None else c_prev.detach().clone()).requires_grad_()
+    c, h = lstm_cell(gates, None, cp)
+    loss = (h * dh).sum()
+    if dc_in is not None:
+        loss = loss + (c * dc_in).sum()
+    loss.backward()
+    return {'c': c.detach(), 'h': h.detach(), 'dg': gates.grad, 'dc_prev': cp.grad}
+
+
+def lstm_chain(x_proj, w_hh, steps):
+    """`steps` cell steps on the same input projection x_proj (n,4H) = x W_ih^T + b: hs (n, steps, H).  Step 0 has neither a
+    recurrent term nor a previous cell, as the kernels run it."""
+    hs, h, c = [], None, None
+    for _ in range(steps):
+        c, h = lstm_cell(x_proj, None if h is None else h @ w_hh.t(), c)
+        hs.append(h)
+    return torch.stack(hs, 1)
+
+
+CELL_SHAPES = [(1, 4), (3, 8), (37, 256), (257, 52), (2049, 256)]   # one thread / partial workgroup / ragged tails / H % 64 != 0
+CELL_PLANTS = (30.0, -30.0, 100.0, -100.0, 1e-4, -1e-4)             # both tails of both activations, and small arguments
+CELL_FAST = (0, 1)
+CELL_MORE = 7                                                       # gate-gradient slabs of other steps: eight steps at most
+CELL_FWD_FORMS = [(cp, gh) for cp in (False, True) for gh in (False, True)]                   # (c_prev given, gh given)
+CELL_REF_FORMS = [(gh, cp, dc) for gh in (False, True) for cp in (False, True) for dc in (False, True)]
+CELL_OUT_FORMS = [(True, None), (False, None), (True, 0), (False, 1), (True, 7)]            # (dg stored, dgx_sum: None or n_more)
+CELL_BWD_FORMS = [r + o for r in CELL_REF_FORMS for o in CELL_OUT_FORMS]                      # (gh, c_prev, dc_in, dg, n_more)
+_CELL_INPUTS, _CELL_REFS = {}, {}
+
+
+def cell_inputs(n, H):
+    """float32 values in float64, seeded per shape: gx, gh (n,4H) in [-3, 3] with CELL_PLANTS planted at drawn places of each, c_prev
+    (n,H) in [-2, 2], dh, dc_in (n,H) and dg_more (CELL_MORE,n,4H) in [-1, 1] (drawn once per shape and shared: read-only)"""
+    if (n, H) not in _CELL_INPUTS:
+        g = torch.Generator().manual_seed(5000 + 97 * n + H)
+        u = lambda lo, hi, *s: (torch.rand(*s, generator=g, dtype=torch.float64) * (hi - lo) + lo).float().double()      # noqa: E731
+        x = {'gx': u(-3, 3, n, 4 * H), 'gh': u(-3, 3, n, 4 * H), 'c_prev': u(-2, 2, n, H), 'dh': u(-1, 1, n, H), 'dc_in': u(-1, 1, n, H),
+             'dg_more': u(-1, 1, CELL_MORE, n, 4 * H)}
+        copies = max(1, min(n * 4 * H // 64, 16))
+        for k in ('gx', 'gh'):
+            where = torch.randperm(n * 4 * H, generator=g)[:copies * len(CELL_PLANTS)]
+            x[k].view(-1)[where] = torch.tensor(CELL_PLANTS, dtype=torch.float64).float().double().repeat(copies)
+        _CELL_INPUTS[(n, H)] = x
+    return _CELL_INPUTS[(n, H)]
+
+
+def cell_reference(n, H, gh, cp, dc, dtype=torch.float64):
+    """lstm_cell_grads on cell_inputs(n, H) with the recurrent term, the previous cell and the incoming cell gradient given or not
+    (computed once per form and dtype, shared, read-only); dtype float32: the restatement's own float32 run, for the gap"""
+    key = (n, H, gh, cp, dc, dtype)
+    if key not in _CELL_REFS:
+        x = {k: v.to(dtype) for k, v in cell_inputs(n, H).items()}
+        _CELL_REFS[key] = lstm_cell_grads(x['gx'], x['gh'] if gh else None, x['c_prev'] if cp else None, x['dh'], x['dc_in'] if dc else None)
+    return _CELL_REFS[key]
+
+
+ENC_COUNTS = tuple(range(1, 9))
+ENC_ROWS = (1, 37, 256, 300)          # below / on / above a 256-row tile; 1 and 37 are no multiple of 4 (weight gradients leave the MFMA kernel)
+ENC_GEMMS = ('bf16x3', 'fp32')
+ENC_REGIMES = ('analytic', 'init', 'stress')
+ENC_D, ENC_H = 1024, 256
+
+
+def encoder_cases():
+    """(K, rows, regime, gemm, arena): the full cross"""
+    return [(K, rows, regime, gemm, arena) for K in ENC_COUNTS for rows in ENC_ROWS for regime in ENC_REGIMES for gemm in ENC_GEMMS
+            for arena in (True, False)]
+
+
+def encoder_dx_cases():
+    """(K, rows, regime, gemm): one case per K through ops.encoder_lstm with the gradient of the input asked for"""
+    return [(K, 40, ENC_REGIMES[K % 3], 'bf16x3') for K in ENC_COUNTS]
+
+
+def encoder_product_paths(rows, gemm, arena, needs_dx=False, gemm_ok=None):
+    """Which kernels the products of _EncoderLstmFn take at a row count: 'mfma' (csrc/gemm_bf16.hip) or 'library'.
+    forward (x W_ih^T, h W_hh^T) and dh (dg W_hh): the MFMA kernel unless gemm = 'fp32' -- their float4 sizes are 1024 and 256;
+    wgrad (dW_ih, dW_hh): over `rows`, so the MFMA kernel only where rows % 4 == 0; direct: gradients added into the arena's views
+    inside the kernels (needs the MFMA weight-gradient path and no gradient of the input)"""
+    ok = gemm_ok if gemm_ok is not None else (lambda *d: all(int(v) % 4 == 0 and int(v) > 0 for v in d))
+    mfma = gemm != 'fp32' and ok(ENC_D, ENC_H)
+    wgrad = mfma and ok(rows)
+    return {'forward': 'mfma' if mfma else 'library', 'dh': 'mfma' if mfma else 'library', 'wgrad': 'mfma' if wgrad else 'library',
+            'direct': bool(arena and wgrad and not needs_dx)}
+
+
+_ENC_INPUTS, _ENC_REFS = {}, {}
+
+
+def encoder_inputs(K, rows):
+    """frames (rows,1,32,32) in [0, 1] and an output weighting (rows,K,8) in [0, 1], float32 values in float64"""
+    if (K, rows) not in _ENC_INPUTS:
+        g = torch.Generator().manual_seed(9000 + 10 * rows + K)
+        _ENC_INPUTS[(K, rows)] = (torch.rand(rows, 1, 32, 32, generator=g, dtype=torch.float64).float().double(),
+                                  torch.rand(rows, K, 8, generator=g, dtype=torch.float64).float().double())
+    return _ENC_INPUTS[(K, rows)]
+
+
+def encoder_reference(K, rows, regime, dtype=torch.float64):
+    """O.encoder_forward + backward under the output weighting: dict(codes, hs, grads {name without 'sup.encoder.': grad}); once per
+    (K, rows, regime, dtype), shared, read-only.  float32: the oracle's own float32 run, for the gap."""
+    key = (K, rows, regime, dtype)
+    if key not in _ENC_REFS:
+        c, _, params = oracle_setup(dtype, regime=regime, num_obj=K)
+        params = {k: v for k, v in params.items() if k.startswith('sup.encoder.')}
+        x, w = (t.to(dtype) for t in encoder_inputs(K, rows))
+        codes, hs = O.encoder_forward(c, params, x, hidden=True)
+        (codes * w).sum().backward()
+        _ENC_REFS[key] = {'codes': codes.detach(), 'hs': hs.detach(), 'grads': {k[len('sup.encoder.'):]: p.grad for k, p in params.items()}}
+    return _ENC_REFS[key]
+
+
+COLSUM_ROWS = (0, 1, 15, 16, 17, 511, 512, 513, 8193)     # the level boundaries of colsum_level: <= 16 chunks, <= 512, a second level
+COLSUM_COLS = (1, 3, 8, 50, 64, 68, 1024)                 # the narrow kernel (padded powers of two) and the float4 kernel
+CHUNK_SIZES, CHUNK_COUNTS = (4, 1028), (1, 2, 16, 17)
+
+
+def sum_inputs(seed, *shape):
+    """float32 values in float64 in [-0.5, 1]: sums that grow with the row count, so the max norm has a scale"""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(*shape, generator=g, dtype=torch.float64) * 1.5 - 0.5).float().double()
+
+
+# ------------------------------------------------------------------------------------------------ the assembled model at every count
+MODEL_COUNTS = tuple(range(1, 9))
+MODEL_SHAPES = ((3, 5), (1, 3))                  # (B, T); one sequence and a single recursion step in the second
+MODEL_INIT_COUNTS = (1, 4, 8)
+
+
+def model_cfg(N):
+    """CASES['n6'] of tests/test_gpu_dynamics.py taken to every count: 'greedy' outside three objects, the six-object overlap weight
+    and object scale above three"""
+    cfg = dict(num_obj=N)
+    if N != 3:
+        cfg['debug_match_objects'] = 'greedy'
+    if N > 3:
+        cfg.update(overlap_beta=100.0, max_obj_scale=0.22)
+    return cfg
+
+
+def model_cases():
+    """(N, B, T, regime, fused): every count x both shapes x the fused dynamics / state / ELBO switches on and off under the
+    'analytic' weights, and the 'init' weights at 1, 4 and 8 objects (the flat parameter arena is on in all of them)"""
+    return [(N, B, T, regime, fused) for N in MODEL_COUNTS for B, T in MODEL_SHAPES
+            for regime in (('analytic', 'init') if N in MODEL_INIT_COUNTS else ('analytic',)) for fused in (True, False)]
+
+
+def model_case_id(case):
+    return 'N%d-B%dT%d-%s-%s' % (case[:4] + ('fused' if case[4] else 'opbyop',))
+
+
+def paint_discs(centres, radii, res=32):
+    """Frames of 1 .. 8 discs: centres (..., N, 2) = (x, y) in [-1, 1] frame coordinates, radii (N,) in pixels -> (..., 3, res, res)
+    float32 values in float64, object k in colour channel k % 3, clipped to [0, 1].  A disc is 1 inside, 0 outside and falls
+    linearly over the one pixel around its rim (so a sub-pixel move changes the frame)."""
+    centres = np.asarray(centres, dtype=np.float64)
+    N = centres.shape[-2]
+    pix = np.arange(res, dtype=np.float64) + 0.5
+    yy, xx = np.meshgrid(pix, pix, indexing='ij')
+    out = np.zeros(centres.shape[:-2] + (3, res, res))
+    for k in range(N):
+        cx = (centres[..., k, 0] + 1) / 2 * res
+        cy = (centres[..., k, 1] + 1) / 2 * res
+        d = np.sqrt((xx - cx[..., None, None]) ** 2 + (yy - cy[..., None, None]) ** 2)
+        out[..., k % 3, :, :] += np.clip(radii[k] + 0.5 - d, 0.0, 1.0)
+    return torch.from_numpy(np.clip(out, 0.0, 1.0)).float().double()
+
+
+def disc_radii(N):
+    """every object its own radius (pixels): a swapped or dropped object changes the frame"""
+    return (2.4 if N <= 3 else 1.6) + 0.3 * np.arange(N)
+
+
+def draw_tracks(g, m, T, N):
+    """m sequences of N disc centres over T frames (m,T,N,2): a start in [-0.7, 0.7]^2 and a velocity in [-0.12, 0.12]^2 per object,
+    reflected at +-0.8"""
+    p0 = torch.rand(m, 1, N, 2, generator=g, dtype=torch.float64) * 1.4 - 0.7
+    v = torch.rand(m, 1, N, 2, generator=g, dtype=torch.float64) * 0.24 - 0.12
+    p = p0 + v * torch.arange(T, dtype=torch.float64).view(1, T, 1, 1)
+    return (0.8 - ((p + 0.8) % 3.2 - 1.6).abs()).numpy()
+
+
+def model_decisions(N, regime, x, dtype):
+    """The discrete decisions of the oracle's run in `dtype` on colour frames x (m,T,3,32,32): the matching indices (m,T,N) and the
+    fix_supair hit masks (m,T,N) (helpers.state_chain on the oracle's own codes)"""
+    c, _, params = _model_oracle(N, regime, dtype)
+    m, T = x.shape[:2]
+    with torch.no_grad():
+        codes = O.encoder_forward(c, params, O.bw_transform(x.to(dtype)).flatten(0, 1))
+        out = state_chain(c, codes.reshape(-1, 8), m, T, N, c.skip, c.debug_fix_supair, c.debug_match_objects)
+    return out['idx'], out['hits']
+
+
+_MODEL_ORACLES, _MODEL_INPUTS = {}, {}
+
+
+def _model_oracle(N, regime, dtype):
+    key = (N, regime, dtype)
+    if key not in _MODEL_ORACLES:
+        c, structs, params = oracle_setup(dtype, requires_grad=False, regime=regime, **model_cfg(N))
+        _MODEL_ORACLES[key] = (c, structs, {k: v for k, v in params.items() if k.startswith('sup.encoder.')})
+    return _MODEL_ORACLES[key]
+
+
+def model_same_decisions(N, regime, x):
+    """per sequence: the oracle's float32 run takes the matching and the fix_supair hits of its float64 run"""
+    i64, h64 = model_decisions(N, regime, x, torch.float64)
+    i32, h32 = model_decisions(N, regime, x, torch.float32)
+    return (i64 == i32).flatten(1).all(1) & (h64 == h32).flatten(1).all(1)
+
+
+def model_inputs(N, B, T, regime):
+    """(x (B,T,3,32,32), eps as O.draw_eps) of a model case, float32 values in float64: the first B painted sequences of a seeded
+    stream on which the oracle's float32 run takes its float64 run's decisions (model_same_decisions); drawn once, shared"""
+    key = (N, B, T, regime)
+    if key not in _MODEL_INPUTS:
+        g = torch.Generator().manual_seed(810000 + 1000 * N + 10 * B + T + (500 if regime != 'analytic' else 0))
+        seqs = _accept(g, B, lambda g_, m: (paint_discs(draw_tracks(g_, m, T, N), disc_radii(N)),),
+                       lambda cand: model_same_decisions(N, regime, cand[0]), 'model N%d B%d T%d %s' % (N, B, T, regime))
+        eps = O.draw_eps(B, N, T, generator=g, dtype=torch.float64)
+        eps = {'latent': eps['latent'].float().double(), 'std': eps['std'].float().double(), 'steps': [e.float().double() for e in eps['steps']]}
+        _MODEL_INPUTS[key] = (torch.stack([s[0] for s in seqs]), eps)
+    return _MODEL_INPUTS[key]
