@@ -210,6 +210,21 @@ int stove_objspn_mpe(const StoveSpnTables* t, const float* leaf_means, const flo
 int stove_render_frames(const float* bg, const float* patches, int frames_per_patch, const float* z, float* out, int n_frames,
                         int n_obj, void* stream);
 
+/* ---- frame rendering at run-time sizes, with the squared pixel error fused in (csrc/render.hip): the composed paste of
+ * Supair.reconstruct_from_z per channel, out (n_frames, C*W*H) = clamp(bg + sum_k grid_sample(patch_k, inverse transform of z_k), 0, 1),
+ * bilinear, zero padding, either align_corners convention.  A frame plane is W rows of H columns, a patch plane pw rows of ph columns
+ * (the width / height order of that code); the transform's x runs along the columns.  bg (C*W*H,), patches (., C*pw*ph) flattened
+ * (channel, row, column) and indexed as in stove_render_frames, z (n_frames*n_obj, 4) = [sx, sy, x, y].
+ * truth (n_frames, C*W*H) and sqerr (n_frames,) come together or not at all: sqerr[f] = sum over the frame's C*W*H pixels of
+ * (clamped frame - truth)^2, summed in a fixed order without atomics (bit-identical between calls, and with or without `out`).
+ * out may be NULL (no frame is written then), but not together with sqerr.  n_frames == 0 launches nothing.
+ * With sqerr a frame is one workgroup whatever its size (that is what keeps the sum in one fixed order): meant for many small
+ * frames; a few very large ones are rendered faster without truth (tiled) and summed by the caller.
+ * hipErrorInvalidValue, nothing launched: a NULL bg / patches / z, truth without sqerr or the reverse, neither out nor sqerr,
+ * n_obj outside 1..8, C outside 1..4, a size < 1, frames_per_patch < 0, n_frames < 0.  No gradients. */
+int stove_render_frames_any(const float* bg, const float* patches, int frames_per_patch, const float* z, const float* truth, float* out,
+                            float* sqerr, int n_frames, int n_obj, int C, int W, int H, int pw, int ph, int align_corners, void* stream);
+
 /* ---- glimpses + masks alone (supair.py:241-356), for the Supair.patches_from_z /
  * masks_from_z API: patches, marg_patch: (n_frames*n_obj,100); overlap: (n_frames*n_obj,).
  * `tile` is scratch of stove_objspn_tile_floats(n_frames*n_obj) floats. */

@@ -112,6 +112,7 @@ def _declare(lib):
         'stove_glimpse_mean': (I, [P, P, P, I, I, I, P]),
         'stove_objspn_mpe': (I, [T, P, P, P, P, P, I, P]),
         'stove_render_frames': (I, [P, P, I, P, P, I, I, P]),
+        'stove_render_frames_any': (I, [P, P, I, P, P, P, P] + [I] * 8 + [P]),
         'stove_enc_head_fwd': (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
         'stove_enc_head_bwd_ws_floats': (S, [I, I]),
         'stove_enc_head_bwd': (I, [P, P, P, P, P, P, P, P, P, P, I, P, I, I, I, I, I, P]),

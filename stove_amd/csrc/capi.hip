@@ -37,6 +37,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "reward_head.hip"
 #include "plan.hip"
 #include "plan_tree.hip"
+#include "render.hip"
 
 namespace stove {
 
@@ -167,7 +168,8 @@ extern "C" {
 //    (added since, nothing changed: stove_rollout_sample_fwd, stove_rollout_sample_fwd_cl -- the sampling rollout;
 //     stove_plan_expand_ws_bytes, stove_plan_expand -- one expansion of a batch of search trees;
 //     stove_rollout_bwd_ws_bytes, stove_rollout_bwd and their _cl siblings -- the backward of both rollouts;
-//     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device)
+//     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device;
+//     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in)
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -830,6 +832,46 @@ int stove_render_frames(const float* bg, const float* patches, int frames_per_pa
   if (frames_per_patch < 0 || n_obj < 0 || (total + 255) / 256 > 0x7fffffffLL) return (int)hipErrorInvalidValue;
   STOVE_LAUNCH(render_frames_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bg, patches,
                frames_per_patch, z, out, n_frames, n_obj);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- rendering at run-time sizes + squared pixel error (render.hip)
+int stove_render_frames_any(const float* bg, const float* patches, int frames_per_patch, const float* z, const float* truth, float* out,
+                            float* sqerr, int n_frames, int n_obj, int C, int W, int H, int pw, int ph, int align_corners, void* stream) {
+  STOVE_VALIDATE(render_any(bg, patches, frames_per_patch, z, truth, out, sqerr, n_frames, n_obj, C, W, H, pw, ph));
+  if (n_frames == 0) return 0;
+  RenderGeom g;
+  g.C = C; g.W = W; g.H = H; g.pw = pw; g.ph = ph;
+  // affine_grid's base grid (a single pixel sits at 0 under either convention), grid_sample's unnormalisation
+  const auto base = [&](int n, float* a, float* b) {
+    if (n == 1) { *a = 0.0f; *b = 0.0f; }
+    else if (align_corners) { *a = 2.0f / (n - 1); *b = -1.0f; }
+    else { *a = 2.0f / n; *b = 1.0f / n - 1.0f; }
+  };
+  const auto unnorm = [&](int n, float* a, float* b) {
+    if (align_corners) { *a = 0.5f * (n - 1); *b = 0.5f * (n - 1); }
+    else { *a = 0.5f * n; *b = 0.5f * n - 0.5f; }
+  };
+  base(H, &g.col_a, &g.col_b);
+  base(W, &g.row_a, &g.row_b);
+  unnorm(ph, &g.px_a, &g.px_b);
+  unnorm(pw, &g.py_a, &g.py_b);
+  const int P = W * H;
+  // the fused sum wants the whole frame in one workgroup; frames alone are cut into tiles of four positions per thread
+  const int kTile = 4 * kRenderThreads;
+  const int tiles = sqerr ? 1 : (P + kTile - 1) / kTile;
+  const int tile_len = sqerr ? P : kTile;
+  if (tiles > 65535) return (int)hipErrorInvalidValue;
+  const size_t lds = (size_t)(frames_per_patch > 0 ? n_obj : 1) * C * pw * ph * sizeof(float);
+  const dim3 grid((unsigned)n_frames, (unsigned)tiles), block(kRenderThreads);
+  if (lds <= 56 * 1024) {
+    STOVE_LAUNCH(render_frames_any_k<true>, grid, block, lds, (hipStream_t)stream, bg, patches, frames_per_patch, z, truth, out, sqerr, n_obj,
+                 g, tile_len);
+  } else {          // the frame's patch rows do not fit the LDS: the taps read global memory
+    STOVE_LAUNCH(render_frames_any_k<false>, grid, block, 0, (hipStream_t)stream, bg, patches, frames_per_patch, z, truth, out, sqerr, n_obj,
+                 g, tile_len);
+  }
   STOVE_LAUNCH_CHECK();
   return 0;
 }

@@ -228,6 +228,18 @@ inline int plan_search(const float* z_pool, const int* first, const int* parent,
   return 0;
 }
 
+// ---- stove_render_frames_any: frames of C x W x H pixels from glimpses of C x pw x ph (csrc/render.hip).  n_frames == 0 is a valid empty
+// call; truth and sqerr come together; one of out / sqerr is wanted.  The frame and the patch set are indexed with ints.
+inline int render_any(const float* bg, const float* patches, int frames_per_patch, const float* z, const float* truth, const float* out,
+                      const float* sqerr, int n_frames, int n_obj, int C, int W, int H, int pw, int ph) {
+  if (n_frames < 0 || n_obj < 1 || n_obj > kMaxObjects || C < 1 || C > 4 || W < 1 || H < 1 || pw < 1 || ph < 1 || frames_per_patch < 0)
+    return kStoveInvalidValue;
+  if (n_frames == 0) return 0;          // (arrays without elements have no address)
+  if ((truth == nullptr) != (sqerr == nullptr) || (out == nullptr && sqerr == nullptr) || null_any(bg, patches, z)) return kStoveInvalidValue;
+  if ((long long)C * W * H > 0x3fffffffLL || (long long)kMaxObjects * C * pw * ph > 0x3fffffffLL) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

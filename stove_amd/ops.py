@@ -458,6 +458,39 @@ def render_frames(bg, patches, frames_per_patch, z, n_obj):
     return out
 
 
+@torch.no_grad()
+def render_frames_any(bg, patches, frames_per_patch, z, n_obj, geom, truth=None, want_frames=True):
+    """render_frames at run-time sizes, with the squared pixel error fused in (stove_render_frames_any, csrc/render.hip).
+    geom = (C, W, H, patch_width, patch_height, align_corners); bg (C*W*H,), patches (., C*pw*ph) flattened (channel, row, column) and
+    indexed as in render_frames, z (nf*n_obj, 4) -> frames (nf, C*W*H).  With truth (nf, C*W*H): (frames, sqerr), sqerr (nf,) = sum over a
+    frame's pixels of (frame - truth)^2 in a fixed order; want_frames=False: (None, sqerr), no frame is written to memory."""
+    lib = _lib.load()
+    C, W, H, pw, ph, ac = (int(v) for v in geom)
+    n_obj, frames_per_patch = int(n_obj), int(frames_per_patch)
+    if not (1 <= n_obj <= 8 and 1 <= C <= 4 and min(W, H, pw, ph) >= 1 and frames_per_patch >= 0):
+        raise ValueError('render_frames_any: n_obj %d, geom %s, frames_per_patch %d out of range' % (n_obj, tuple(geom), frames_per_patch))
+    bg, patches, z = _f32(bg), _f32(patches), _f32(z)
+    px, pd = C * W * H, C * pw * ph
+    if z.dim() != 2 or z.shape[-1] != 4 or z.shape[0] % n_obj:
+        raise ValueError('render_frames_any: z %s is not (frames * %d, 4)' % (tuple(z.shape), n_obj))
+    nf, dev = z.shape[0] // n_obj, z.device
+    need = 1 if frames_per_patch == 0 else ((nf + frames_per_patch - 1) // frames_per_patch) * n_obj
+    if bg.numel() != px or patches.numel() % pd or patches.numel() // pd < need:
+        raise ValueError('render_frames_any: bad shapes bg %s patches %s z %s for geom %s' % (tuple(bg.shape), tuple(patches.shape), tuple(z.shape), tuple(geom)))
+    if truth is None and not want_frames:
+        raise ValueError('render_frames_any: nothing asked for (no truth and want_frames=False)')
+    if truth is not None:
+        truth = _f32(truth)
+        if truth.numel() != nf * px:
+            raise ValueError('render_frames_any: truth %s does not hold %d frames of %d pixels' % (tuple(truth.shape), nf, px))
+    with torch.cuda.device(dev):
+        out = torch.empty(nf, px, dtype=torch.float32, device=dev) if want_frames else None
+        sqerr = torch.empty(nf, dtype=torch.float32, device=dev) if truth is not None else None
+        check(lib.stove_render_frames_any(ptr(bg), ptr(patches), frames_per_patch, ptr(z), ptr(truth), ptr(out), ptr(sqerr), nf, n_obj,
+                                          C, W, H, pw, ph, 1 if ac else 0, stream()), 'stove_render_frames_any')
+    return out if truth is None else (out, sqerr)
+
+
 def scene_likelihood(frames, z, obj_tabs, bg_tabs, n_obj, beta, sink=None, geom=None):
     """frames (nf,1024), z (nf*n_obj,4)=[sx,sy,x,y]; obj_tabs=(coef,wsum,wroot,scope,leaf_slot),
     bg_tabs=(coef,wroot,side[,dense]) -> ll (nf,), parts (nf,3)=(bg, patches, overlap).

@@ -227,6 +227,24 @@ class Supair(nn.Module):
         recons = spn.mpe(patches.flatten(start_dim=1))
         return recons.view(x.shape[0], self.c.num_obj, -1).type(self.c.dtype)
 
+    def render_geom(self):
+        """(channels, width, height, patch_width, patch_height, align_corners) of ops.render_frames_any."""
+        c = self.c
+        return (c.channels, c.width, c.height, c.patch_width, c.patch_height, bool(getattr(c, 'align_corners', False)))
+
+    @torch.no_grad()
+    def render_inputs(self, z, x=None, max_activation=True, single_image=True):
+        """What reconstruct_from_z pastes: the background SPN's max-activation image (c*w*h,), the patch rows (., c*pw*ph) and how many
+        consecutive frames share a row set (0: one row for every object of every frame; ops.render_frames' frames_per_patch)."""
+        T = z.shape[1]
+        bg = self.spn_max_activation(self.bg_spn)
+        if max_activation:
+            return bg, self.spn_max_activation(self.obj_spn).view(1, -1), 0
+        if x is None:
+            raise ValueError('Need x for reconstructions.')
+        z_in, x_in = (z[:, 0], x) if single_image else (z.flatten(end_dim=1), x.flatten(end_dim=1))
+        return bg, self.spn_mpe(z_in, x_in, spn=self.obj_spn), (T if single_image else 1)
+
     @torch.no_grad()
     def reconstruct_from_z(self, z, x=None, max_activation=True, single_image=True):
         """Render frames from object states: the background SPN's max-activation image plus one patch per object pasted
@@ -238,20 +256,18 @@ class Supair(nn.Module):
         c = self.c
         z = z[..., :4]
         n, T, o = z.shape[:3]
-        if c.channels != 1:
-            raise NotImplementedError('reconstruct_from_z: single-channel SPN inputs only (as the reference, supair.py:452-464)')
-        bg = self.spn_max_activation(self.bg_spn)
-        if max_activation:
-            patches, per = self.spn_max_activation(self.obj_spn).view(1, -1), 0
-        else:
-            if x is None:
-                raise ValueError('Need x for reconstructions.')
-            z_in, x_in = (z[:, 0], x) if single_image else (z.flatten(end_dim=1), x.flatten(end_dim=1))
-            patches, per = self.spn_mpe(z_in, x_in, spn=self.obj_spn), (T if single_image else 1)
-        if (c.width, c.height) == (32, 32) and (c.patch_width, c.patch_height) == (10, 10) and not bool(getattr(c, 'align_corners', False)):
+        bg, patches, per = self.render_inputs(z, x, max_activation, single_image)
+        if c.channels == 1 and (c.width, c.height) == (32, 32) and (c.patch_width, c.patch_height) == (10, 10) \
+                and not bool(getattr(c, 'align_corners', False)):
             frames = ops.render_frames(bg.float(), patches.float(), per, z.reshape(-1, 4).float(), o)
             return frames.view(n, T, c.channels, c.width, c.height).type(c.dtype)
-        # any other frame size / sampling convention: the reference's paste through the inverse transform (supair.py:480-498)
+        if z.is_cuda and (c.channels > 1 or c.dtype == torch.float32):
+            # colour frames, other frame / glimpse sizes, the other sampling convention: one kernel at run-time sizes (csrc/render.hip;
+            # float32, as every kernel of the colour model)
+            frames = ops.render_frames_any(bg.float(), patches.float().reshape(-1, patches.shape[-1]), per,
+                                           z.reshape(-1, 4).float().contiguous(), o, self.render_geom())
+            return frames.view(n, T, c.channels, c.width, c.height).type(c.dtype)
+        # single-channel models in other dtypes, any model on the host: the reference's paste through the inverse transform (supair.py:480-498), the kernel's specification
         zf = z.reshape(n * T, o, 4)
         if per == 0:
             pat = patches.view(1, 1, -1).expand(n * T, o, -1)

@@ -177,13 +177,16 @@ class AbstractTrainer:
 
 
 def _save_clip(path, frames, fps=24):
-    """frames (T, H, W) uint8 -> path.gif (PIL) or path.npy."""
+    """frames (T, H, W) uint8, or three colour planes (T, 3, H, W) -> path.gif (PIL; RGB for the planes) or path.npy."""
+    rgb = frames.ndim == 4
+    if rgb:
+        frames = np.ascontiguousarray(np.transpose(frames, (0, 2, 3, 1)))
     try:
         from PIL import Image
     except ImportError:
         np.save(path + '.npy', frames)
         return
-    imgs = [Image.fromarray(f, mode='L') for f in frames]
+    imgs = [Image.fromarray(f, mode='RGB' if rgb else 'L') for f in frames]
     imgs[0].save(path + '.gif', save_all=True, append_images=imgs[1:], duration=int(1000 / fps), loop=0)
 
 
@@ -202,12 +205,16 @@ class Trainer(AbstractTrainer):
         """Position / velocity error of (n,T,o,4) predictions against the labels under the best
         object permutation: one permutation per sequence (chosen on the first <=4 frames), or per
         image for SuPAIR-only training.  Also the number of sequences without identity swaps."""
+        return Trainer._prediction_error(self, predicted, true, return_velocity, return_id_swaps, return_full, return_matched, level, 4)
+
+    def _prediction_error(self, predicted, true, return_velocity, return_id_swaps, return_full, return_matched, level, fit_frames):
+        """prediction_error with the number of frames the per-sequence permutation is chosen on (pixel_error fits on five)."""
         if self.c.supair_only:
             return_velocity, level = False, 'image'
         perms = list(itertools.permutations(range(self.c.num_obj)))
         perm_t = torch.tensor(perms, device=predicted.device)                     # (P, o)
         pos_p, pos_t = predicted[..., :2], true[..., :2]
-        t_fit = min(4, predicted.shape[1])
+        t_fit = min(fit_frames, predicted.shape[1])
 
         def permuted(x, best):
             """x (n, T, o, d) with the objects of sequence i reordered by perms[best[i]] (one gather, no host loop)."""
@@ -443,6 +450,90 @@ class Trainer(AbstractTrainer):
                 break
         self.stove.train()
 
+    @staticmethod
+    def linear_rollout(z_last, num):
+        """The evaluation's "linear motion" baseline (reference scripts/pixel_error.py:69-85): z_last (n, o, D) = [sx, sy, x, y, vx, vy, ..]
+        -> (n, num, o, D) with sizes, velocities and the rest held and positions x + v * t for t = 1..num."""
+        t = torch.arange(1, num + 1, device=z_last.device, dtype=z_last.dtype).view(1, num, 1, 1)
+        held = z_last.unsqueeze(1).repeat(1, num, 1, 1)
+        return torch.cat([held[..., :2], held[..., 2:4] + held[..., 4:6] * t, held[..., 4:]], -1)
+
+    @torch.no_grad()
+    def _pixel_error_inputs(self, linear, real_mpe, num):
+        """What pixel_error scores, on the device (the caller holds eval mode): z_seq (n, T', o, D) = cat(z_recon, z_pred), the true
+        frames (n, T', c, w, h) as the SPNs see them, the true states (n, T', o, .) and the frame the MPE patches are cut from (or None)."""
+        c, ds = self.c, self.test_dataset
+        step, nv, skip, bs = c.frame_step, c.num_visible, c.skip, c.batch_size
+        num = c.num_frames // step - nv if num is None else int(num)
+        images, labels = ds.total_img[:bs, ::step], ds.total_data[:bs, ::step]
+        if num < 0 or images.shape[1] < nv + num:
+            raise ValueError('pixel_error: %d visible + %d rollout frames asked for, the test sequences hold %d' % (nv, num, images.shape[1]))
+        stove_input = self.init_t(torch.from_numpy(np.ascontiguousarray(images[:, :nv])))
+        true_images = self.init_t(torch.from_numpy(np.ascontiguousarray(images[:, skip:nv + num])))
+        act = fut = None
+        if c.action_conditioned:
+            actions = ds.total_actions[:bs, ::step]
+            act = self.init_t(torch.from_numpy(np.ascontiguousarray(actions[:, :nv])))
+            fut = self.init_t(torch.from_numpy(np.ascontiguousarray(actions[:, nv:nv + num])))
+        _, prop_dict, _ = self.stove(stove_input, c.plot_every, act, False)
+        z_recon = prop_dict['z']
+        if linear:
+            z_pred = self.linear_rollout(z_recon[:, -1], num)
+        else:
+            app = prop_dict['obj_appearances'][:, -1] if c.debug_core_appearance else None
+            z_pred, _ = self.stove.rollout(z_recon[:, -1], num=num, actions=fut, appearance=app)
+        z_seq = torch.cat([z_recon, z_pred], 1)
+        if linear:                              # positions clamped to the frame, the velocity columns dropped (pixel_error.py:89-95)
+            lim = 0.8 if c.coord_lim == 10 else 0.9
+            z_seq = torch.cat([z_seq[..., :2], torch.clamp(z_seq[..., 2:4], -lim, lim), z_seq[..., 6:]], -1)
+        img = None
+        if real_mpe:                            # the frame the first scored state was inferred from, as the SPNs see it
+            img = stove_input[:, skip]
+            if c.debug_bw:
+                img = torch.clamp(img.sum(1), 0, 1).unsqueeze(1)
+        if c.debug_bw:
+            true_images = bw_transform(true_images)
+        true_states = self.init_t(torch.from_numpy(np.ascontiguousarray(labels[:, skip:nv + num])))
+        return z_seq, true_images, true_states, img
+
+    @torch.no_grad()
+    def pixel_error(self, linear=False, real_mpe=False, num=None, fused=True):
+        """Pixel-space prediction error over time (reference scripts/pixel_error.py:38-161): the first batch_size test sequences (every
+        frame_step-th frame), num_visible frames encoded, `num` (default num_frames // frame_step - num_visible) steps rolled out -- or
+        extrapolated at constant velocity with positions clamped to the frame (`linear`) --, every state of cat(z_recon, z_pred) rendered
+        with reconstruct_from_z's paste (`real_mpe`: with the MPE patches of the first scored frame instead of the max-activation patch)
+        and held against the true frames (the bw plane under debug_bw).
+        -> {'mse': (T',) mean squared pixel error per time step over sequences and pixels (channels included),
+            'mse_states': (T',) position error per time step under the object permutation fitted on the first 5 frames}, CPU tensors,
+        T' = num_visible - skip + num.  fused=True: the render kernel returns the per-frame squared error and writes no frame
+        (ops.render_frames_any); fused=False: the frames are materialised and the mean is taken in torch (the cross-check).
+        [amd] rank 0 evaluates, in eval mode, as test() does."""
+        if self.rank != 0:
+            return None
+        c = self.c
+        if c.supair_only:
+            raise ValueError('pixel_error: needs the dynamics model (supair_only is set)')
+        self.stove.eval()
+        try:
+            z_seq, true_images, true_states, img = self._pixel_error_inputs(linear, real_mpe, num)
+            n, T = z_seq.shape[:2]
+            sup = self.stove.sup
+            if fused:
+                z4 = z_seq[..., :4]
+                bg, patches, per = sup.render_inputs(z4, img, max_activation=not real_mpe, single_image=True)
+                from .. import ops
+                _, sq = ops.render_frames_any(bg.float(), patches.float().reshape(-1, patches.shape[-1]), per,
+                                              z4.reshape(-1, 4).float().contiguous(), z4.shape[2], sup.render_geom(),
+                                              truth=true_images.float().reshape(n * T, -1), want_frames=False)
+                mse = (sq.view(n, T).double().sum(0) / (n * true_images[0, 0].numel())).to(c.dtype)
+            else:
+                model_images = torch.clamp(sup.reconstruct_from_z(z_seq, img, max_activation=not real_mpe, single_image=True), 0, 1)
+                mse = torch.mean((true_images - model_images) ** 2, dim=(0, 2, 3, 4))
+            err = self._prediction_error(z_seq[..., 2:4], true_states[..., :2], False, False, True, False, 'sequence', 5)
+        finally:
+            self.stove.train()
+        return {'mse': mse.detach().cpu(), 'mse_states': err['error']}
+
     @torch.no_grad()
     def long_rollout(self, idx=None, actions=None, step_counter=None, num=500):
         """Roll the dynamics out for `num` frames from the first visible frames of a few test
@@ -470,8 +561,9 @@ class Trainer(AbstractTrainer):
             err = self.prediction_error(z_pred[:, :avail, :, 2:], true, return_full=True, return_id_swaps=False)
             out.update({k: v.numpy() for k, v in err.items()})
         z_recon = prop_dict['z']
-        if self.c.channels == 1:
-            real = bw_transform(present) if present.shape[2] != 1 else present
+        if self.c.channels == 1 or present.shape[2] == self.c.channels:
+            # the frames the SPNs model: the bw plane, or the colour planes themselves
+            real = bw_transform(present) if self.c.channels == 1 and present.shape[2] != 1 else present
             clips = {'real': real[:, self.c.skip:],
                      'rollout': self.stove.reconstruct_from_z(torch.cat([z_recon, z_pred], 1)),
                      'recon': self.stove.reconstruct_from_z(z_recon)}
@@ -480,6 +572,6 @@ class Trainer(AbstractTrainer):
             tag = 'final' if step_counter is None else '{:06d}'.format(step_counter)
             np.save(os.path.join(self.logger.rollout_states_dir, 'rollout_states_{}.npy'.format(tag)), out['z_pred'])
             for k in [k for k in out if k.startswith('frames_')]:
-                _save_clip(os.path.join(self.logger.rollout_gifs_dir, k[len('frames_'):]), out[k][0, :, 0])
+                _save_clip(os.path.join(self.logger.rollout_gifs_dir, k[len('frames_'):]), out[k][0] if out[k].shape[2] == 3 else out[k][0, :, 0])
         self.stove.train()
         return out
