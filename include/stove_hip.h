@@ -387,6 +387,23 @@ int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* N
                       int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
                       float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream);
 
+/* ---- The environments the planner plays: M avoidance / billiards environments stepped once and rendered, in place (csrc/env.hip,
+ * csrc/env_step.h; stove_amd/envs/envs.py -- PhysicsEnv.step, BillardsEnv.simulate_physics, AvoidanceTask.step, draw_image -- is the
+ * specification).  x, v (M, N, 2) double in/out; r, m (M, N) double; 1 <= N <= 6.  action (M,) indices into the nine directions of
+ * AvoidanceTask.action_selection (0: acting with zero force; ball 0 gets direction * action_force * t), or NULL: plain billiards, ball 0
+ * left alone and no collision counts as controlled.  `granularity` substeps of: x += t eps v; friction; walls on the next position;
+ * (nothing more with `drift`); the i > j pair loop with the controlled-ball rule.  collisions (M,): 1 if a controlled collision
+ * happened.  frames (M, 3, res, res) float or NULL: draw_image of the new state in float64 (BALL_COLOURS with use_colors, else ball i
+ * on channel i % 3), clamped at 1, rounded to float32 once.  Every operation on the state is an IEEE double add, multiply, divide or
+ * sqrt, uncontracted: x and v equal stove_amd/envs/batched.py's host arithmetic bit for bit.
+ * status (M,): 0 stepped; 2 the environment's action index is outside [0, 9) -- its x, v, collisions and frame are not written, the
+ * other environments are unaffected.  One launch on `stream`, no synchronisation (the call can be captured), no atomics.  A NULL x, v,
+ * r, m, collisions or status, M < 0, N outside 1 .. 6, granularity < 1, res < 1: hipErrorInvalidValue, nothing launched.  M == 0 is a
+ * valid empty call. */
+int stove_env_step(double* x, double* v, const double* r, const double* m, const int* action, int* collisions, int* status,
+                   float* frames, int M, int N, int granularity, int res, int use_colors, int drift, double hw, double t,
+                   double friction, double action_force, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

@@ -38,6 +38,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "plan.hip"
 #include "plan_tree.hip"
 #include "render.hip"
+#include "env.hip"
 
 namespace stove {
 
@@ -169,6 +170,7 @@ extern "C" {
 //     stove_plan_expand_ws_bytes, stove_plan_expand -- one expansion of a batch of search trees;
 //     stove_rollout_bwd_ws_bytes, stove_rollout_bwd and their _cl siblings -- the backward of both rollouts;
 //     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device;
+//     stove_env_step -- a batch of avoidance / billiards environments stepped and rendered in place (env.hip);
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in)
 int stove_abi_version(void) { return 7; }
 
@@ -1546,6 +1548,20 @@ int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* N
     STOVE_LAUNCH_CHECK();
   }
   STOVE_LAUNCH(plan_tree_action_k, dim3((M + 63) / 64), dim3(64), 0, st, first, Nsa, action, M, cap, A);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- the environments the planner plays: step and frame (env.hip)
+static_assert(stove_validate::kEnvMaxObjects == env_step::kMaxObjects, "validate.h admits what env_step.h holds");
+int stove_env_step(double* x, double* v, const double* r, const double* m, const int* action, int* collisions, int* status, float* frames,
+                   int M, int N, int granularity, int res, int use_colors, int drift, double hw, double t, double friction,
+                   double action_force, void* stream) {
+  STOVE_VALIDATE(env_step(x, v, r, m, collisions, status, M, N, granularity, res));
+  if (M == 0) return 0;
+  const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
+  STOVE_LAUNCH(env_step_k, dim3(M), dim3(kEnvThreads), 0, (hipStream_t)stream, x, v, r, m, action, collisions, status, frames, p, res,
+               use_colors != 0 ? 1 : 0);
   STOVE_LAUNCH_CHECK();
   return 0;
 }

@@ -240,6 +240,16 @@ inline int render_any(const float* bg, const float* patches, int frames_per_patc
   return 0;
 }
 
+// ---- stove_env_step: M environments of N balls stepped (and rendered at res x res) in place (csrc/env.hip).  M == 0 is a valid empty
+// call; action and frames are optional.  The action indices are device memory and are checked by the kernel (status).
+constexpr int kEnvMaxObjects = 6;
+inline int env_step(const double* x, const double* v, const double* r, const double* m, const int* collisions, const int* status, int M,
+                    int N, int granularity, int res) {
+  if (M < 0 || N < 1 || N > kEnvMaxObjects || granularity < 1 || res < 1) return kStoveInvalidValue;
+  if (M == 0) return 0;          // (arrays without elements have no address)
+  return (null_any(x, v, r, m) || null_any(collisions, status)) ? kStoveInvalidValue : 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

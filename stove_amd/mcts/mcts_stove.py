@@ -519,9 +519,15 @@ def run_mcts_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, m
 def plan_on_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False):
     """run_mcts_model (the reference's surface, whose parameter list stays the reference's) with the search's switches as arguments:
     `fused` as BatchedMCTSHandler.run_mcts takes it, `device_trees` as the handler's attribute of that name."""
+    return plan_on_frames(encode_img(img), model, actions, num_parallel_envs, mcts_steps, max_rollout_depth, fused, device_trees)
+
+
+def plan_on_frames(x, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False):
+    """plan_on_model on frames already in the model's layout: x (envs, time, channels, width, height) float32, on any device (frames
+    rendered on the model's device reach it without a host round trip)."""
     dev = next(model.parameters()).device
     with torch.no_grad():
-        _, prop_dict, _ = model(encode_img(img).to(dev), 0, actions=actions.to(dev), pretrain=False)
+        _, prop_dict, _ = model(x.to(dev), 0, actions=actions.to(dev), pretrain=False)
         apps = prop_dict['obj_appearances']
         all_mcts = [MCTS(apps[env:env + 1, -1] if apps is not None else None, prop_dict['z'][env:env + 1, -1],
                          max_rollout_depth=max_rollout_depth) for env in range(num_parallel_envs)]

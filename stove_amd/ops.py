@@ -994,6 +994,47 @@ def plan_search(z_pool, arrays, app, acts, emb_w, emb_b, gnn_params, rh_params, 
     return action
 
 
+def env_step(x, v, r, m, action, granularity, res, hw, t=1.0, friction=0.0, action_force=0.6, use_colors=True, drift=False, render=True,
+             out=None):
+    """One step of M avoidance / billiards environments (stove_env_step, csrc/env.hip).  x, v (M, N, 2) float64 device tensors are
+    updated in place; r, m (M, N) float64; action (M,) int32 indices into the nine directions, or None (plain billiards).
+    out: (frames (M, 3, res, res) float32 or None, collisions (M,) int32, status (M,) int32) to write into; None allocates them.
+    -> (frames or None with render=False, collisions, status); status 2: that environment's action index was outside [0, 9) and
+    nothing of it was written."""
+    lib = _lib.load()
+    for name, ten in (('x', x), ('v', v), ('r', r), ('m', m)):
+        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
+            raise RuntimeError('ops.env_step: %s must be a tensor on the GPU (the host path is BatchedAvoidance(device=None))' % name)
+        if ten.dtype != torch.float64 or not ten.is_contiguous() or ten.device != x.device:
+            raise RuntimeError('ops.env_step: %s must be a contiguous float64 tensor on %s' % (name, x.device))
+    if x.dim() != 3 or x.shape[2] != 2:
+        raise ValueError('ops.env_step: x must be (M, N, 2)')
+    M, N = x.shape[:2]
+    if tuple(v.shape) != (M, N, 2) or tuple(r.shape) != (M, N) or tuple(m.shape) != (M, N):
+        raise ValueError('ops.env_step: argument shapes do not fit M = %d environments of N = %d objects' % (M, N))
+    dev = x.device
+    if action is not None:
+        if not isinstance(action, torch.Tensor) or action.dtype != torch.int32 or action.device != dev or not action.is_contiguous():
+            raise RuntimeError('ops.env_step: action must be a contiguous int32 tensor on %s' % dev)
+        if tuple(action.shape) != (M,):
+            raise ValueError('ops.env_step: action is %s, the batch needs %s' % (tuple(action.shape), (M,)))
+    with torch.cuda.device(dev):
+        if out is None:
+            frames = torch.empty(M, 3, res, res, dtype=torch.float32, device=dev) if render else None
+            collisions = torch.empty(M, dtype=torch.int32, device=dev)
+            status = torch.empty(M, dtype=torch.int32, device=dev)
+        else:
+            frames, collisions, status = out
+            for name, ten, dt, shape in (('frames', frames, torch.float32, (M, 3, res, res)), ('collisions', collisions, torch.int32, (M,)),
+                                         ('status', status, torch.int32, (M,))):
+                if ten is not None and (ten.dtype != dt or ten.device != dev or not ten.is_contiguous() or tuple(ten.shape) != shape):
+                    raise RuntimeError('ops.env_step: out %s must be a contiguous %s tensor %s on %s' % (name, str(dt).split('.')[-1], shape, dev))
+        check(lib.stove_env_step(ptr(x), ptr(v), ptr(r), ptr(m), ptr(action), ptr(collisions), ptr(status), ptr(frames), M, N, int(granularity),
+                                 int(res), int(bool(use_colors)), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
+                                 stream()), 'stove_env_step')
+    return frames, collisions, status
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 

@@ -1,0 +1,317 @@
+"""CPU-side checks (-m "not gpu") of the batched avoidance environments and the episode driver: the step of stove_amd/csrc/env_step.h --
+the text the kernel of csrc/env.hip runs -- compiled host-only under sanitizers with contraction off (tests/abi/env_driver.cpp) and
+held to the numpy class BatchedAvoidance bit for bit; the numpy class held to envs.py (BillardsEnv + AvoidanceTask, themselves pinned
+to the reference by g0_envs.npz); play() and its rings; stove_env_step's host-side argument check; the C ABI addition exported,
+declared and bound.  (All fail before the feature: the header, the modules and the symbol do not exist.)"""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import env_cases as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ULP32 = 2.0 ** -23
+# test_numpy_class_against_envs_py: the largest |x| or |v| deviation between the numpy class and envs.py over all cases, measured on
+# the CPU this was written on, was 8.62e-14 (case n2); the smallest branch margin that is not an exact tie was 3.686e-4 (case n3_g50; 3.68e-4 below).
+# The bar is 100 x the former and stays below 1e-3 x the latter.
+MEASURED_DEVIATION, SMALLEST_MARGIN = 8.62e-14, 3.68e-4
+BAR = min(100 * MEASURED_DEVIATION, 1e-3 * SMALLEST_MARGIN)
+
+
+@pytest.fixture(scope='module')
+def driver(tmp_path_factory):
+    """the driver, built once with the flags of tests/test_plan_tree_cpu.py"""
+    cxx = shutil.which('g++') or shutil.which('c++')
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    exe = str(tmp_path_factory.mktemp('env_driver') / 'env_driver')
+    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-ffp-contract=off',
+                        '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'env_driver.cpp')], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+def _drive(exe, tmp_path, name, res=32):
+    b = C.start(name)
+    acts = C.actions(name)
+    M, N = b.M, b.n
+    src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.bin')
+    with open(src, 'wb') as fh:
+        fh.write(np.array([M, N, b.granularity, b.drift, acts is not None, C.STEPS, res, b.use_colors], dtype=np.int32).tobytes())
+        fh.write(np.array([b.hw, b.t, b.friction, b.action_force], dtype=np.float64).tobytes())
+        for a in (b.x, b.v, b.r, b.m):
+            fh.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        if acts is not None:
+            fh.write(np.ascontiguousarray(acts, dtype=np.int32).tobytes())
+    r = subprocess.run([exe, 'run', src, dst], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr                     # (a sanitizer report ends the driver with a non-zero status)
+    raw = open(dst, 'rb').read()
+    out, pos = {}, 0
+    for key, shape, dt in [('x', (C.STEPS, M, N, 2), np.float64), ('v', (C.STEPS, M, N, 2), np.float64), ('collisions', (C.STEPS, M), np.int32),
+                           ('status', (C.STEPS, M), np.int32), ('frame', (M, 3, res, res), np.float32)]:
+        n = int(np.prod(shape)) * np.dtype(dt).itemsize
+        out[key] = np.frombuffer(raw[pos:pos + n], dtype=dt).reshape(shape)
+        pos += n
+    assert pos == len(raw)
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ 1. header = numpy class, bit for bit
+@pytest.mark.parametrize('name', list(C.CASES))
+def test_header_equals_the_numpy_class_bit_for_bit(driver, tmp_path, name):
+    """env_step.h on the CPU (sanitizers, -ffp-contract=off) against BatchedAvoidance(device=None), both free-running for 24 steps of
+    seeded actions: x, v bit for bit, collisions equal; the end frame to one float32 ulp (exp is a library call on either side)."""
+    out, host = _drive(driver, tmp_path, name), C.host_run(name)
+    assert not out['status'].any()
+    assert np.array_equal(_bits(out['x']), _bits(host['x'])) and np.array_equal(_bits(out['v']), _bits(host['v']))
+    assert np.array_equal(out['collisions'], host['collisions'])
+    err = float(np.abs(out['frame'].astype(np.float64) - host['frame'].astype(np.float64)).max())
+    print(f'{name}: header frame against numpy frame {err:.3g}')
+    assert err <= ULP32
+    assert host['frame'].max() == 1.0 and host['frame'].min() == 0.0
+
+
+def test_the_trajectories_exercise_every_branch():
+    """at least one wall bounce, one free collision and one controlled collision (counted on the envs.py side), friction that slows
+    the free balls down, a drifting case whose balls pass through each other"""
+    runs = {name: C.envs_run(name) for name in C.CASES}
+    print({name: (r['wall_hits'], r['free_hits'], r['controlled_hits']) for name, r in runs.items()})
+    for name in ('n3', 'n6', 'n3_g50'):
+        assert runs[name]['wall_hits'] >= 1 and runs[name]['free_hits'] >= 1 and runs[name]['controlled_hits'] >= 1, name
+    assert runs['n1']['wall_hits'] >= 1 and runs['n2']['controlled_hits'] >= 1
+    assert runs['n3_none']['free_hits'] >= 1 and runs['n3_none']['controlled_hits'] == 0 and not runs['n3_none']['collisions'].any()
+    assert runs['n3_drift']['free_hits'] == runs['n3_drift']['controlled_hits'] == 0 and runs['n3_drift']['wall_hits'] >= 1
+    assert any(r['collisions'].any() for r in runs.values())
+    speed = np.sqrt((C.host_run('n3_fric')['v'][:, :, 1:] ** 2).sum(-1))
+    assert speed[-1].mean() < 0.5 * speed[0].mean()             # (1 - 0.05 / 5) ^ (5 x 23) = 0.31 for a ball nothing hits
+
+
+def test_validation_and_status_two_under_sanitizers(driver):
+    """stove_env_step's host-side argument check (csrc/validate.h: env_step) through the driver: every documented bad argument returns
+    hipErrorInvalidValue, an empty batch is accepted, nothing is dereferenced; and status 2: an action index of 9, -1 or 2^30 in
+    environment 1 of 3 leaves that environment as handed over and its neighbours as in a clean run, nothing read out of bounds."""
+    for mode in ('validate', 'status'):
+        r = subprocess.run([driver, mode], capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert '0 failure(s)' in r.stdout
+
+
+# ------------------------------------------------------------------------------------------------ 2. numpy class against envs.py
+def test_recording_subclass_is_envs_py():
+    """the instrumented subclass computes what BillardsEnv computes, bit for bit"""
+    from stove_amd.envs import envs
+    plain, acts = C.make_tasks('n3'), C.actions('n3')
+    rec = C.envs_run('n3')
+    for s in range(C.STEPS):
+        for e, task in enumerate(plain):
+            _, st, rew, _ = task.step(int(acts[s, e]))
+            assert np.array_equal(st[:, :2], rec['x'][s, e]) and np.array_equal(st[:, 2:], rec['v'][s, e]) and -rew == rec['collisions'][s, e]
+    assert isinstance(rec['tasks'][0].env, envs.BillardsEnv)
+
+
+@pytest.mark.parametrize('name', list(C.CASES))
+def test_numpy_class_against_envs_py(name):
+    """The same trajectories on envs.py.  The two differ only where BLAS norms / dots differ from the plain forms in the last bit,
+    amplified by collisions.  Every branch margin of the envs.py side (|next - r|, |next - (hw - r)|, |gap - (r_i + r_j)|) is an exact
+    tie that any arithmetic reproduces (the ball clamped to that wall and at rest on that axis) or >= 1e-6 -- no case and no step is
+    excluded -- so both sides take the same branches: collisions are equal, and x, v agree within BAR = 8.62e-12, which is 100 x the
+    largest deviation measured (8.62e-14, case n2) and below 1e-3 x the smallest non-tie margin measured (3.686e-4, case n3_g50)."""
+    ref, host = C.envs_run(name), C.host_run(name)
+    margins = np.array([m for m, tie in ref['margins'] if not tie])
+    ties = [m for m, tie in ref['margins'] if tie]
+    assert all(m == 0.0 for m in ties)
+    assert margins.min() >= 1e-6, margins.min()
+    assert margins.min() >= SMALLEST_MARGIN, margins.min()              # (the figure the bar was set from)
+    dev = max(float(np.abs(host['x'] - ref['x']).max()), float(np.abs(host['v'] - ref['v']).max()))
+    print(f'{name}: smallest margin {margins.min():.3g}, {len(ties)} exact ties, deviation {dev:.3g} (bar {BAR:.3g})')
+    assert np.array_equal(host['collisions'], ref['collisions'])
+    assert dev <= BAR
+
+
+@pytest.mark.parametrize('res,use_colors', [(32, True), (50, False), (32, False)])
+def test_frames_against_draw_image(res, use_colors):
+    """draw_image of the SAME state, cast to float32 and put in the model's layout, against the class's frame: <= 2^-23 (the two
+    sides differ only by last-bit float64 differences -- pow against two squarings, the centres -- before the single rounding)"""
+    from stove_amd.envs.batched import BatchedAvoidance
+    from stove_amd.mcts.mcts_stove import encode_img
+    for name in ('n3', 'n6'):
+        tasks = C.make_tasks(name, res=res, use_colors=use_colors)[:3]
+        b = BatchedAvoidance.from_tasks(tasks)
+        acts = C.actions(name)[:, :3]
+        for s in range(4):
+            frames, _ = b.step(acts[s])
+            twins = b.tasks()
+            want = encode_img(np.stack([t.env.draw_image() for t in twins])[None])[0].numpy()
+            assert frames.dtype == np.float32 and frames.shape == (3, 3, res, res) == want.shape
+            assert float(np.abs(frames.astype(np.float64) - want.astype(np.float64)).max()) <= ULP32
+            assert np.array_equal(frames, b.frames())
+        assert frames.max() == 1.0
+
+
+# ------------------------------------------------------------------------------------------------ 3. play and its rings
+def _hand_loop(tasks, run_len, seed):
+    """the reference's loop with random actions, written out: 8 warm-up steps with action 0, then one randint(9, size=M) per step"""
+    for t in tasks:
+        for _ in range(8):
+            t.step(0)
+    np.random.seed(seed)
+    acts, rews, states, frames = [], [], [], []
+    for _ in range(run_len):
+        a = np.random.randint(9, size=len(tasks))
+        res = [t.step(int(a[j])) for j, t in enumerate(tasks)]
+        acts.append(a)
+        frames.append(np.stack([r[0] for r in res]))
+        states.append(np.stack([r[1] for r in res]))
+        rews.append([r[2] for r in res])
+    _margins_fine(tasks)
+    return np.array(acts), np.array(rews, dtype=np.float64), np.array(states), np.array(frames)
+
+
+def _margins_fine(tasks):
+    """test 2's condition on trajectories other than its own (tasks built on C.Recording): every branch margin a tie or >= 1e-6"""
+    margins = [m for t in tasks for m, tie in t.env.margins if not tie]
+    assert min(margins) >= 1e-6, min(margins)
+
+
+def test_play_with_random_policy_on_lists_and_on_the_numpy_class():
+    from stove_amd.envs.batched import BatchedAvoidance
+    from stove_amd.mcts.play import play
+    run_len, seed = 6, 3
+    acts, rews, states, frames = _hand_loop(C.make_tasks('n3', cls=C.Recording), run_len, seed)
+    np.random.seed(seed)
+    got = play(None, C.make_tasks('n3'), run_len=run_len, policy='random', keep_frames=True)
+    assert set(got) == {'actions', 'rewards', 'states', 'frames'}
+    assert np.array_equal(got['actions'], acts) and np.array_equal(got['rewards'], rews) and np.array_equal(got['states'], states)
+    assert np.array_equal(got['frames'], np.transpose(frames, (0, 1, 4, 2, 3)).astype(np.float32))
+    np.random.seed(seed)
+    got = play(None, BatchedAvoidance.from_tasks(C.make_tasks('n3')), run_len=run_len, policy='random', keep_frames=True)
+    assert got['actions'].shape == (run_len, 8) and got['states'].shape == (run_len, 8, 3, 4) and got['frames'].shape == (run_len, 8, 3, 32, 32)
+    assert np.array_equal(got['actions'], acts) and np.array_equal(got['rewards'], rews)
+    assert float(np.abs(got['states'] - states).max()) <= BAR
+    assert float(np.abs(got['frames'].astype(np.float64) - np.transpose(frames, (0, 1, 4, 2, 3))).max()) <= ULP32
+    assert set(play(None, C.make_tasks('n3')[:2], run_len=0, policy='random')) == {'actions', 'rewards', 'states'}
+    with pytest.raises(ValueError, match='policy'):
+        play(None, C.make_tasks('n3')[:1], policy='greedy')
+    with pytest.raises(ValueError, match='model'):
+        play(None, C.make_tasks('n3')[:1], policy='mcts')
+
+
+@pytest.mark.parametrize('k', [1, 8, 9])
+def test_rings_hold_the_last_eight_in_time_order(k):
+    """after k steps (before, at and past one full turn) frame slot 7 - d is the frame d steps ago, zeros before the first step, and the
+    action slots the one-hot rows of the actions taken"""
+    from stove_amd.mcts.play import Rings
+    b = C.fresh('n3')
+    acts = C.actions('n3')
+    rings = Rings(b)
+    frames = []
+    for s in range(k):
+        rings.step(acts[s])
+        frames.append(b.frames())
+    x, a = rings.tensors()
+    assert x.shape == (8, 8, 3, 32, 32) and x.dtype == torch.float32 and a.shape == (8, 8, 9) and a.dtype == torch.float32
+    for slot in range(8):
+        s = k - 8 + slot                                   # the step this slot holds
+        if s < 0:
+            assert not x[:, slot].any() and not a[:, slot].any()
+        else:
+            assert np.array_equal(x[:, slot].numpy(), frames[s])
+            assert np.array_equal(a[:, slot].numpy(), np.eye(9, dtype=np.float32)[acts[s]])
+
+
+def test_warm_up_is_initialize_img():
+    """warm_up on the numpy class against initialize_img on the same environments: action rows equal, states within BAR (under test
+    2's condition on the margins of these eight steps), frames to one float32 ulp"""
+    from stove_amd.mcts.mcts_stove import encode_img, initialize_img
+    from stove_amd.mcts.play import warm_up
+    tasks = C.make_tasks('n3', cls=C.Recording)
+    img, actions = initialize_img(tasks, steps=8, res=32)
+    _margins_fine(tasks)
+    rings = warm_up(C.fresh('n3'))
+    x, a = rings.tensors()
+    assert torch.equal(a, actions)
+    assert float((x.double() - encode_img(img).double()).abs().max()) <= ULP32
+    assert float(np.abs(rings.envs.state() - np.stack([np.concatenate([t.env.x, t.env.v], 1) for t in tasks])).max()) <= BAR
+
+
+# ------------------------------------------------------------------------------------------------ 4. bookkeeping
+def test_env_step_symbol_is_exported_declared_and_bound():
+    from stove_amd import _lib, build, ops
+    build.build_library()
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), 'stove_env_step')
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
+    m = re.search(r'^int\s+stove_env_step\s*\(([^;]*?)\)\s*;', header, flags=re.M | re.S)
+    assert m, 'stove_env_step is not declared in include/stove_hip.h'
+    params = [a.strip() for a in m.group(1).split(',')]
+    fn = lib.stove_env_step
+    assert fn.restype is ctypes.c_int and len(fn.argtypes) == len(params) == 19
+    for ct, text in zip(fn.argtypes, params):
+        want = ctypes.c_void_p if '*' in text else (ctypes.c_double if text.startswith('double') else ctypes.c_int)
+        assert ct is want, (text, ct)
+    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7
+    assert callable(ops.env_step)
+    # host-visible nonsense is refused before anything touches a device (this machine has none): hipErrorInvalidValue == 1
+    P = ctypes.c_void_p
+    good = ctypes.create_string_buffer(64)
+    addr = ctypes.addressof(good)
+    call = lambda x=addr, M=1, N=3, gran=5, res=32: fn(P(x), P(addr), P(addr), P(addr), None, P(addr), P(addr), None, M, N, gran, res, 1, 0,
+                                                      10.0, 1.0, 0.0, 0.6, None)
+    assert call(x=None) == 1 and call(M=-1) == 1 and call(N=0) == 1 and call(N=7) == 1 and call(gran=0) == 1 and call(res=0) == 1
+    assert call(M=0) == 0
+    # the public surface
+    import model.envs.envs as menvs
+    import model.mcts.mcts_stove as mmcts
+    from stove_amd.envs.batched import BatchedAvoidance
+    from stove_amd.mcts import mcts_stove as sm
+    from stove_amd.mcts.play import play
+    assert menvs.BatchedAvoidance is BatchedAvoidance and mmcts.play is play and callable(sm.plan_on_frames)
+    assert sm.FUSED_WHERE_ELIGIBLE is False
+
+
+def test_refusals():
+    from stove_amd import ops
+    from stove_amd.envs import envs
+    from stove_amd.envs.batched import BatchedAvoidance
+    mk = lambda **k: envs.AvoidanceTask(envs.BillardsEnv(**dict(dict(n=3, hw=10, r=1., res=32, seed=0), **k)), action_force=0.6)
+    for other in (dict(n=2), dict(res=50), dict(granularity=10), dict(hw=12), dict(t=0.5), dict(friction_coefficient=0.1), dict(drift=True),
+                  dict(use_colors=False)):
+        with pytest.raises(ValueError, match='share'):
+            BatchedAvoidance.from_tasks([mk(), mk(**other)])
+    odd = mk()
+    odd.action_force = 0.3
+    with pytest.raises(ValueError, match='share action_force'):
+        BatchedAvoidance.from_tasks([mk(), odd])
+    with pytest.raises(ValueError, match='stays on the host'):
+        BatchedAvoidance.from_tasks([envs.AvoidanceTask(envs.GravityEnv(seed=0))])
+    with pytest.raises(ValueError, match='at least one'):
+        BatchedAvoidance.from_tasks([])
+    b = BatchedAvoidance(range(2))
+    assert (b.n, b.res, b.granularity, b.hw, b.action_force, b.M) == (3, 32, 5, 10.0, 0.6, 2) and b.m[:, 0].tolist() == [10000.0, 10000.0]
+    cpu = [torch.from_numpy(a) for a in (b.x, b.v, b.r, b.m)]
+    with pytest.raises(RuntimeError, match='GPU'):
+        ops.env_step(*cpu, None, 5, 32, 10.0)
+    # status 2 on the host class: environment 1 untouched, its twin neighbours as in a clean run
+    for bad in (9, -1):
+        t = BatchedAvoidance(([0, 1, 0]))
+        clean = BatchedAvoidance(([0, 1, 0]))
+        x1, v1 = t.x[1].copy(), t.v[1].copy()
+        frames, reward = t.step([1, bad, 1])
+        clean.step([1, 3, 1])
+        assert t.status.tolist() == [0, 2, 0] and np.array_equal(t.x[1], x1) and np.array_equal(t.v[1], v1) and reward[1] == 0
+        assert not frames[1].any() and np.array_equal(t.x[[0, 2]], clean.x[[0, 2]]) and np.array_equal(t.x[0], t.x[2])
+    # a round trip through tasks() carries the state and the settings
+    again = BatchedAvoidance.from_tasks(C.start('n3_fric').tasks())
+    for k in ('x', 'v', 'r', 'm'):
+        assert np.array_equal(getattr(again, k), getattr(C.start('n3_fric'), k)), k
+    assert again.friction == 0.05 and again.state().shape == (8, 3, 4)
