@@ -404,6 +404,29 @@ int stove_env_step(double* x, double* v, const double* r, const double* m, const
                    float* frames, int M, int N, int granularity, int res, int use_colors, int drift, double hw, double t,
                    double friction, double action_force, void* stream);
 
+/* ---- Tree search on those environments themselves (csrc/env_search.hip, csrc/env_search.h; the host forest EnvForest of
+ * stove_amd/mcts/mcts_env.py is the specification): R independent trees per environment, T = M R, tree e R + k searching from
+ * environment e's state x, v (M, N, 2), r, m (M, N) double, which is read only.  Nine actions, c = 1, rollout depth D >= 2.  Trees as in
+ * stove_plan_search: per tree `cap` entries, slot 0 the root, first, parent, depth, Ns, Nsa (T, cap) int32, Qsa (T, cap) double, used
+ * (T,) the next free slot; 1 + 9 runs slots always suffice.  draws (T, runs, D) int32 in [0, 9): iteration i of tree t reads row (t, i)
+ * from column 0 on.  One iteration replays its path from the root state: Descend takes the first-index argmax of Qsa + sqrt(log Ns /
+ * (1 + Nsa)) fresh at every level and steps; Expand (a node without children, key length < D) takes A fresh slots with Qsa = -1, Nsa =
+ * 0, steps with column 0 and rolls out D - length more steps with the following columns, value = minus the collisions counted;
+ * Terminal (key length D - 1, expanded) takes no step, value = Qsa of the edge drawn with column 0, counts edge 0 and leaves its Qsa
+ * alone.  Ns and Nsa are raised and Qsa averaged from there up to the root.  All `runs` iterations of all trees in one launch, then
+ * action[e] = first-index argmax of the root's Nsa summed over environment e's R trees (0 for an empty search).
+ * min_gap (T,) in/out: lowered to the smallest u_best - u_a over the Descend levels walked, among a whose (Qsa, Nsa) differ from the
+ * best's.  Qsa equals the host forest's bit for bit (no contraction; log is the only library call).
+ * status (T,) in/out: 0 searched; 1 out of slots (an expansion with used + 9 > cap); 2 a draw outside [0, 9) or a failed index check.
+ * A tree with non-zero status is frozen as it stood at the start of the offending iteration, the other trees unaffected; nothing is
+ * read or written out of bounds.  On `stream`, no synchronisation (the call can be captured), no atomics.  A NULL array, M < 0, R < 1,
+ * N outside 1 .. 6, D < 2, runs < 0, cap < 10, granularity < 1: hipErrorInvalidValue, nothing launched.  M == 0 is a valid empty call;
+ * with runs == 0 only `action` is written (draws may then be NULL). */
+int stove_env_search(const double* x, const double* v, const double* r, const double* m, const int* draws, int* first, int* parent,
+                     int* depth, int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap, int* status, int* action, int M, int R,
+                     int N, int D, int runs, int cap, int granularity, int drift, double hw, double t, double friction,
+                     double action_force, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

@@ -39,6 +39,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "plan_tree.hip"
 #include "render.hip"
 #include "env.hip"
+#include "env_search.hip"
 
 namespace stove {
 
@@ -171,6 +172,7 @@ extern "C" {
 //     stove_rollout_bwd_ws_bytes, stove_rollout_bwd and their _cl siblings -- the backward of both rollouts;
 //     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device;
 //     stove_env_step -- a batch of avoidance / billiards environments stepped and rendered in place (env.hip);
+//     stove_env_search -- tree search on those environments themselves, one launch per planning step (env_search.hip);
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in)
 int stove_abi_version(void) { return 7; }
 
@@ -1562,6 +1564,34 @@ int stove_env_step(double* x, double* v, const double* r, const double* m, const
   const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
   STOVE_LAUNCH(env_step_k, dim3(M), dim3(kEnvThreads), 0, (hipStream_t)stream, x, v, r, m, action, collisions, status, frames, p, res,
                use_colors != 0 ? 1 : 0);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- planning on the true environment: a whole search in one launch (env_search.hip)
+static_assert(stove_validate::kEnvActions == env_search::kActions, "validate.h sizes the trees for env_search.h's action count");
+int stove_env_search(const double* x, const double* v, const double* r, const double* m, const int* draws, int* first, int* parent, int* depth,
+                     int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap, int* status, int* action, int M, int R, int N, int D,
+                     int runs, int cap, int granularity, int drift, double hw, double t, double friction, double action_force, void* stream) {
+  STOVE_VALIDATE(env_search(x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, M, R, N, D, runs, cap,
+                            granularity));
+  if (M == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int T = M * R;
+  const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
+  if (runs > 0) {
+    switch (N) {
+      case 1: env_search_launch<1>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
+      case 2: env_search_launch<2>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
+      case 3: env_search_launch<3>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
+      case 4: env_search_launch<4>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
+      case 5: env_search_launch<5>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
+      default: env_search_launch<6>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
+    }
+    STOVE_LAUNCH_CHECK();
+  }
+  STOVE_LAUNCH(env_search_action_k, dim3((M + kEnvSearchThreads - 1) / kEnvSearchThreads), dim3(kEnvSearchThreads), 0, st, (const int*)first,
+               (const int*)Nsa, action, M, R, cap);
   STOVE_LAUNCH_CHECK();
   return 0;
 }

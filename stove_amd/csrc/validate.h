@@ -250,6 +250,24 @@ inline int env_step(const double* x, const double* v, const double* r, const dou
   return (null_any(x, v, r, m) || null_any(collisions, status)) ? kStoveInvalidValue : 0;
 }
 
+// ---- stove_env_search: R trees per environment searched on M environments of N balls (csrc/env_search.hip).  M == 0 is a valid empty
+// call, and so is runs == 0 (only `action` is written; draws may be NULL).  The table and the trees are device memory and are checked
+// by the kernel (status).
+constexpr int kEnvActions = 9;
+inline int env_search(const double* x, const double* v, const double* r, const double* m, const int* draws, const int* first,
+                      const int* parent, const int* depth, const int* Ns, const int* Nsa, const double* Qsa, const int* used,
+                      const double* min_gap, const int* status, const int* action, int M, int R, int N, int D, int runs, int cap,
+                      int granularity) {
+  if (M < 0 || R < 1 || N < 1 || N > kEnvMaxObjects || D < 2 || runs < 0 || cap < 1 + kEnvActions || granularity < 1)
+    return kStoveInvalidValue;
+  if ((long long)M * R > 0x7fffffffLL || (long long)runs * D > 0x7fffffffLL) return kStoveInvalidValue;
+  if (M == 0) return 0;          // (arrays without elements have no address)
+  if (null_any(x, v, r, m) || null_any(first, parent, depth, Ns, Nsa, used, status, action) || null_any(Qsa, min_gap) ||
+      (runs > 0 && draws == nullptr))
+    return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

@@ -1,5 +1,6 @@
 """Closed-loop planning: play avoidance episodes with the tree search on the learned model (reference scripts/run_mcts.py:
-main_mcts_model; policy='random' is scripts/random_env_baseline.py).
+main_mcts_model; policy='random' is scripts/random_env_baseline.py; policy='env_mcts' is main_mcts_env, the search on the
+environments themselves, mcts_env.py).
 
 Eight warm-up steps with action 0 fill a ring of the last 8 frames and a ring of the last 8 one-hot actions; then per step: plan on
 the rings, step every environment with the chosen action, shift both rings.  On a list of AvoidanceTask this is the reference's loop on
@@ -10,6 +11,7 @@ import numpy as np
 import torch
 
 from ..envs.batched import ACTIONS, BatchedAvoidance
+from .mcts_env import plan_on_envs
 from .mcts_stove import initialize_img, plan_on_frames, plan_on_model, update_buffer
 
 WARMUP = 8
@@ -69,14 +71,20 @@ def warm_up(envs):
     return rings
 
 
-def play(model, envs, run_len=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False, policy='mcts', keep_frames=False):
+def play(model, envs, run_len=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False, policy='mcts', keep_frames=False,
+         replicas=1):
     """One episode of every environment.  envs: a BatchedAvoidance (host or device) or a list of AvoidanceTask (the reference's
     per-environment loop).  policy: 'mcts' plans with `mcts_steps` expansions per tree on `model` (an action-conditioned Stove);
-    'random' draws one np.random.randint(9, size=M) per step and needs no model.
+    'random' draws one np.random.randint(9, size=M) per step and needs no model; 'env_mcts' searches the environments themselves
+    (mcts_env.plan_on_envs: `replicas` trees of `mcts_steps` iterations per environment, one np.random.randint(9, size=(M replicas,
+    mcts_steps, max_rollout_depth)) per step), needs no model either and looks at no frame; a list of AvoidanceTask goes through
+    BatchedAvoidance.from_tasks for the search only.  It raises ValueError for max_rollout_depth < 2, whatever run_len is.
     -> dict(actions (run_len, M) int64, rewards (run_len, M) float64, states (run_len, M, N, 4) float64 [, frames (run_len, M, 3, res,
     res) float32 with keep_frames]), the warm-up steps not included."""
-    if policy not in ('mcts', 'random'):
-        raise ValueError("policy is 'mcts' or 'random', not %r" % (policy,))
+    if policy not in ('mcts', 'random', 'env_mcts'):
+        raise ValueError("policy is 'mcts', 'random' or 'env_mcts', not %r" % (policy,))
+    if policy == 'env_mcts' and max_rollout_depth < 2:
+        raise ValueError('the search on the environments needs max_rollout_depth >= 2, not %r' % (max_rollout_depth,))
     if policy == 'mcts' and model is None:
         raise ValueError("policy='mcts' plans on a model")
     batched = isinstance(envs, BatchedAvoidance)
@@ -89,6 +97,8 @@ def play(model, envs, run_len=100, mcts_steps=100, max_rollout_depth=10, fused=N
     for _ in range(run_len):
         if policy == 'random':
             nxt = [int(a) for a in np.random.randint(ACTIONS, size=M)]
+        elif policy == 'env_mcts':
+            nxt = plan_on_envs(envs if batched else BatchedAvoidance.from_tasks(envs), mcts_steps, max_rollout_depth, replicas)
         elif batched:
             x, acts = rings.tensors()
             nxt = plan_on_frames(x, model, acts, M, mcts_steps, max_rollout_depth, fused, device_trees)

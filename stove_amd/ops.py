@@ -1035,6 +1035,53 @@ def env_step(x, v, r, m, action, granularity, res, hw, t=1.0, friction=0.0, acti
     return frames, collisions, status
 
 
+def env_search(x, v, r, m, draws, arrays, depth, granularity, hw, t=1.0, friction=0.0, action_force=0.6, drift=False, replicas=1):
+    """Tree search on M avoidance environments themselves (stove_env_search, csrc/env_search.hip): `replicas` trees per environment,
+    T = M replicas, all draws.shape[1] iterations in one launch, nothing synchronised.  x, v (M, N, 2), r, m (M, N) float64 device
+    tensors, the root states: read only.  draws (T, runs, depth) int32 in [0, 9).  arrays: dict of contiguous device tensors -- first,
+    parent, depth, Ns, Nsa (T, cap) int32, Qsa (T, cap) float64, used, status (T,) int32, min_gap (T,) float64 (EnvForest.to_device
+    makes them) --, updated in place.  -> action (M,) int32: the first-index argmax of the root's visit counts summed over an
+    environment's trees.  status[t] != 0 afterwards: tree t was frozen (1 out of slots, 2 a draw outside [0, 9) or a failed index check)."""
+    lib = _lib.load()
+    for name, ten in (('x', x), ('v', v), ('r', r), ('m', m)):
+        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
+            raise RuntimeError('ops.env_search: %s must be a tensor on the GPU (the host path is mcts_env.EnvForest)' % name)
+        if ten.dtype != torch.float64 or not ten.is_contiguous() or ten.device != x.device:
+            raise RuntimeError('ops.env_search: %s must be a contiguous float64 tensor on %s' % (name, x.device))
+    if x.dim() != 3 or x.shape[2] != 2:
+        raise ValueError('ops.env_search: x must be (M, N, 2)')
+    M, N = x.shape[:2]
+    if tuple(v.shape) != (M, N, 2) or tuple(r.shape) != (M, N) or tuple(m.shape) != (M, N):
+        raise ValueError('ops.env_search: argument shapes do not fit M = %d environments of N = %d objects' % (M, N))
+    R, D = int(replicas), int(depth)
+    if R < 1:
+        raise ValueError('ops.env_search: replicas must be at least 1')
+    dev, T = x.device, M * R
+    if not isinstance(draws, torch.Tensor) or draws.dtype != torch.int32 or draws.device != dev or not draws.is_contiguous():
+        raise RuntimeError('ops.env_search: draws must be a contiguous int32 tensor on %s' % dev)
+    if draws.dim() != 3 or draws.shape[0] != T or draws.shape[2] != D:
+        raise ValueError('ops.env_search: draws is %s, the search needs (%d, runs, %d)' % (tuple(draws.shape), T, D))
+    runs = draws.shape[1]
+    names = ('first', 'parent', 'depth', 'Ns', 'Nsa', 'Qsa', 'used', 'status', 'min_gap')
+    for name in names:
+        ten, want = arrays.get(name) if isinstance(arrays, dict) else None, torch.float64 if name in ('Qsa', 'min_gap') else torch.int32
+        if not isinstance(ten, torch.Tensor) or ten.dtype != want or ten.device != dev or not ten.is_contiguous():
+            raise RuntimeError('ops.env_search: %s must be a contiguous %s tensor on %s' % (name, str(want).split('.')[-1], dev))
+    cap = arrays['first'].shape[1] if arrays['first'].dim() == 2 else -1
+    for name in names:
+        shape = (T, cap) if name in names[:6] else (T,)
+        if tuple(arrays[name].shape) != shape:
+            raise ValueError('ops.env_search: %s is %s, the forest needs %s' % (name, tuple(arrays[name].shape), shape))
+    a = arrays
+    with torch.cuda.device(dev):
+        action = torch.zeros(M, dtype=torch.int32, device=dev)
+        check(lib.stove_env_search(ptr(x), ptr(v), ptr(r), ptr(m), ptr(draws), ptr(a['first']), ptr(a['parent']), ptr(a['depth']), ptr(a['Ns']),
+                                   ptr(a['Nsa']), ptr(a['Qsa']), ptr(a['used']), ptr(a['min_gap']), ptr(a['status']), ptr(action), M, R, N, D,
+                                   runs, cap, int(granularity), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
+                                   stream()), 'stove_env_search')
+    return action
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 

@@ -1,0 +1,108 @@
+"""Shared cases of the tests of the search on the true environment (tests/test_env_search_cpu.py, tests/test_gpu_env_search.py): the
+reference's recorded trees (tests/golden/g23_mcts_env.npz, tools/make_mcts_env_goldens.py), the seeded shape cases, and the host forest's
+search of each (computed once per case, never modified)."""
+import functools
+import os
+
+import numpy as np
+
+from stove_amd.envs.batched import BatchedAvoidance
+from stove_amd.mcts.mcts_env import EnvForest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+A, WARMUP = 9, 8
+ARRAYS = ('first', 'parent', 'depth', 'Ns', 'Nsa', 'Qsa')
+_R1 = (0, 1, 4, 8, 13, 15, 18, 21, 27, 29, 35, 37, 38, 42, 44, 49, 50, 53, 55, 56, 57, 62, 67, 69, 71, 72, 74, 75, 79, 82, 83, 88, 93, 97, 98, 100,
+       101, 102, 103, 108, 116, 117, 120, 122, 125, 126, 127, 128, 129, 130, 131, 132, 134, 137, 142, 146, 148, 154, 159, 160, 164, 165, 166,
+       167, 169)
+_R2 = (0, 4, 8, 13, 16, 18, 20, 27, 37, 42, 44, 49, 53, 54, 55, 56, 57, 62, 67, 69, 71, 74, 75, 78, 82, 83, 89, 90, 93, 97, 98, 99, 102, 103, 116,
+       117, 123, 126, 127, 128, 131, 132, 146, 148, 159, 160, 166, 169, 170, 175, 181, 183, 192, 194, 200, 201, 204, 206, 210, 211, 221, 222,
+       224, 225, 234)
+# name -> (R, N, D, runs, granularity, friction, drift, environment seeds); T = R x len(seeds): one tree; a few; one wave plus one lane;
+# two waves plus two lanes with two trees per environment.  Tree k of the environment with seed s reads the table of RandomState(500 + s R
+# + k), so a tree does not depend on its batch.  The seeds are those, in order from 0, all of whose trees have a host decision gap >= 1e-9
+# (asserted by the tests with no tree dropped).  Most others are out for one reason: an expansion worth exactly -1 leaves its node with
+# Ns = 1, edges (-1, 0) and one edge (-1, 1); at the next visit log(1) = 0 makes every u equal -1 and the gap, as it is defined, 0.
+CASES = {
+    't1_n1_d2': (1, 1, 2, 1, 5, 0.0, False, (0,)),
+    't4_n1_d3': (1, 1, 3, 12, 5, 0.0, False, (0, 1, 2, 3)),
+    't4_n3_d3': (1, 3, 3, 12, 5, 0.0, False, (0, 1, 2, 3)),
+    't65_n3_d10': (1, 3, 10, 40, 5, 0.0, False, _R1),
+    't130_r2_n3_d10': (2, 3, 10, 40, 5, 0.0, False, _R2),
+    't4_n6_d10': (1, 6, 10, 40, 5, 0.0, False, (1, 13, 16, 17)),
+    't4_n6_d2': (1, 6, 2, 12, 5, 0.0, False, (0, 1, 2, 3)),
+    't4_r4_n3_g50': (4, 3, 3, 12, 50, 0.0, False, (0,)),
+    't4_n3_fric': (1, 3, 10, 40, 5, 0.05, False, (2, 5, 6, 7)),
+    't4_n3_drift': (1, 3, 3, 12, 5, 0.0, True, (0, 1, 2, 3)),
+}
+CASES.update({'t4_n3_d%d_runs%d' % (D, runs): (1, 3, D, runs, 5, 0.0, False, (0, 1, 4, 8) if D == 10 else (0, 1, 2, 3))
+              for D in (2, 3, 10) for runs in (1, 12, 40)})
+assert len(_R1) == len(_R2) == 65
+
+
+def shape(name):
+    """-> (T, R, N, D, runs)"""
+    R, N, D, runs = CASES[name][:4]
+    return R * len(CASES[name][7]), R, N, D, runs
+
+
+@functools.lru_cache(maxsize=None)
+def golden():
+    """-> list of dicts, one per case of the golden file"""
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'g23_mcts_env.npz'))
+    out = []
+    for c in range(int(g['cases'])):
+        pre = 'c%d_' % c
+        out.append({k[len(pre):]: g[k] for k in g.files if k.startswith(pre)})
+    return out
+
+
+def golden_envs(G, copies=1, device=None):
+    """a BatchedAvoidance of `copies` environments at the golden case's root state"""
+    b = BatchedAvoidance([0] * copies, n=int(G['n']), hw=float(G['hw']), granularity=int(G['granularity']), action_force=float(G['action_force']),
+                         t=float(G['t']), friction_coefficient=float(G['friction']), drift=bool(G['drift']))
+    for k in ('x', 'v', 'r', 'm'):
+        setattr(b, k, np.ascontiguousarray(np.broadcast_to(G[k], (copies,) + G[k].shape), dtype=np.float64))
+    return b.to(device) if device is not None else b
+
+
+def golden_keys(G):
+    return ['r' + ''.join(str(int(d)) for d in row if d >= 0) for row in G['keys']]
+
+
+def assert_golden_tree(forest, tree, G):
+    """tree `tree` of `forest` is the reference's recorded tree: every key of the case, Nsa and Ns equal, Qsa bit for bit"""
+    keys = golden_keys(G)
+    assert int(forest.used[tree]) == 1 + len(keys) and int(forest.Ns[tree, 0]) == int(G['ns_root'])
+    for key, nsa, qsa, ns, expanded in zip(keys, G['nsa'], G['qsa'], G['ns'], G['expanded']):
+        s = forest.slot_of(tree, key)
+        assert s >= 1, key
+        assert forest.Nsa[tree, s] == nsa and forest.Ns[tree, s] == ns and (forest.first[tree, s] >= 0) == bool(expanded), key
+        assert forest.Qsa[tree, s].tobytes() == np.float64(qsa).tobytes(), key
+
+
+@functools.lru_cache(maxsize=None)
+def start(name):
+    """-> (a host BatchedAvoidance of T / R environments after WARMUP steps of action 0, draws (T, runs, D) int32), both shared: search
+    them, never step or write them"""
+    R, N, D, runs, gran, fric, drift, seeds = CASES[name]
+    b = BatchedAvoidance(seeds, n=N, granularity=gran, friction_coefficient=fric, drift=drift)
+    for _ in range(WARMUP):
+        b.step(np.zeros(b.M, dtype=np.int64), render=False)
+    draws = np.stack([np.random.RandomState(500 + s * R + k).randint(A, size=(runs, D)) for s in seeds for k in range(R)]).astype(np.int32)
+    for a in (b.x, b.v, b.r, b.m, draws):
+        a.setflags(write=False)
+    return b, draws
+
+
+@functools.lru_cache(maxsize=None)
+def host_search(name):
+    """-> (the EnvForest after searching case `name`, action (M,)); read only"""
+    T, R, _, D, runs = shape(name)
+    b, draws = start(name)
+    f = EnvForest(T, A, D, runs)
+    action = f.search(b, draws, R)
+    for k in ARRAYS + ('used', 'status', 'gap'):
+        getattr(f, k).setflags(write=False)
+    action.setflags(write=False)
+    return f, action
