@@ -427,6 +427,32 @@ int stove_env_search(const double* x, const double* v, const double* r, const do
                      int N, int D, int runs, int cap, int granularity, int drift, double hw, double t, double friction,
                      double action_force, void* stream);
 
+/* ---- The model-free PPO arm on states: S steps of B of those environments under a policy, next_value and the discounted returns in
+ * one launch (csrc/ppo_collect.hip, csrc/ppo_policy.h; the host forest PolicyForest of stove_amd/rl/collect.py is the specification).
+ * The policy is Policy(base='control') of stove_amd/rl/rl_model.py: Linear(4N, 128), ReLU, Linear(128, 32), ReLU, Linear(32, H), ReLU
+ * [with `deep`: Linear(H, H), ReLU, Linear(H, H), ReLU], then the value (H -> 1) and nine logits (H -> 9); 1 <= N <= 6, 1 <= H <= 128.
+ * params: stove_ppo_param_floats(N, H, deep) floats (0 for an N or H outside its range), the layers in that order, each as its
+ * TRANSPOSED weight wT[k * out + j] = weight[j][k] followed by its bias (out); the last layer is the two heads side by side, out = 10,
+ * column 0 the value head, columns 1 .. 9 the actor head (Policy.flat_params() writes it).
+ * Step s of environment b: obs[b][s] = (x[i][0], x[i][1], v[i][0], v[i][1])_i rounded to float32; every neuron is one float32 sum
+ * that starts at its bias and adds w[k] * in[k] for k ascending, uncontracted; values[b][s] the value; the action is drawn from the
+ * logits with the caller's uniform u[b][s] in [0, 1): d_a = l_a - max l in float32, c_a the running double sum of exp(d_a), the first a
+ * with c_a > u c_8 (else 8), logp = d_a - log c_8 rounded to float32; then stove_env_step's step with that action, rewards[b][s] =
+ * -collisions.  After step S - 1: obs[b][S], next_value[b] the value there, returns[b][s] = returns[b][s + 1] * discount + rewards[b][s]
+ * in float32 (discount rounded to float32 once).  x, v (B, N, 2) double in/out; r, m (B, N) double; u, rewards, values, logp, returns
+ * (B, S) float; actions (B, S) int32; obs (B, S + 1, 4N) float; next_value (B,) float.  Everything but logp (exp, log) equals the host
+ * forest bit for bit wherever the uniform is not within a last-bit error of exp of a boundary.
+ * status (B,): 0 collected; 3 a value or logit was not finite at some step: nothing of that step or after it is written (no obs row, no
+ * next_value, no returns), x and v stand as the steps before left them, the other environments are unaffected.  One launch on `stream`,
+ * no synchronisation (the call can be captured), no atomics.  A NULL array, B < 0, S < 0, N outside 1 .. 6, H outside 1 .. 128,
+ * granularity < 1: hipErrorInvalidValue, nothing launched.  B == 0 is a valid empty call; with S == 0 only obs (B, 1, 4N), next_value
+ * and status are written (the (B, S) arrays may then be NULL). */
+size_t stove_ppo_param_floats(int N, int H, int deep);
+int stove_ppo_collect(double* x, double* v, const double* r, const double* m, const float* params, const float* u, float* obs,
+                      int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status, int B,
+                      int S, int N, int H, int deep, int granularity, int drift, double hw, double t, double friction,
+                      double action_force, double discount, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

@@ -40,6 +40,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "render.hip"
 #include "env.hip"
 #include "env_search.hip"
+#include "ppo_collect.hip"
 
 namespace stove {
 
@@ -173,7 +174,8 @@ extern "C" {
 //     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device;
 //     stove_env_step -- a batch of avoidance / billiards environments stepped and rendered in place (env.hip);
 //     stove_env_search -- tree search on those environments themselves, one launch per planning step (env_search.hip);
-//     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in)
+//     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in;
+//     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip))
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1594,6 +1596,29 @@ int stove_env_search(const double* x, const double* v, const double* r, const do
                (const int*)Nsa, action, M, R, cap);
   STOVE_LAUNCH_CHECK();
   return 0;
+}
+
+// ---------------------------------------------------------------- the PPO arm: a batch of trajectories in one launch (ppo_collect.hip)
+static_assert(stove_validate::kPpoMaxHidden == ppo_policy::kMaxHidden, "validate.h admits what ppo_policy.h holds");
+size_t stove_ppo_param_floats(int N, int H, int deep) {
+  if (N < 1 || N > env_step::kMaxObjects || H < 1 || H > ppo_policy::kMaxHidden) return 0;
+  return ppo_policy::param_floats(ppo_policy::Shape{N, H, deep != 0 ? 1 : 0});
+}
+int stove_ppo_collect(double* x, double* v, const double* r, const double* m, const float* params, const float* u, float* obs, int* actions,
+                      float* rewards, float* values, float* logp, float* next_value, float* returns, int* status, int B, int S, int N, int H,
+                      int deep, int granularity, int drift, double hw, double t, double friction, double action_force, double discount,
+                      void* stream) {
+  STOVE_VALIDATE(ppo_collect(x, v, r, m, params, u, obs, actions, rewards, values, logp, next_value, returns, status, B, S, N, H, granularity));
+  if (B == 0) return 0;
+  const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
+  const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
+  const size_t n = ppo_policy::param_floats(sh), lds = ppo_lds_bytes(n);
+  const dim3 grid((B + kPpoWaves - 1) / kPpoWaves), block(kPpoThreads);
+  if (ppo_staged(n))
+    return STOVE_LAUNCH_LDS(ppo_collect_k<true>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards, values, logp,
+                            next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
+  return STOVE_LAUNCH_LDS(ppo_collect_k<false>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards, values, logp,
+                          next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
 }
 
 // ---------------------------------------------------------------- stream ordering / graph replay helpers

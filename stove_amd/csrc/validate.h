@@ -268,6 +268,21 @@ inline int env_search(const double* x, const double* v, const double* r, const d
   return 0;
 }
 
+// ---- stove_ppo_collect: S steps of B environments of N balls under a policy of head width H (csrc/ppo_collect.hip).  B == 0 is a valid
+// empty call; with S == 0 only obs (B, 1, 4N), next_value and status are written and the (B, S) arrays may be NULL.  Everything the
+// pointers name is device memory: a non-finite policy output is found by the kernel (status).
+constexpr int kPpoMaxHidden = 128;
+inline int ppo_collect(const double* x, const double* v, const double* r, const double* m, const float* params, const float* u,
+                       const float* obs, const int* actions, const float* rewards, const float* values, const float* logp,
+                       const float* next_value, const float* returns, const int* status, int B, int S, int N, int H, int granularity) {
+  if (B < 0 || S < 0 || N < 1 || N > kEnvMaxObjects || H < 1 || H > kPpoMaxHidden || granularity < 1) return kStoveInvalidValue;
+  if ((long long)B * ((long long)S + 1) * 4 * N > 0x7fffffffLL) return kStoveInvalidValue;
+  if (B == 0) return 0;          // (arrays without elements have no address)
+  if (null_any(x, v, r, m) || null_any(params, obs, next_value) || status == nullptr) return kStoveInvalidValue;
+  if (S > 0 && (null_any(u, rewards, values, logp, returns) || actions == nullptr)) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

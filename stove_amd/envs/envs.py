@@ -54,6 +54,15 @@ class PhysicsEnv:
             v = v * self.rng.uniform(1 / init_v_factor, init_v_factor)
         return v
 
+    def reset(self, init_v_factor=None):
+        """a new configuration, drawn in the reference's order -- velocities first, then positions"""
+        self.v = self.init_v(init_v_factor)
+        self.a = np.zeros_like(self.v)
+        self.x = self.init_x()
+
+    def get_state_shape(self):
+        return np.concatenate([self.x, self.v], axis=1).shape
+
     # -- dynamics -------------------------------------------------------------------------
     def simulate_physics(self, actions):
         raise NotImplementedError

@@ -1082,6 +1082,63 @@ def env_search(x, v, r, m, draws, arrays, depth, granularity, hw, t=1.0, frictio
     return action
 
 
+def ppo_param_floats(N, H, deep):
+    """length of the parameter image stove_ppo_collect reads (Policy.flat_params() writes it)"""
+    return int(_lib.load().stove_ppo_param_floats(int(N), int(H), int(bool(deep))))
+
+
+def ppo_collect(x, v, r, m, params, u, hidden, deep, granularity, hw, t=1.0, friction=0.0, action_force=0.3, drift=False, discount=0.95,
+                out=None):
+    """The PPO arm's collection on states (stove_ppo_collect, csrc/ppo_collect.hip): S = u.shape[1] steps of B avoidance environments
+    under Policy(base='control') with head width `hidden`, next_value and the discounted returns in one launch, nothing synchronised.
+    x, v (B, N, 2) float64 device tensors are updated in place; r, m (B, N) float64; params the float32 image of
+    ppo_param_floats(N, hidden, deep) entries (Policy.flat_params()); u (B, S) float32 uniforms in [0, 1), one per draw.
+    out: a dict of the tensors to write into (obs (B, S + 1, 4N), rewards, values, logp, returns (B, S), next_value (B,) float32,
+    actions (B, S), status (B,) int32); None allocates them (zeros).  -> that dict; status 3: a value or logit of that environment was
+    not finite, nothing of that step or after it was written and its state stands as the steps before left it."""
+    lib = _lib.load()
+    for name, ten in (('x', x), ('v', v), ('r', r), ('m', m)):
+        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
+            raise RuntimeError('ops.ppo_collect: %s must be a tensor on the GPU (the host path is rl.collect.PolicyForest)' % name)
+        if ten.dtype != torch.float64 or not ten.is_contiguous() or ten.device != x.device:
+            raise RuntimeError('ops.ppo_collect: %s must be a contiguous float64 tensor on %s' % (name, x.device))
+    if x.dim() != 3 or x.shape[2] != 2:
+        raise ValueError('ops.ppo_collect: x must be (B, N, 2)')
+    B, N = x.shape[:2]
+    if tuple(v.shape) != (B, N, 2) or tuple(r.shape) != (B, N) or tuple(m.shape) != (B, N):
+        raise ValueError('ops.ppo_collect: argument shapes do not fit B = %d environments of N = %d objects' % (B, N))
+    dev, H, deep = x.device, int(hidden), int(bool(deep))
+    if not 1 <= N <= 6 or not 1 <= H <= 128:
+        raise ValueError('ops.ppo_collect: the kernel serves 1 .. 6 objects and head widths 1 .. 128, not N = %d, hidden = %d' % (N, H))
+    for name, ten in (('params', params), ('u', u)):
+        if not isinstance(ten, torch.Tensor) or ten.dtype != torch.float32 or ten.device != dev or not ten.is_contiguous():
+            raise RuntimeError('ops.ppo_collect: %s must be a contiguous float32 tensor on %s' % (name, dev))
+    n = ppo_param_floats(N, H, deep)
+    if tuple(params.shape) != (n,):
+        raise ValueError('ops.ppo_collect: params is %s, the policy needs (%d,)' % (tuple(params.shape), n))
+    if u.dim() != 2 or u.shape[0] != B:
+        raise ValueError('ops.ppo_collect: u is %s, the batch needs (%d, S)' % (tuple(u.shape), B))
+    S = u.shape[1]
+    shapes = {'obs': ((B, S + 1, 4 * N), torch.float32), 'actions': ((B, S), torch.int32), 'rewards': ((B, S), torch.float32),
+              'values': ((B, S), torch.float32), 'logp': ((B, S), torch.float32), 'next_value': ((B,), torch.float32),
+              'returns': ((B, S), torch.float32), 'status': ((B,), torch.int32)}
+    with torch.cuda.device(dev):
+        if out is None:
+            out = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        for name, (shape, dt) in shapes.items():
+            ten = out.get(name) if isinstance(out, dict) else None
+            if not isinstance(ten, torch.Tensor) or ten.dtype != dt or ten.device != dev or not ten.is_contiguous():
+                raise RuntimeError('ops.ppo_collect: out %s must be a contiguous %s tensor on %s' % (name, str(dt).split('.')[-1], dev))
+            if tuple(ten.shape) != shape:
+                raise ValueError('ops.ppo_collect: out %s is %s, the batch needs %s' % (name, tuple(ten.shape), shape))
+        o = out
+        check(lib.stove_ppo_collect(ptr(x), ptr(v), ptr(r), ptr(m), ptr(params), ptr(u), ptr(o['obs']), ptr(o['actions']), ptr(o['rewards']),
+                                    ptr(o['values']), ptr(o['logp']), ptr(o['next_value']), ptr(o['returns']), ptr(o['status']), B, S, N, H,
+                                    deep, int(granularity), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
+                                    float(discount), stream()), 'stove_ppo_collect')
+    return out
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 

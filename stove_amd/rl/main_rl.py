@@ -1,0 +1,111 @@
+"""Train the model-free PPO arm (counterpart of the reference's model/rl/main_rl.py): `parse_args` carries the reference's flags,
+`main` serves `--use-states` on the billiards environment under the avoidance task.  `--device-envs` keeps the batch of environments
+on the GPU, where a batch of trajectories is one launch (stove_ppo_collect); without it the collection runs on the host
+(collect.PolicyForest) and only the update uses the device.  The image, gym and pretrained-model variants are not part of this package."""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from ..envs.envs import AvoidanceTask, BillardsEnv
+from .agents import PPOAgent
+from .rl_model import Policy
+from .runners import PPORunner
+
+
+def parse_args(args):
+    parser = argparse.ArgumentParser(description='RL')
+    parser.add_argument('--experiment_id', default='ppo', help='name of the experiment')
+    parser.add_argument('--env', default='billards', help='environment to use: billards')
+    parser.add_argument('--task', default='avoidance', help='task to learn if training: avoidance | maxdist | mindist')
+    parser.add_argument('--seed', type=int, default=0, help='random seed')
+    parser.add_argument('--lr', type=float, default=2e-4, help='learning rate')
+    parser.add_argument('--clip-param', type=float, default=0.1, help='ppo clip parameter')
+    parser.add_argument('--num-steps', type=int, default=128, help='number of forward steps in PPO')
+    parser.add_argument('--batch-size', type=int, default=32, help='number of trajectories sampled per batch')
+    parser.add_argument('--num-env-steps', type=int, default=10000000, help='number of total environment steps')
+    parser.add_argument('--num-ppo-mb', type=int, default=32, help='number of batches for ppo')
+    parser.add_argument('--num-ppo-epochs', type=int, default=4, help='number of epochs for ppo')
+    parser.add_argument('--save-interval', type=int, default=100, help='save interval, one save per n batches')
+    parser.add_argument('--value-loss-coef', type=float, default=0.5, help='value loss coefficient')
+    parser.add_argument('--entropy-coef', type=float, default=0.01, help='entropy term coefficient')
+    parser.add_argument('--eps', type=float, default=1e-5, help='Adam optimizer epsilon')
+    parser.add_argument('--max-grad-norm', type=float, default=40, help='max norm of gradients')
+    parser.add_argument('--summary-dir', type=str, default='./summary/', help='directory to save args (and summaries of a writer)')
+    parser.add_argument('--model-dir', type=str, default='./models/', help='directory to save models')
+    parser.add_argument('--hidden-size', type=int, default=512, help='hidden size in the policy head (image variant)')
+    parser.add_argument('--gym', action='store_true', default=False, help='whether or not to use gym as environment')
+    parser.add_argument('--use-states', action='store_true', default=False, help='use states instead of images when true')
+    parser.add_argument('--use-deep-layers', action='store_true', default=False, help='use more linear layers in head')
+    parser.add_argument('--num-balls', type=int, default=3, help='number of balls to simulate in the environment')
+    parser.add_argument('--radius', type=float, default=1., help='radius of each ball in the environment')
+    parser.add_argument('--gran', type=int, default=2, help='granularity of the simulation in the environment')
+    parser.add_argument('--dt', type=float, default=1., help='dt of the simulation computed in each time step')
+    parser.add_argument('--action-force', type=float, default=.3, help='action force of the task simulation')
+    parser.add_argument('--num-stacked-frames', type=int, default=4, help='number of frames stacked as inputs')
+    parser.add_argument('--use-grid', action='store_true', default=False, help='add grid information to the visual input')
+    parser.add_argument('--use-pretrained-model', action='store_true', default=False, help='use the pretrained model as world model')
+    parser.add_argument('--device-envs', action='store_true', default=False,
+                        help='keep the environments on the GPU: a batch of trajectories is one launch')
+    parser.add_argument('--device', default=None, help='device of the policy (default: cuda when there is one)')
+    args = parser.parse_args(args)
+    assert args.task in ['avoidance', 'maxdist', 'mindist']
+    assert not (args.gym and args.use_states)
+    assert not (args.gym and args.use_pretrained_model)
+    assert not (args.use_states and args.use_pretrained_model)
+    if not args.gym:
+        assert args.env in ['billards']
+    return args
+
+
+def save_args(args, path):
+    with open(os.path.join(path, 'args.json'), 'w') as fp:
+        json.dump(vars(args), fp, sort_keys=True, indent=4)
+
+
+def build(args, writer=None):
+    """-> (runner, actor_critic) for parsed `args`"""
+    if not args.use_states or args.gym or args.use_pretrained_model or args.task != 'avoidance':
+        raise NotImplementedError('this package trains the avoidance task on states (--use-states); the image, gym, pretrained-model '
+                                  'and distance-task variants are not part of it')
+    env = BillardsEnv(n=args.num_balls, r=args.radius, granularity=args.gran, t=args.dt, seed=args.seed)
+    task = AvoidanceTask(env, num_stacked=args.num_stacked_frames, action_force=args.action_force, greyscale=False)
+    shape = env.get_state_shape()
+    actor_critic = Policy(shape[0] * shape[1], task.get_action_space(), hidden_size=64, base='control')
+    agent = PPOAgent(actor_critic, args.clip_param, args.num_ppo_epochs, args.num_ppo_mb, args.value_loss_coef, args.entropy_coef, args.lr,
+                     args.eps, args.max_grad_norm)
+    device = args.device or ('cuda' if torch.cuda.is_available() else 'cpu')
+    if args.device_envs and torch.device(device).type != 'cuda':
+        raise ValueError('--device-envs needs a GPU')
+    runner = PPORunner(env=env, task=task, summary_path=os.path.join(args.summary_dir, args.experiment_id), device=device, agent=agent,
+                       actor_critic=actor_critic, num_steps=args.num_steps, batch_size=args.batch_size, discount=0.95, writer=writer,
+                       device_envs=bool(args.device_envs))
+    return runner, actor_critic
+
+
+def main(args, writer=None):
+    args = parse_args(args)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    model_path = os.path.join(args.model_dir, args.experiment_id)
+    summary_path = os.path.join(args.summary_dir, args.experiment_id)
+    os.makedirs(model_path, exist_ok=True)
+    os.makedirs(summary_path, exist_ok=True)
+    save_args(args, summary_path)
+    runner, actor_critic = build(args, writer)
+    num_batches = int(args.num_env_steps) // args.num_steps // args.batch_size
+    save = lambda i: torch.save(actor_critic.state_dict(), os.path.join(model_path, 'model' + str(i) + '.pt'))
+    i = 0
+    try:
+        for i in range(num_batches):
+            runner.run_batch_states()
+            if i % args.save_interval == 0:
+                save(i)
+    except BaseException:
+        save(i)
+        raise
+    if not os.path.isfile(os.path.join(model_path, 'model' + str(i) + '.pt')):
+        save(i)
+    return runner

@@ -1,0 +1,178 @@
+"""Collect a batch of trajectories on states and update the policy (counterpart of the reference's model/rl/runners.py, the
+`--use-states` path).  The reference walks its batch_size environments one after the other, num_steps each, with a one-row
+`Policy.act`, a `.cpu()` and a numpy step per step.  Here the batch_size start states are drawn first, exactly as the reference draws
+them (`reset()` plus one step with action 0 on the one environment object, in order), and then stepped together:
+
+  on a device, one ops.ppo_collect launch (stove_ppo_collect) when the policy is one the kernel serves, else -- or with fused=False --
+  composed: per step one batched `policy.act` and one `BatchedAvoidance.step(render=False)`, nothing synchronised;
+  on the host, `collect.PolicyForest`, the numpy specification of that kernel.
+
+All three draw action s of environment b from the same uniform u[b][s] (collect.py says why the reference's stream is not
+reproduced), so they agree action for action wherever no draw sits within rounding of a boundary.  Logging goes to an optional
+`writer` with an `add_scalar(key, value, step)` method (a tensorboardX SummaryWriter fits); none is required."""
+import numpy as np
+import torch
+
+from ..envs.batched import BatchedAvoidance
+from . import collect as _collect
+
+
+class BatchStorage:
+    def __init__(self, batch_size, num_steps, obs_shape, device):
+        self.obs = torch.zeros((batch_size, num_steps + 1, *obs_shape)).to(device)
+        self.actions = torch.zeros((batch_size, num_steps, 1)).to(device)
+        self.rewards = torch.zeros((batch_size, num_steps, 1)).to(device)
+        self.values = torch.zeros((batch_size, num_steps, 1)).to(device)
+        self.dones = torch.zeros((batch_size, num_steps, 1)).to(device)
+        self.action_log_probs = torch.zeros((batch_size, num_steps, 1)).to(device)
+
+    def insert(self, b, step, o, a, r, v, d, alp):
+        self.obs[b, step + 1] = torch.as_tensor(o)
+        self.rewards[b, step] = torch.as_tensor(r)
+        self.dones[b, step] = torch.as_tensor(d)
+        self.actions[b, step] = a
+        self.values[b, step] = v
+        self.action_log_probs[b, step] = alp
+
+    def insert_batch(self, step, o, a, r, v, d, alp):
+        self.obs[:, step + 1] = o
+        self.rewards[:, step] = r
+        self.dones[:, step] = d
+        self.actions[:, step] = a
+        self.values[:, step] = v
+        self.action_log_probs[:, step] = alp
+
+
+class Runner:
+    def __init__(self, env, task, summary_path, device, agent, actor_critic, num_steps, batch_size, discount, do_train, writer=None):
+        self.env, self.task = env, task
+        self.summary_path = summary_path
+        dev = None if device is None else torch.device(device)
+        self.device = torch.device('cpu') if dev is None else dev
+        self.agent, self.actor_critic = agent, actor_critic
+        self.num_steps, self.batch_size, self.discount, self.do_train = num_steps, batch_size, discount, do_train
+        self.summary_writer = writer
+        self.batch_counter = 0
+        self.episode_counter = 0
+        self.actor_critic.to(self.device)
+
+    def _calculate_returns(self, next_value, rewards, dones):
+        """next_value (b, 1), rewards, dones (b, n, 1) -> the discounted returns (b, n, 1)"""
+        returns = torch.zeros((rewards.size(0), rewards.size(1) + 1, 1), dtype=rewards.dtype, device=rewards.device)
+        returns[:, -1] = next_value
+        for step in reversed(range(rewards.size(1))):
+            returns[:, step] = returns[:, step + 1] * self.discount * (1 - dones[:, step]) + rewards[:, step]
+        return returns[:, :-1]
+
+    def _log_to_tb(self, log_dict, use_total_steps=True):
+        if self.summary_writer is None:
+            return
+        counter = self.batch_counter * self.num_steps * self.batch_size if use_total_steps else self.batch_counter
+        for key, value in log_dict.items():
+            self.summary_writer.add_scalar(key, value, counter)
+
+    def reset(self):
+        """a new configuration and one step with action 0, as the reference starts every trajectory -> (frame, state)"""
+        self.env.reset()
+        img, state, _, _ = self.task.step(0)
+        return img, state
+
+    def run_batch(self):
+        raise NotImplementedError
+
+
+class PPORunner(Runner):
+    def __init__(self, env, task, summary_path=None, device=None, agent=None, actor_critic=None, num_steps=128, batch_size=32, discount=0.99,
+                 do_train=True, writer=None, device_envs=None):
+        """device_envs: False keeps the environments on the host while the policy is updated on `device`; None / True: they live where
+        the policy lives"""
+        super().__init__(env, task, summary_path, device, agent, actor_critic, num_steps, batch_size, discount, do_train, writer)
+        self.env_device = self.device if device_envs is None or device_envs else torch.device('cpu')
+        if self.env_device.type == 'cuda' and self.device.type != 'cuda':
+            raise ValueError('device_envs needs the policy on a GPU')
+
+    # ------------------------------------------------------------------------------------------------ the collection
+    def start_batch(self, batch_size):
+        """batch_size start states drawn one after the other from the runner's environment -> a host BatchedAvoidance holding them"""
+        xs, vs = [], []
+        for _ in range(batch_size):
+            self.reset()
+            xs.append(np.array(self.env.x, dtype=np.float64))
+            vs.append(np.array(self.env.v, dtype=np.float64))
+        batch = BatchedAvoidance.from_tasks([self.task] * batch_size)
+        batch.x, batch.v = np.stack(xs), np.stack(vs)
+        return batch
+
+    def fused_serves(self):
+        return self.env_device.type == 'cuda' and self.actor_critic.kernel_shape() is not None
+
+    def collect(self, batch_size, num_steps, fused=None, u=None):
+        """-> (dict of obs (B, S + 1, 4N), rewards, values, logp, returns (B, S), next_value (B,) float32, actions (B, S), status (B,),
+        as tensors on the runner's device; the stepped BatchedAvoidance).  u: the (B, S) float32 table of uniforms, drawn from numpy's
+        global stream when None."""
+        if u is None:
+            u = np.random.random_sample((batch_size, num_steps)).astype(np.float32).clip(max=np.float32(1) - np.float32(2) ** -24)
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape != (batch_size, num_steps):
+            raise ValueError('u is %s, the batch needs %s' % (u.shape, (batch_size, num_steps)))
+        if fused and not self.fused_serves():
+            raise ValueError('fused=True needs a device batch and a policy stove_ppo_collect serves: Policy(base="control") on 1 .. 6 '
+                             'objects with a head of width 1 .. 128 and nine actions')
+        batch = self.start_batch(batch_size)
+        if self.env_device.type != 'cuda':
+            if self.actor_critic.kernel_shape() is None:
+                raise ValueError('the host collection restates Policy(base="control"); this policy is another one')
+            out = _collect.PolicyForest.from_policy(self.actor_critic).collect(batch, u, self.discount)
+            return {k: torch.from_numpy(a).to(self.device) for k, a in out.items()}, batch
+        batch.to(self.device)
+        ut = torch.from_numpy(u).to(self.device)
+        if fused or (fused is None and self.fused_serves()):
+            from .. import ops
+            _, H, deep = self.actor_critic.kernel_shape()
+            out = ops.ppo_collect(batch.x, batch.v, batch.r, batch.m, self.actor_critic.flat_params(), ut, H, deep, batch.granularity, batch.hw,
+                                  batch.t, batch.friction, batch.action_force, batch.drift, self.discount)
+            return out, batch
+        return self._collect_composed(batch, ut), batch
+
+    @torch.no_grad()
+    def _collect_composed(self, batch, u):
+        B, S = u.shape
+        storage = BatchStorage(B, S, (4 * batch.n,), self.device)
+        flat = lambda: batch.state().reshape(B, -1).float()
+        storage.obs[:, 0] = flat()
+        for step in range(S):
+            value, action, logp = self.actor_critic.act(storage.obs[:, step], u=u[:, step])
+            _, reward = batch.step(action, render=False)
+            storage.insert_batch(step, flat(), action.reshape(B, 1), reward.reshape(B, 1), value, 0., logp)
+        next_value = self.actor_critic.get_value(storage.obs[:, -1])
+        returns = self._calculate_returns(next_value, storage.rewards, storage.dones)
+        return {'obs': storage.obs, 'actions': storage.actions[:, :, 0].to(torch.int32), 'rewards': storage.rewards[:, :, 0],
+                'values': storage.values[:, :, 0], 'logp': storage.action_log_probs[:, :, 0], 'next_value': next_value[:, 0],
+                'returns': returns[:, :, 0], 'status': batch.status}
+
+    # ------------------------------------------------------------------------------------------------ a batch
+    def run_batch_states(self, fused=None, u=None):
+        """collect batch_size trajectories of num_steps, then one PPO update on them -> the collection (see collect)"""
+        out, batch = self.collect(self.batch_size, self.num_steps, fused, u)
+        if bool(out['status'].any()):
+            bad = torch.nonzero(out['status']).reshape(-1).tolist()
+            raise RuntimeError('the policy put out a non-finite value or logit in environments %s (status %s)'
+                               % (bad, out['status'][bad].tolist()))
+        self.last_batch = batch
+        three = lambda a: a.unsqueeze(-1)
+        values, returns = three(out['values']), three(out['returns'])
+        adv_targ = (returns - values).detach()
+        losses = self._train_ppo(out['obs'][:, :-1], three(out['actions']).long(), returns, values, three(out['logp']), adv_targ)
+        self._log_to_tb({'/losses/value_loss': losses[0], '/losses/action_loss': losses[1], '/losses/entropy': losses[2],
+                         '/info/rewards': float(out['rewards'].mean())})
+        self.batch_counter += 1
+        return out
+
+    def _test_actorcritic(self, batch_size, num_steps, fused=None, u=None):
+        """the mean reward of a fresh collection, without an update"""
+        out, _ = self.collect(batch_size, num_steps, fused, u)
+        return float(out['rewards'].mean())
+
+    def _train_ppo(self, obs, actions, returns, values, action_log_probs, adv_targ):
+        flat = lambda a: a.reshape((-1, *a.size()[2:]))
+        return self.agent.update(flat(obs), flat(actions), flat(returns), flat(values), flat(action_log_probs), flat(adv_targ))

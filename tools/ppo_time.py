@@ -1,0 +1,108 @@
+"""Time one PPO batch on states, piece by piece, on this tree (writes profiles/ppo_collect.json):
+
+    python tools/ppo_time.py [--reps 5] [--out profiles/ppo_collect.json]
+
+Per batch of 32 x 128 and 256 x 128 steps (N = 3, H = 64, main_rl's environment settings), wall-clock with a device synchronisation
+at either end, the median of --reps runs after one warm-up:
+  start_ms      drawing the batch's start states on the host (reset + one step each; common to every variant below)
+  fused_ms      the one-launch collection (ops.ppo_collect), the image built from the policy included
+  composed_ms   the composed device collection: per step one batched policy.act and one stove_env_step
+  host_loop_ms  the reference's shape: environment after environment, per step a one-row policy.act on the device, a .cpu() and a
+                numpy AvoidanceTask.step (--reps 1 for this one: it is slow by construction)
+  update_ms     PPOAgent.update on the collected batch (4 epochs x 32 mini-batches, torch autograd + Adam)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from stove_amd import build  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_collect.json'))
+    args = ap.parse_args()
+    build.build_library()
+    import numpy as np
+    import torch
+    from stove_amd import ops
+    from stove_amd.envs import envs
+    from stove_amd.rl.agents import PPOAgent
+    from stove_amd.rl.rl_model import Policy
+    from stove_amd.rl.runners import PPORunner
+
+    dev = 'cuda:0'
+    sync = torch.cuda.synchronize
+
+    def timed(fn, reps):
+        fn()
+        times = []
+        for _ in range(reps):
+            sync()
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            times.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(times)
+
+    result = {'device': torch.cuda.get_device_name(0), 'reps': args.reps, 'policy': {'N': 3, 'H': 64, 'deep': False}, 'batches': {}}
+    for B, S in ((32, 128), (256, 128)):
+        torch.manual_seed(0)
+        np.random.seed(0)
+        env = envs.BillardsEnv(n=3, granularity=2, seed=0)
+        task = envs.AvoidanceTask(env, action_force=.3)
+        policy = Policy(12, 9, hidden_size=64, base='control')
+        agent = PPOAgent(policy, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40)
+        runner = PPORunner(env, task, None, dev, agent, policy, num_steps=S, batch_size=B, discount=.95)
+        u = np.random.random_sample((B, S)).astype(np.float32)
+        ut = torch.from_numpy(u).to(dev)
+        row = {'start_ms': timed(lambda: runner.start_batch(B), args.reps)}
+        start = runner.start_batch(B).to(dev)
+        x0, v0 = start.x.clone(), start.v.clone()
+
+        def rewind():
+            start.x.copy_(x0)
+            start.v.copy_(v0)
+
+        def fused():
+            rewind()
+            return ops.ppo_collect(start.x, start.v, start.r, start.m, policy.flat_params(), ut, 64, False, start.granularity, start.hw, start.t,
+                                   start.friction, start.action_force, start.drift, .95)
+
+        def composed():
+            rewind()
+            return runner._collect_composed(start, ut)
+
+        def host_loop():
+            with torch.no_grad():
+                for b in range(B):
+                    _, state = runner.reset()
+                    obs = torch.from_numpy(state.reshape(1, -1)).float().to(dev)
+                    for s in range(S):
+                        value, action, logp = policy.act(obs)
+                        _, state, r, _ = task.step(int(action[0].cpu()))
+                        obs = torch.from_numpy(state.reshape(1, -1)).float().to(dev)
+
+        row['fused_ms'] = timed(fused, args.reps)
+        row['composed_ms'] = timed(composed, args.reps)
+        row['host_loop_ms'] = timed(host_loop, 1)
+        out = fused()
+        three = lambda a: a.unsqueeze(-1)
+        flat = lambda a: a.reshape((-1, *a.size()[2:]))
+        batch = [flat(out['obs'][:, :-1]), flat(three(out['actions']).long()), flat(three(out['returns'])), flat(three(out['values'])),
+                 flat(three(out['logp'])), flat(three(out['returns'] - out['values']))]
+        row['update_ms'] = timed(lambda: agent.update(*batch), max(1, args.reps // 2))
+        result['batches']['%dx%d' % (B, S)] = row
+        print('%dx%d' % (B, S), json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as fh:
+        json.dump(result, fh, indent=1, sort_keys=True)
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,22 @@
+"""Train the model-free PPO arm on states (stove_amd/rl/main_rl.py):
+
+    python tools/run_ppo.py --use-states --experiment_id run0 [--device-envs] [--num-env-steps 409600]
+
+The reference's `python -m model.rl.main_rl --use-states` with the same flags; `--device-envs` keeps the environments on the GPU, where a
+batch of trajectories is collected in one launch."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from stove_amd import build  # noqa: E402
+
+
+def main(argv=None):
+    build.build_library()          # (hipcc is spawned before the process touches the GPU)
+    from stove_amd.rl.main_rl import main as main_rl
+    return main_rl(sys.argv[1:] if argv is None else argv)
+
+
+if __name__ == '__main__':
+    main()
