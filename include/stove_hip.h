@@ -453,6 +453,29 @@ int stove_ppo_collect(double* x, double* v, const double* r, const double* m, co
                       int S, int N, int H, int deep, int granularity, int drift, double hw, double t, double friction,
                       double action_force, double discount, void* stream);
 
+/* ---- The PPO arm's update: every epoch and mini-batch of PPOAgent.update (stove_amd/rl/agents.py, the specification), E x M
+ * dependent optimiser steps, in ONE launch of one workgroup (csrc/ppo_update.hip, csrc/ppo_update.h).  params: the image above, in/out;
+ * m, v: Adam's moments in the image's layout, in/out; step (1,) in/out: the optimiser's step count.  obs (n, 4N) float; actions (n,)
+ * int32 in 0 .. 8; returns, values, logp, adv (n,) float; perm (E, n) int32: epoch e's permutation of 0 .. n - 1.  Step e M + i works on
+ * the mb = n / M rows perm[e][i mb .. (i + 1) mb - 1] (the trailing n - M mb indices of an epoch are never read): the forward of each
+ * row, log-softmax and entropy in float64, ratio = exp(new_logp - logp), the surrogate -min(ratio adv, clamp(ratio, 1 - clip, 1 + clip)
+ * adv), the value loss 0.5 max((v - R)^2, (v_old + clamp(v - v_old, -clip, clip) - R)^2) (0.5 (v - R)^2 with clipped_value_loss == 0),
+ * their means over the rows, the loss value_loss * value_coef + action_loss - entropy * entropy_coef and its gradient as torch's
+ * autograd gives it (equal arguments of min / max share the gradient, a clamp passes it on its closed range); every weight and bias
+ * gradient is one float32 sum over the rows in order; the norm in float64, the factor min(1, max_grad_norm / (norm + 1e-6)), then
+ * torch.optim.Adam with betas (0.9, 0.999), no weight decay and eps outside the root.  losses (E M, 3): value loss, action loss,
+ * entropy of each step; gnorm (E M,): its gradient norm before clipping.  max_steps stops after that many steps (E M runs them all).
+ * status (2,): [0] 0 completed; 2 an index of perm outside 0 .. n - 1 or an action outside 0 .. 8 among a step's rows (device memory:
+ * the kernel checks it, as everywhere in this interface); 3 a loss or the gradient norm of a step was not finite.  With 2 or 3 that step
+ * and everything after it change nothing: params, m, v and step stand as the step before left them and the later rows of losses and
+ * gnorm are not written.  [1] the number of steps completed.  Deterministic: the same inputs give the same bits.  One launch on `stream`,
+ * no synchronisation (the call can be captured), no atomics.  A NULL array, n < M, M < 1, E < 0, max_steps outside 0 .. E M, N outside
+ * 1 .. 6, H outside 1 .. 128: hipErrorInvalidValue, nothing launched.  E == 0 and max_steps == 0 are valid empty calls. */
+int stove_ppo_update(float* params, float* m, float* v, int* step, const float* obs, const int* actions, const float* returns,
+                     const float* values, const float* logp, const float* adv, const int* perm, float* losses, float* gnorm, int* status,
+                     int n, int E, int M, int max_steps, int N, int H, int deep, float clip, float value_coef, float entropy_coef, float lr,
+                     float eps, float max_grad_norm, int clipped_value_loss, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

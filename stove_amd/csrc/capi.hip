@@ -41,6 +41,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "env.hip"
 #include "env_search.hip"
 #include "ppo_collect.hip"
+#include "ppo_update.hip"
 
 namespace stove {
 
@@ -175,7 +176,8 @@ extern "C" {
 //     stove_env_step -- a batch of avoidance / billiards environments stepped and rendered in place (env.hip);
 //     stove_env_search -- tree search on those environments themselves, one launch per planning step (env_search.hip);
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in;
-//     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip))
+//     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
+//     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip))
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1619,6 +1621,31 @@ int stove_ppo_collect(double* x, double* v, const double* r, const double* m, co
                             next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
   return STOVE_LAUNCH_LDS(ppo_collect_k<false>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards, values, logp,
                           next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
+}
+
+// ---------------------------------------------------------------- the PPO arm: the whole update in one launch (ppo_update.hip)
+int stove_ppo_update(float* params, float* m, float* v, int* step, const float* obs, const int* actions, const float* returns,
+                     const float* values, const float* logp, const float* adv, const int* perm, float* losses, float* gnorm, int* status, int n,
+                     int E, int M, int max_steps, int N, int H, int deep, float clip, float value_coef, float entropy_coef, float lr, float eps,
+                     float max_grad_norm, int clipped_value_loss, void* stream) {
+  STOVE_VALIDATE(ppo_update(params, m, v, step, obs, actions, returns, values, logp, adv, perm, losses, gnorm, status, n, E, M, max_steps, N, H));
+  const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
+  const ppo_update::Hyper hy{clip, value_coef, entropy_coef, lr, eps, max_grad_norm, clipped_value_loss != 0 ? 1 : 0};
+  const size_t lds = upd_lds_bytes(sh);
+  const dim3 grid(1), block(kUpdThreads);
+  hipStream_t st = (hipStream_t)stream;
+  if (upd_staged(sh)) {
+    if (sh.deep)
+      return STOVE_LAUNCH_LDS(ppo_update_k<true, true>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
+                              losses, gnorm, status, sh, hy, n, M, max_steps);
+    return STOVE_LAUNCH_LDS(ppo_update_k<true, false>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
+                            losses, gnorm, status, sh, hy, n, M, max_steps);
+  }
+  if (sh.deep)
+    return STOVE_LAUNCH_LDS(ppo_update_k<false, true>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
+                            losses, gnorm, status, sh, hy, n, M, max_steps);
+  return STOVE_LAUNCH_LDS(ppo_update_k<false, false>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
+                          losses, gnorm, status, sh, hy, n, M, max_steps);
 }
 
 // ---------------------------------------------------------------- stream ordering / graph replay helpers

@@ -283,6 +283,18 @@ inline int ppo_collect(const double* x, const double* v, const double* r, const 
   return 0;
 }
 
+// ---- stove_ppo_update: up to max_steps of E x M optimiser steps on n collected rows (csrc/ppo_update.hip).  E == 0 and max_steps == 0
+// are valid empty calls (one launch that writes status only).  Everything the pointers name is device memory: the indices of perm and
+// the actions are checked by the kernel (status 2), a non-finite loss or norm is found there too (status 3).
+inline int ppo_update(const float* params, const float* m, const float* v, const int* step, const float* obs, const int* actions,
+                      const float* returns, const float* values, const float* logp, const float* adv, const int* perm, const float* losses,
+                      const float* gnorm, const int* status, int n, int E, int M, int max_steps, int N, int H) {
+  if (N < 1 || N > kEnvMaxObjects || H < 1 || H > kPpoMaxHidden || M < 1 || n < M || E < 0 || max_steps < 0) return kStoveInvalidValue;
+  if ((long long)max_steps > (long long)E * M || (long long)E * n > 0x7fffffffLL || (long long)n * 4 * N > 0x7fffffffLL) return kStoveInvalidValue;
+  if (null_any(params, m, v, obs, returns, values, logp, adv, losses, gnorm) || null_any(step, actions, perm, status)) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

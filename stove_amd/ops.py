@@ -1139,6 +1139,66 @@ def ppo_collect(x, v, r, m, params, u, hidden, deep, granularity, hw, t=1.0, fri
     return out
 
 
+def ppo_update(params, m, v, step, obs, actions, returns, values, logp, adv, perm, num_mini_batch, hidden, deep, clip, value_coef, entropy_coef,
+               lr, eps, max_grad_norm, clipped_value_loss=True, max_steps=None, out=None):
+    """The PPO arm's update (stove_ppo_update, csrc/ppo_update.hip): the E = perm.shape[0] epochs of num_mini_batch optimiser steps of
+    PPOAgent.update on n collected rows in one launch, nothing synchronised.  params (the float32 image, Policy.flat_params()), m, v
+    (Adam's moments, same layout) and step (1,) int32 are updated in place; obs (n, 4N), returns, values, logp, adv (n,) float32;
+    actions (n,) int32; perm (E, n) int32, epoch e's permutation.  max_steps: stop after that many steps (None: all E * num_mini_batch).
+    out: a dict of the tensors to write into (losses (E * M, 3), gnorm (E * M,) float32, status (2,) int32); None allocates them
+    (zeros).  -> that dict; status[0] 3: a loss or the norm of step status[1] was not finite (2: an index of perm or an action out of
+    range), that step and all after it changed nothing."""
+    lib = _lib.load()
+    for name, ten in (('params', params), ('m', m), ('v', v), ('obs', obs), ('returns', returns), ('values', values), ('logp', logp), ('adv', adv)):
+        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
+            raise RuntimeError('ops.ppo_update: %s must be a tensor on the GPU (the host path is rl.agents.PPOAgent without fused)' % name)
+        if ten.dtype != torch.float32 or not ten.is_contiguous() or ten.device != params.device:
+            raise RuntimeError('ops.ppo_update: %s must be a contiguous float32 tensor on %s' % (name, params.device))
+    dev = params.device
+    for name, ten in (('step', step), ('actions', actions), ('perm', perm)):
+        if not isinstance(ten, torch.Tensor) or ten.dtype != torch.int32 or ten.device != dev or not ten.is_contiguous():
+            raise RuntimeError('ops.ppo_update: %s must be a contiguous int32 tensor on %s' % (name, dev))
+    if obs.dim() != 2 or obs.shape[1] % 4:
+        raise ValueError('ops.ppo_update: obs must be (n, 4N)')
+    n, N = obs.shape[0], obs.shape[1] // 4
+    H, deep, M = int(hidden), int(bool(deep)), int(num_mini_batch)
+    if not 1 <= N <= 6 or not 1 <= H <= 128:
+        raise ValueError('ops.ppo_update: the kernel serves 1 .. 6 objects and head widths 1 .. 128, not N = %d, hidden = %d' % (N, H))
+    if M < 1 or n < M:
+        raise ValueError('ops.ppo_update: %d rows do not make %d mini-batches' % (n, M))
+    count = ppo_param_floats(N, H, deep)
+    for name, ten in (('params', params), ('m', m), ('v', v)):
+        if tuple(ten.shape) != (count,):
+            raise ValueError('ops.ppo_update: %s is %s, the policy needs (%d,)' % (name, tuple(ten.shape), count))
+    for name, ten in (('actions', actions), ('returns', returns), ('values', values), ('logp', logp), ('adv', adv)):
+        if tuple(ten.shape) != (n,):
+            raise ValueError('ops.ppo_update: %s is %s, the batch needs (%d,)' % (name, tuple(ten.shape), n))
+    if tuple(step.shape) != (1,) or perm.dim() != 2 or perm.shape[1] != n:
+        raise ValueError('ops.ppo_update: step must be (1,) and perm (E, %d)' % n)
+    E = perm.shape[0]
+    max_steps = E * M if max_steps is None else int(max_steps)
+    if not 0 <= max_steps <= E * M:
+        raise ValueError('ops.ppo_update: max_steps = %d is outside 0 .. %d' % (max_steps, E * M))
+    shapes = {'losses': ((E * M, 3), torch.float32), 'gnorm': ((E * M,), torch.float32), 'status': ((2,), torch.int32)}
+    with torch.cuda.device(dev):
+        if out is None:
+            out = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        for name, (shape, dt) in shapes.items():
+            ten = out.get(name) if isinstance(out, dict) else None
+            if not isinstance(ten, torch.Tensor) or ten.dtype != dt or ten.device != dev or not ten.is_contiguous():
+                raise RuntimeError('ops.ppo_update: out %s must be a contiguous %s tensor on %s' % (name, str(dt).split('.')[-1], dev))
+            if tuple(ten.shape) != shape:
+                raise ValueError('ops.ppo_update: out %s is %s, the update needs %s' % (name, tuple(ten.shape), shape))
+        if E * M == 0:          # (arrays without elements have no address; the launch needs them)
+            out['status'].zero_()
+            return out
+        check(lib.stove_ppo_update(ptr(params), ptr(m), ptr(v), ptr(step), ptr(obs), ptr(actions), ptr(returns), ptr(values), ptr(logp), ptr(adv),
+                                   ptr(perm), ptr(out['losses']), ptr(out['gnorm']), ptr(out['status']), n, E, M, max_steps, N, H, deep,
+                                   float(clip), float(value_coef), float(entropy_coef), float(lr), float(eps), float(max_grad_norm),
+                                   int(bool(clipped_value_loss)), stream()), 'stove_ppo_update')
+    return out
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 

@@ -49,6 +49,8 @@ def parse_args(args):
     parser.add_argument('--use-pretrained-model', action='store_true', default=False, help='use the pretrained model as world model')
     parser.add_argument('--device-envs', action='store_true', default=False,
                         help='keep the environments on the GPU: a batch of trajectories is one launch')
+    parser.add_argument('--fused-update', action='store_true', default=False,
+                        help='run the PPO update on the GPU in one launch (needs the policy and the batch there)')
     parser.add_argument('--device', default=None, help='device of the policy (default: cuda when there is one)')
     args = parser.parse_args(args)
     assert args.task in ['avoidance', 'maxdist', 'mindist']
@@ -75,8 +77,10 @@ def build(args, writer=None):
     shape = env.get_state_shape()
     actor_critic = Policy(shape[0] * shape[1], task.get_action_space(), hidden_size=64, base='control')
     agent = PPOAgent(actor_critic, args.clip_param, args.num_ppo_epochs, args.num_ppo_mb, args.value_loss_coef, args.entropy_coef, args.lr,
-                     args.eps, args.max_grad_norm)
+                     args.eps, args.max_grad_norm, fused=True if args.fused_update else None)
     device = args.device or ('cuda' if torch.cuda.is_available() else 'cpu')
+    if args.fused_update and torch.device(device).type != 'cuda':
+        raise ValueError('--fused-update needs a GPU')
     if args.device_envs and torch.device(device).type != 'cuda':
         raise ValueError('--device-envs needs a GPU')
     runner = PPORunner(env=env, task=task, summary_path=os.path.join(args.summary_dir, args.experiment_id), device=device, agent=agent,

@@ -156,3 +156,32 @@ class Policy(nn.Module):
         layers.append((torch.cat([h.values_head.weight, h.actor_head.weight], 0), torch.cat([h.values_head.bias, h.actor_head.bias], 0)))
         with torch.no_grad():
             return torch.cat([p for w, bias in layers for p in (w.t().reshape(-1), bias.reshape(-1))]).float().contiguous()
+
+    def load_flat_params(self, image):
+        """the inverse of flat_params(): the layers' weights and biases written from the image, in place"""
+        if self.kernel_shape() is None:
+            raise ValueError('load_flat_params: the image is that of Policy(base="control") on 4 N inputs (N in 1 .. 6) with a head of '
+                             'width 1 .. 128 and nine actions')
+        b, h = self.base, self.head
+        layers = [b.main[0], b.main[2], h.main] + ([h.in_between[0], h.in_between[2]] if h.use_deep_layers else [])
+        H = h.main.out_features
+        if not isinstance(image, torch.Tensor) or image.dim() != 1 or \
+                image.numel() != sum(l.weight.numel() + l.bias.numel() for l in layers) + (H + 1) * 10:
+            raise ValueError('load_flat_params: the image does not have the length of flat_params()')
+        at = 0
+
+        def take(count):
+            nonlocal at
+            at += count
+            return image[at - count:at]
+        with torch.no_grad():
+            for layer in layers:
+                out, k = layer.weight.shape
+                layer.weight.copy_(take(out * k).reshape(k, out).t())
+                layer.bias.copy_(take(out))
+            heads = take(H * 10).reshape(H, 10).t()
+            h.values_head.weight.copy_(heads[:1])
+            h.actor_head.weight.copy_(heads[1:])
+            bias = take(10)
+            h.values_head.bias.copy_(bias[:1])
+            h.actor_head.bias.copy_(bias[1:])

@@ -9,7 +9,15 @@ at either end, the median of --reps runs after one warm-up:
   composed_ms   the composed device collection: per step one batched policy.act and one stove_env_step
   host_loop_ms  the reference's shape: environment after environment, per step a one-row policy.act on the device, a .cpu() and a
                 numpy AvoidanceTask.step (--reps 1 for this one: it is slow by construction)
-  update_ms     PPOAgent.update on the collected batch (4 epochs x 32 mini-batches, torch autograd + Adam)"""
+  update_ms     PPOAgent.update on the collected batch (4 epochs x 32 mini-batches, torch autograd + Adam)
+
+    python tools/ppo_time.py --update [--reps 5] [--update-out profiles/ppo_update.json]
+
+times the update alone, both ways in this one process on the same collected batch (writes profiles/ppo_update.json):
+  torch_update_ms   PPOAgent.update as above (the code path of fused=None, unchanged by the fused one)
+  fused_update_ms   PPOAgent(fused=True).update: the permutations, their upload, the image, one stove_ppo_update launch, the image
+                    written back into the policy, and the one read of the losses and the status
+  fused_launch_ms   ops.ppo_update alone on prepared tensors"""
 import argparse
 import json
 import os
@@ -26,6 +34,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_collect.json'))
+    ap.add_argument('--update', action='store_true', help='time the update alone: torch against the one-launch update')
+    ap.add_argument('--update-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_update.json'))
     args = ap.parse_args()
     build.build_library()
     import numpy as np
@@ -88,19 +98,37 @@ def main():
                         _, state, r, _ = task.step(int(action[0].cpu()))
                         obs = torch.from_numpy(state.reshape(1, -1)).float().to(dev)
 
-        row['fused_ms'] = timed(fused, args.reps)
-        row['composed_ms'] = timed(composed, args.reps)
-        row['host_loop_ms'] = timed(host_loop, 1)
+        if not args.update:
+            row['fused_ms'] = timed(fused, args.reps)
+            row['composed_ms'] = timed(composed, args.reps)
+            row['host_loop_ms'] = timed(host_loop, 1)
         out = fused()
         three = lambda a: a.unsqueeze(-1)
         flat = lambda a: a.reshape((-1, *a.size()[2:]))
         batch = [flat(out['obs'][:, :-1]), flat(three(out['actions']).long()), flat(three(out['returns'])), flat(three(out['values'])),
                  flat(three(out['logp'])), flat(three(out['returns'] - out['values']))]
-        row['update_ms'] = timed(lambda: agent.update(*batch), max(1, args.reps // 2))
+        if args.update:
+            row = {'torch_update_ms': timed(lambda: agent.update(*batch), args.reps)}
+            twin = Policy(12, 9, hidden_size=64, base='control').to(dev)
+            twin.load_state_dict(policy.state_dict())
+            fused_agent = PPOAgent(twin, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40, fused=True)
+            row['fused_update_ms'] = timed(lambda: fused_agent.update(*batch), args.reps)
+            n = batch[0].shape[0]
+            image = twin.flat_params()
+            m, v, step = torch.zeros_like(image), torch.zeros_like(image), torch.zeros(1, dtype=torch.int32, device=dev)
+            perm = torch.stack([torch.randperm(n) for _ in range(4)]).to(device=dev, dtype=torch.int32)
+            rows = [batch[0].contiguous(), batch[1].reshape(n).to(torch.int32)] + [t.reshape(n).contiguous() for t in batch[2:]]
+            outs = ops.ppo_update(image, m, v, step, *rows, perm, 32, 64, False, .1, .5, .01, 2e-4, 1e-5, 40.)
+            row['fused_launch_ms'] = timed(lambda: ops.ppo_update(image, m, v, step, *rows, perm, 32, 64, False, .1, .5, .01, 2e-4, 1e-5, 40., out=outs),
+                                           args.reps)
+            row['fused_status'] = outs['status'].tolist()
+        else:
+            row['update_ms'] = timed(lambda: agent.update(*batch), max(1, args.reps // 2))
         result['batches']['%dx%d' % (B, S)] = row
         print('%dx%d' % (B, S), json.dumps(row), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as fh:
+    path = args.update_out if args.update else args.out
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, 'w') as fh:
         json.dump(result, fh, indent=1, sort_keys=True)
 
 

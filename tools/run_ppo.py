@@ -1,9 +1,9 @@
 """Train the model-free PPO arm on states (stove_amd/rl/main_rl.py):
 
-    python tools/run_ppo.py --use-states --experiment_id run0 [--device-envs] [--num-env-steps 409600]
+    python tools/run_ppo.py --use-states --experiment_id run0 [--device-envs] [--fused-update] [--num-env-steps 409600]
 
 The reference's `python -m model.rl.main_rl --use-states` with the same flags; `--device-envs` keeps the environments on the GPU, where a
-batch of trajectories is collected in one launch."""
+batch of trajectories is collected in one launch; `--fused-update` runs the PPO update there in one launch too (off by default)."""
 import os
 import sys
 
