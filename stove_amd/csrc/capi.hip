@@ -129,6 +129,13 @@ template <class F>
 static int with_flag(bool b, F f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
 }
+// f(Int<n>) for a count n of 1 .. MAX that is a template parameter itself (env_search_k's objects)
+template <int MAX, class F>
+static int with_count(int n, F f) {
+  if (n == MAX) return f(Int<MAX>{});
+  if constexpr (MAX > 1) return with_count<MAX - 1>(n, f);
+  return (int)hipErrorInvalidValue;
+}
 // f(NMX, ELU, NT) for a small graph of N objects: NMX = 4 / 6, the kernels built for up to four objects and up to six, NT = N where the count is a compile-time constant of the kernel
 // (three objects; six where the kernel has that instantiation, SIX, and the call can use it, `six`), else 0.
 template <bool SIX, class F>
@@ -1584,14 +1591,11 @@ int stove_env_search(const double* x, const double* v, const double* r, const do
   const int T = M * R;
   const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
   if (runs > 0) {
-    switch (N) {
-      case 1: env_search_launch<1>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
-      case 2: env_search_launch<2>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
-      case 3: env_search_launch<3>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
-      case 4: env_search_launch<4>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
-      case 5: env_search_launch<5>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
-      default: env_search_launch<6>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D); break;
-    }
+    const int rc = with_count<6>(N,[&](auto n) {
+      env_search_launch<decltype(n)::value>(st, T, x, v, r, m, draws, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, p, R, runs, cap, D);
+      return 0;
+    });
+    if (rc) return rc;
     STOVE_LAUNCH_CHECK();
   }
   STOVE_LAUNCH(env_search_action_k, dim3((M + kEnvSearchThreads - 1) / kEnvSearchThreads), dim3(kEnvSearchThreads), 0, st, (const int*)first,
@@ -1616,11 +1620,10 @@ int stove_ppo_collect(double* x, double* v, const double* r, const double* m, co
   const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
   const size_t n = ppo_policy::param_floats(sh), lds = ppo_lds_bytes(n);
   const dim3 grid((B + kPpoWaves - 1) / kPpoWaves), block(kPpoThreads);
-  if (ppo_staged(n))
-    return STOVE_LAUNCH_LDS(ppo_collect_k<true>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards, values, logp,
-                            next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
-  return STOVE_LAUNCH_LDS(ppo_collect_k<false>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards, values, logp,
-                          next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
+  return with_flag(ppo_staged(n), [&](auto staged) {
+    return STOVE_LAUNCH_LDS(ppo_collect_k<decltype(staged)::value>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards,
+                            values, logp, next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
+  });
 }
 
 // ---------------------------------------------------------------- the PPO arm: the whole update in one launch (ppo_update.hip)
@@ -1634,18 +1637,12 @@ int stove_ppo_update(float* params, float* m, float* v, int* step, const float* 
   const size_t lds = upd_lds_bytes(sh);
   const dim3 grid(1), block(kUpdThreads);
   hipStream_t st = (hipStream_t)stream;
-  if (upd_staged(sh)) {
-    if (sh.deep)
-      return STOVE_LAUNCH_LDS(ppo_update_k<true, true>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
-                              losses, gnorm, status, sh, hy, n, M, max_steps);
-    return STOVE_LAUNCH_LDS(ppo_update_k<true, false>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
-                            losses, gnorm, status, sh, hy, n, M, max_steps);
-  }
-  if (sh.deep)
-    return STOVE_LAUNCH_LDS(ppo_update_k<false, true>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
-                            losses, gnorm, status, sh, hy, n, M, max_steps);
-  return STOVE_LAUNCH_LDS(ppo_update_k<false, false>, grid, block, lds, st, params, m, v, step, obs, actions, returns, values, logp, adv, perm,
-                          losses, gnorm, status, sh, hy, n, M, max_steps);
+  return with_flag(upd_staged(sh), [&](auto staged) {
+    return with_flag(sh.deep != 0, [&](auto dp) {
+      return STOVE_LAUNCH_LDS(ppo_update_k<decltype(staged)::value, decltype(dp)::value>, grid, block, lds, st, params, m, v, step, obs, actions,
+                              returns, values, logp, adv, perm, losses, gnorm, status, sh, hy, n, M, max_steps);
+    });
+  });
 }
 
 // ---------------------------------------------------------------- stream ordering / graph replay helpers

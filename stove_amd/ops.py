@@ -40,6 +40,79 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 4) // 4 + 1, dtype=torch.float32, device=device)
 
 
+# The argument checks of the forward-only control ops (plan_expand ... ppo_update, below).
+_F32, _F64, _I32 = torch.float32, torch.float64, torch.int32
+
+
+def _arg(op, name, t, dtype, dev, shape=None, owner='batch'):
+    """`t` is a contiguous `dtype` tensor on `dev` and, with `shape`, of that shape -- what `owner` (forest, batch, ...) needs"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise RuntimeError('ops.%s: %s must be a contiguous %s tensor on %s' % (op, name, str(dtype).split('.')[-1], dev))
+    if shape is not None and tuple(t.shape) != shape:
+        raise ValueError('ops.%s: %s is %s, the %s needs %s' % (op, name, tuple(t.shape), owner, shape))
+
+
+def _on_gpu(op, name, t, host_path):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError('ops.%s: %s must be a tensor on the GPU (the host path is %s)' % (op, name, host_path))
+
+
+def _env_state(op, x, v, r, m, host_path, count='M'):
+    """x, v (M, N, 2), r, m (M, N): the float64 state of M environments (`count`: the letter the op calls M by) -> (M, N, device)"""
+    for name, t in (('x', x), ('v', v), ('r', r), ('m', m)):
+        _on_gpu(op, name, t, host_path)
+        _arg(op, name, t, _F64, x.device)
+    if x.dim() != 3 or x.shape[2] != 2:
+        raise ValueError('ops.%s: x must be (%s, N, 2)' % (op, count))
+    M, N = x.shape[:2]
+    if tuple(v.shape) != (M, N, 2) or tuple(r.shape) != (M, N) or tuple(m.shape) != (M, N):
+        raise ValueError('ops.%s: argument shapes do not fit %s = %d environments of N = %d objects' % (op, count, M, N))
+    return M, N, x.device
+
+
+_FOREST = ('first', 'parent', 'depth', 'Ns', 'Nsa', 'Qsa', 'used', 'status', 'min_gap')
+
+
+def _forest(op, arrays, T, dev, cap=None):
+    """The arrays of T trees (Forest.to_device, EnvForest.to_device): first ... Qsa (T, cap), used, status, min_gap (T,); Qsa and
+    min_gap float64, the rest int32.  cap None: whatever `first` holds.  -> (the pointers in the C calls' order, cap)"""
+    a = arrays if isinstance(arrays, dict) else {}
+    if cap is None:
+        _arg(op, 'first', a.get('first'), _I32, dev)
+        cap = a['first'].shape[1] if a['first'].dim() == 2 else -1
+    for k in _FOREST:
+        _arg(op, k, a.get(k), _F64 if k in ('Qsa', 'min_gap') else _I32, dev, (T, cap) if k in _FOREST[:6] else (T,), 'forest')
+    return [ptr(a[k]) for k in _FOREST[:7] + ('min_gap', 'status')], cap
+
+
+def _outputs(op, out, table, dev, owner, alloc=torch.zeros):
+    """The dict of an op's outputs by `table` = {name: (shape, dtype)}: allocated with out = None, else the caller's, checked"""
+    if out is None:
+        return {k: alloc(shape, dtype=dt, device=dev) for k, (shape, dt) in table.items()}
+    for k, (shape, dt) in table.items():
+        _arg(op, 'out ' + k, out.get(k) if isinstance(out, dict) else None, dt, dev, shape, owner)
+    return out
+
+
+def _plan_model(op, z_pool, app, emb_w, emb_b, gnn_params, rh_params):
+    """What the two planning ops ask of the model's side: nothing to differentiate, float32, z_pool written where it lies"""
+    tensors = (z_pool, app, emb_w, emb_b, gnn_params, rh_params)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError('ops.%s is forward only: call it under torch.no_grad() or with detached inputs' % op)
+    tensors = [_f32(t) for t in tensors]
+    if tensors[0].data_ptr() != z_pool.data_ptr():
+        raise RuntimeError('ops.%s writes the child states into z_pool: it must be contiguous' % op)
+    return tensors
+
+
+def _plan_fits(lib, z_pool, app, emb_w, emb_b, gnn_params, rh_params):
+    """whether the model's tensors fit z_pool's M trees of N objects and the library's parameter counts"""
+    M, _, N = z_pool.shape[:3]
+    return (z_pool.shape[3] == 18 and tuple(emb_w.shape) == (4 * N, emb_w.shape[1]) and emb_b.numel() == 4 * N
+            and (app is None or tuple(app.shape) == (M, N, app.shape[-1]))
+            and gnn_params.numel() == lib.stove_gnn_param_floats() and rh_params.numel() == lib.stove_reward_head_param_floats())
+
+
 class _ObjSpnFn(torch.autograd.Function):
     """RatSpn.forward of the object SPN (reference rat_torch.py:354-357)."""
 
@@ -919,11 +992,8 @@ def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params,
     (M, N, app_dim) or None; emb_w (4 N, A), emb_b (4 N) the action embedding; gnn_params the cl = 32 image (gnn_width(32).image(...));
     rh_params the reward head's 2785 floats; `depth` the search's maximal rollout depth D.
     -> q (M, A) [, r_first (M, A), r_roll (M, A, L) with want_rewards]: the reference's backpropagate value of every child."""
-    tensors = (z_pool, app, emb_w, emb_b, gnn_params, rh_params)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
-        raise RuntimeError('ops.plan_expand is forward only: call it under torch.no_grad() or with detached inputs')
     lib = _lib.load()
-    z_pool, app, emb_w, emb_b, gnn_params, rh_params = [_f32(t) for t in tensors]
+    z_pool, app, emb_w, emb_b, gnn_params, rh_params = model = _plan_model('plan_expand', z_pool, app, emb_w, emb_b, gnn_params, rh_params)
     for name, t in (('leaf', leaf), ('child', child), ('len_s', len_s), ('acts', acts)):
         if t.dtype != torch.int32 or not t.is_cuda:
             raise RuntimeError('ops.plan_expand: %s must be an int32 tensor on the GPU' % name)
@@ -931,11 +1001,7 @@ def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params,
     A = emb_w.shape[1]
     L = acts.shape[-1]
     app_dim = app.shape[-1] if app is not None else 0
-    if z_pool.data_ptr() != tensors[0].data_ptr():
-        raise RuntimeError('ops.plan_expand writes the child states into z_pool: it must be contiguous')
-    if (z_pool.shape[3] != 18 or tuple(emb_w.shape) != (4 * N, A) or emb_b.numel() != 4 * N or acts.numel() != M * A * L
-            or leaf.numel() != M or child.numel() != M or len_s.numel() != M or (app is not None and tuple(app.shape) != (M, N, app_dim))
-            or gnn_params.numel() != lib.stove_gnn_param_floats() or rh_params.numel() != lib.stove_reward_head_param_floats()):
+    if not _plan_fits(lib, *model) or acts.numel() != M * A * L or leaf.numel() != M or child.numel() != M or len_s.numel() != M:
         raise ValueError('ops.plan_expand: argument shapes do not fit M = %d trees, N = %d objects, A = %d actions, L = %d' % (M, N, A, L))
     dev = z_pool.device
     with torch.cuda.device(dev):
@@ -957,40 +1023,27 @@ def plan_search(z_pool, arrays, app, acts, emb_w, emb_b, gnn_params, rh_params, 
     random-rollout actions; sel_trace (R, M) int32 or None receives the selected leaf per iteration; the rest as ops.plan_expand.
     -> action (M,) int32: the first-index argmax of the root's visit counts.  status[m] != 0 afterwards: tree m was frozen (1 out of
     slots, 2 an index check failed)."""
-    tensors = (z_pool, app, emb_w, emb_b, gnn_params, rh_params)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
-        raise RuntimeError('ops.plan_search is forward only: call it under torch.no_grad() or with detached inputs')
     lib = _lib.load()
-    z_pool, app, emb_w, emb_b, gnn_params, rh_params = [_f32(t) for t in tensors]
-    if z_pool.data_ptr() != tensors[0].data_ptr():
-        raise RuntimeError('ops.plan_search writes the child states into z_pool: it must be contiguous')
+    z_pool, app, emb_w, emb_b, gnn_params, rh_params = model = _plan_model('plan_search', z_pool, app, emb_w, emb_b, gnn_params, rh_params)
+    dev = z_pool.device
+    _arg('plan_search', 'acts', acts, _I32, dev)
     if z_pool.dim() != 4 or acts.dim() != 3:
         raise ValueError('ops.plan_search: z_pool must be (M, cap, N, 18) and acts (R, M A, L)')
     M, cap, N = z_pool.shape[:3]
     A = emb_w.shape[1]
     R, L = acts.shape[0], acts.shape[-1]
     app_dim = app.shape[-1] if app is not None else 0
-    dev = z_pool.device
-    ints = [('acts', acts, None)] + [(k, arrays[k], (M, cap)) for k in ('first', 'parent', 'depth', 'Ns', 'Nsa')] + \
-        [(k, arrays[k], (M,)) for k in ('used', 'status')] + ([('sel_trace', sel_trace, (R, M))] if sel_trace is not None else [])
-    for name, t, shape in ints + [('Qsa', arrays['Qsa'], (M, cap)), ('min_gap', arrays['min_gap'], (M,))]:
-        want = torch.float64 if name in ('Qsa', 'min_gap') else torch.int32
-        if t.dtype != want or t.device != dev or not t.is_contiguous():
-            raise RuntimeError('ops.plan_search: %s must be a contiguous %s tensor on %s' % (name, str(want).split('.')[-1], dev))
-        if shape is not None and tuple(t.shape) != shape:
-            raise ValueError('ops.plan_search: %s is %s, the forest needs %s' % (name, tuple(t.shape), shape))
-    if (z_pool.shape[3] != 18 or tuple(emb_w.shape) != (4 * N, A) or emb_b.numel() != 4 * N or tuple(acts.shape) != (R, M * A, L)
-            or (app is not None and tuple(app.shape) != (M, N, app_dim))
-            or gnn_params.numel() != lib.stove_gnn_param_floats() or rh_params.numel() != lib.stove_reward_head_param_floats()):
+    forest, _ = _forest('plan_search', arrays, M, dev, cap)
+    if sel_trace is not None:
+        _arg('plan_search', 'sel_trace', sel_trace, _I32, dev, (R, M), 'forest')
+    if not _plan_fits(lib, *model) or tuple(acts.shape) != (R, M * A, L):
         raise ValueError('ops.plan_search: argument shapes do not fit M = %d trees, N = %d objects, A = %d actions, L = %d' % (M, N, A, L))
-    a = arrays
     with torch.cuda.device(dev):
         action = torch.empty(M, dtype=torch.int32, device=dev)
         ws = _ws(lib.stove_plan_search_ws_bytes(M, A, L, N, app_dim), dev)
-        check(lib.stove_plan_search(ptr(z_pool), ptr(a['first']), ptr(a['parent']), ptr(a['depth']), ptr(a['Ns']), ptr(a['Nsa']), ptr(a['Qsa']),
-                                    ptr(a['used']), ptr(a['min_gap']), ptr(a['status']), ptr(action), ptr(sel_trace), ptr(app), ptr(acts),
-                                    ptr(emb_w), ptr(emb_b), ptr(gnn_params), ptr(rh_params), ptr(ws), M, cap, A, L, int(depth), N, app_dim,
-                                    int(lim_enc), int(elu), *[float(c) for c in consts], float(gamma), R, stream()), 'stove_plan_search')
+        check(lib.stove_plan_search(ptr(z_pool), *forest, ptr(action), ptr(sel_trace), ptr(app), ptr(acts), ptr(emb_w), ptr(emb_b),
+                                    ptr(gnn_params), ptr(rh_params), ptr(ws), M, cap, A, L, int(depth), N, app_dim, int(lim_enc), int(elu),
+                                    *[float(c) for c in consts], float(gamma), R, stream()), 'stove_plan_search')
     return action
 
 
@@ -1002,33 +1055,17 @@ def env_step(x, v, r, m, action, granularity, res, hw, t=1.0, friction=0.0, acti
     -> (frames or None with render=False, collisions, status); status 2: that environment's action index was outside [0, 9) and
     nothing of it was written."""
     lib = _lib.load()
-    for name, ten in (('x', x), ('v', v), ('r', r), ('m', m)):
-        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
-            raise RuntimeError('ops.env_step: %s must be a tensor on the GPU (the host path is BatchedAvoidance(device=None))' % name)
-        if ten.dtype != torch.float64 or not ten.is_contiguous() or ten.device != x.device:
-            raise RuntimeError('ops.env_step: %s must be a contiguous float64 tensor on %s' % (name, x.device))
-    if x.dim() != 3 or x.shape[2] != 2:
-        raise ValueError('ops.env_step: x must be (M, N, 2)')
-    M, N = x.shape[:2]
-    if tuple(v.shape) != (M, N, 2) or tuple(r.shape) != (M, N) or tuple(m.shape) != (M, N):
-        raise ValueError('ops.env_step: argument shapes do not fit M = %d environments of N = %d objects' % (M, N))
-    dev = x.device
+    M, N, dev = _env_state('env_step', x, v, r, m, 'BatchedAvoidance(device=None)')
     if action is not None:
-        if not isinstance(action, torch.Tensor) or action.dtype != torch.int32 or action.device != dev or not action.is_contiguous():
-            raise RuntimeError('ops.env_step: action must be a contiguous int32 tensor on %s' % dev)
-        if tuple(action.shape) != (M,):
-            raise ValueError('ops.env_step: action is %s, the batch needs %s' % (tuple(action.shape), (M,)))
+        _arg('env_step', 'action', action, _I32, dev, (M,))
+    table = {'frames': ((M, 3, res, res), _F32), 'collisions': ((M,), _I32), 'status': ((M,), _I32)}
+    if out is not None:
+        out = dict(zip(table, out))
+    if not (render if out is None else out['frames'] is not None):          # (no frame is written through a null pointer)
+        del table['frames']
     with torch.cuda.device(dev):
-        if out is None:
-            frames = torch.empty(M, 3, res, res, dtype=torch.float32, device=dev) if render else None
-            collisions = torch.empty(M, dtype=torch.int32, device=dev)
-            status = torch.empty(M, dtype=torch.int32, device=dev)
-        else:
-            frames, collisions, status = out
-            for name, ten, dt, shape in (('frames', frames, torch.float32, (M, 3, res, res)), ('collisions', collisions, torch.int32, (M,)),
-                                         ('status', status, torch.int32, (M,))):
-                if ten is not None and (ten.dtype != dt or ten.device != dev or not ten.is_contiguous() or tuple(ten.shape) != shape):
-                    raise RuntimeError('ops.env_step: out %s must be a contiguous %s tensor %s on %s' % (name, str(dt).split('.')[-1], shape, dev))
+        out = _outputs('env_step', out, table, dev, 'batch', torch.empty)
+        frames, collisions, status = out.get('frames'), out['collisions'], out['status']
         check(lib.stove_env_step(ptr(x), ptr(v), ptr(r), ptr(m), ptr(action), ptr(collisions), ptr(status), ptr(frames), M, N, int(granularity),
                                  int(res), int(bool(use_colors)), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
                                  stream()), 'stove_env_step')
@@ -1043,42 +1080,20 @@ def env_search(x, v, r, m, draws, arrays, depth, granularity, hw, t=1.0, frictio
     makes them) --, updated in place.  -> action (M,) int32: the first-index argmax of the root's visit counts summed over an
     environment's trees.  status[t] != 0 afterwards: tree t was frozen (1 out of slots, 2 a draw outside [0, 9) or a failed index check)."""
     lib = _lib.load()
-    for name, ten in (('x', x), ('v', v), ('r', r), ('m', m)):
-        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
-            raise RuntimeError('ops.env_search: %s must be a tensor on the GPU (the host path is mcts_env.EnvForest)' % name)
-        if ten.dtype != torch.float64 or not ten.is_contiguous() or ten.device != x.device:
-            raise RuntimeError('ops.env_search: %s must be a contiguous float64 tensor on %s' % (name, x.device))
-    if x.dim() != 3 or x.shape[2] != 2:
-        raise ValueError('ops.env_search: x must be (M, N, 2)')
-    M, N = x.shape[:2]
-    if tuple(v.shape) != (M, N, 2) or tuple(r.shape) != (M, N) or tuple(m.shape) != (M, N):
-        raise ValueError('ops.env_search: argument shapes do not fit M = %d environments of N = %d objects' % (M, N))
+    M, N, dev = _env_state('env_search', x, v, r, m, 'mcts_env.EnvForest')
     R, D = int(replicas), int(depth)
     if R < 1:
         raise ValueError('ops.env_search: replicas must be at least 1')
-    dev, T = x.device, M * R
-    if not isinstance(draws, torch.Tensor) or draws.dtype != torch.int32 or draws.device != dev or not draws.is_contiguous():
-        raise RuntimeError('ops.env_search: draws must be a contiguous int32 tensor on %s' % dev)
+    T = M * R
+    _arg('env_search', 'draws', draws, _I32, dev)
     if draws.dim() != 3 or draws.shape[0] != T or draws.shape[2] != D:
         raise ValueError('ops.env_search: draws is %s, the search needs (%d, runs, %d)' % (tuple(draws.shape), T, D))
     runs = draws.shape[1]
-    names = ('first', 'parent', 'depth', 'Ns', 'Nsa', 'Qsa', 'used', 'status', 'min_gap')
-    for name in names:
-        ten, want = arrays.get(name) if isinstance(arrays, dict) else None, torch.float64 if name in ('Qsa', 'min_gap') else torch.int32
-        if not isinstance(ten, torch.Tensor) or ten.dtype != want or ten.device != dev or not ten.is_contiguous():
-            raise RuntimeError('ops.env_search: %s must be a contiguous %s tensor on %s' % (name, str(want).split('.')[-1], dev))
-    cap = arrays['first'].shape[1] if arrays['first'].dim() == 2 else -1
-    for name in names:
-        shape = (T, cap) if name in names[:6] else (T,)
-        if tuple(arrays[name].shape) != shape:
-            raise ValueError('ops.env_search: %s is %s, the forest needs %s' % (name, tuple(arrays[name].shape), shape))
-    a = arrays
+    forest, cap = _forest('env_search', arrays, T, dev)
     with torch.cuda.device(dev):
         action = torch.zeros(M, dtype=torch.int32, device=dev)
-        check(lib.stove_env_search(ptr(x), ptr(v), ptr(r), ptr(m), ptr(draws), ptr(a['first']), ptr(a['parent']), ptr(a['depth']), ptr(a['Ns']),
-                                   ptr(a['Nsa']), ptr(a['Qsa']), ptr(a['used']), ptr(a['min_gap']), ptr(a['status']), ptr(action), M, R, N, D,
-                                   runs, cap, int(granularity), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
-                                   stream()), 'stove_env_search')
+        check(lib.stove_env_search(ptr(x), ptr(v), ptr(r), ptr(m), ptr(draws), *forest, ptr(action), M, R, N, D, runs, cap, int(granularity),
+                                   int(bool(drift)), float(hw), float(t), float(friction), float(action_force), stream()), 'stove_env_search')
     return action
 
 
@@ -1097,44 +1112,21 @@ def ppo_collect(x, v, r, m, params, u, hidden, deep, granularity, hw, t=1.0, fri
     actions (B, S), status (B,) int32); None allocates them (zeros).  -> that dict; status 3: a value or logit of that environment was
     not finite, nothing of that step or after it was written and its state stands as the steps before left it."""
     lib = _lib.load()
-    for name, ten in (('x', x), ('v', v), ('r', r), ('m', m)):
-        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
-            raise RuntimeError('ops.ppo_collect: %s must be a tensor on the GPU (the host path is rl.collect.PolicyForest)' % name)
-        if ten.dtype != torch.float64 or not ten.is_contiguous() or ten.device != x.device:
-            raise RuntimeError('ops.ppo_collect: %s must be a contiguous float64 tensor on %s' % (name, x.device))
-    if x.dim() != 3 or x.shape[2] != 2:
-        raise ValueError('ops.ppo_collect: x must be (B, N, 2)')
-    B, N = x.shape[:2]
-    if tuple(v.shape) != (B, N, 2) or tuple(r.shape) != (B, N) or tuple(m.shape) != (B, N):
-        raise ValueError('ops.ppo_collect: argument shapes do not fit B = %d environments of N = %d objects' % (B, N))
-    dev, H, deep = x.device, int(hidden), int(bool(deep))
+    B, N, dev = _env_state('ppo_collect', x, v, r, m, 'rl.collect.PolicyForest', 'B')
+    H, deep = int(hidden), int(bool(deep))
     if not 1 <= N <= 6 or not 1 <= H <= 128:
         raise ValueError('ops.ppo_collect: the kernel serves 1 .. 6 objects and head widths 1 .. 128, not N = %d, hidden = %d' % (N, H))
-    for name, ten in (('params', params), ('u', u)):
-        if not isinstance(ten, torch.Tensor) or ten.dtype != torch.float32 or ten.device != dev or not ten.is_contiguous():
-            raise RuntimeError('ops.ppo_collect: %s must be a contiguous float32 tensor on %s' % (name, dev))
-    n = ppo_param_floats(N, H, deep)
-    if tuple(params.shape) != (n,):
-        raise ValueError('ops.ppo_collect: params is %s, the policy needs (%d,)' % (tuple(params.shape), n))
+    _arg('ppo_collect', 'u', u, _F32, dev)
+    _arg('ppo_collect', 'params', params, _F32, dev, (ppo_param_floats(N, H, deep),), 'policy')
     if u.dim() != 2 or u.shape[0] != B:
         raise ValueError('ops.ppo_collect: u is %s, the batch needs (%d, S)' % (tuple(u.shape), B))
     S = u.shape[1]
-    shapes = {'obs': ((B, S + 1, 4 * N), torch.float32), 'actions': ((B, S), torch.int32), 'rewards': ((B, S), torch.float32),
-              'values': ((B, S), torch.float32), 'logp': ((B, S), torch.float32), 'next_value': ((B,), torch.float32),
-              'returns': ((B, S), torch.float32), 'status': ((B,), torch.int32)}
+    table = {'obs': ((B, S + 1, 4 * N), _F32), 'actions': ((B, S), _I32), 'rewards': ((B, S), _F32), 'values': ((B, S), _F32),
+             'logp': ((B, S), _F32), 'next_value': ((B,), _F32), 'returns': ((B, S), _F32), 'status': ((B,), _I32)}          # (in the C call's order)
     with torch.cuda.device(dev):
-        if out is None:
-            out = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        for name, (shape, dt) in shapes.items():
-            ten = out.get(name) if isinstance(out, dict) else None
-            if not isinstance(ten, torch.Tensor) or ten.dtype != dt or ten.device != dev or not ten.is_contiguous():
-                raise RuntimeError('ops.ppo_collect: out %s must be a contiguous %s tensor on %s' % (name, str(dt).split('.')[-1], dev))
-            if tuple(ten.shape) != shape:
-                raise ValueError('ops.ppo_collect: out %s is %s, the batch needs %s' % (name, tuple(ten.shape), shape))
-        o = out
-        check(lib.stove_ppo_collect(ptr(x), ptr(v), ptr(r), ptr(m), ptr(params), ptr(u), ptr(o['obs']), ptr(o['actions']), ptr(o['rewards']),
-                                    ptr(o['values']), ptr(o['logp']), ptr(o['next_value']), ptr(o['returns']), ptr(o['status']), B, S, N, H,
-                                    deep, int(granularity), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
+        out = _outputs('ppo_collect', out, table, dev, 'batch')
+        check(lib.stove_ppo_collect(ptr(x), ptr(v), ptr(r), ptr(m), ptr(params), ptr(u), *[ptr(out[k]) for k in table], B, S, N, H, deep,
+                                    int(granularity), int(bool(drift)), float(hw), float(t), float(friction), float(action_force),
                                     float(discount), stream()), 'stove_ppo_collect')
     return out
 
@@ -1149,15 +1141,12 @@ def ppo_update(params, m, v, step, obs, actions, returns, values, logp, adv, per
     (zeros).  -> that dict; status[0] 3: a loss or the norm of step status[1] was not finite (2: an index of perm or an action out of
     range), that step and all after it changed nothing."""
     lib = _lib.load()
-    for name, ten in (('params', params), ('m', m), ('v', v), ('obs', obs), ('returns', returns), ('values', values), ('logp', logp), ('adv', adv)):
-        if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
-            raise RuntimeError('ops.ppo_update: %s must be a tensor on the GPU (the host path is rl.agents.PPOAgent without fused)' % name)
-        if ten.dtype != torch.float32 or not ten.is_contiguous() or ten.device != params.device:
-            raise RuntimeError('ops.ppo_update: %s must be a contiguous float32 tensor on %s' % (name, params.device))
+    op, host = 'ppo_update', 'rl.agents.PPOAgent without fused'
+    floats = {'params': params, 'm': m, 'v': v, 'obs': obs, 'returns': returns, 'values': values, 'logp': logp, 'adv': adv}
+    for name, ten in floats.items():
+        _on_gpu(op, name, ten, host)
     dev = params.device
-    for name, ten in (('step', step), ('actions', actions), ('perm', perm)):
-        if not isinstance(ten, torch.Tensor) or ten.dtype != torch.int32 or ten.device != dev or not ten.is_contiguous():
-            raise RuntimeError('ops.ppo_update: %s must be a contiguous int32 tensor on %s' % (name, dev))
+    _arg(op, 'obs', obs, _F32, dev)
     if obs.dim() != 2 or obs.shape[1] % 4:
         raise ValueError('ops.ppo_update: obs must be (n, 4N)')
     n, N = obs.shape[0], obs.shape[1] // 4
@@ -1167,28 +1156,22 @@ def ppo_update(params, m, v, step, obs, actions, returns, values, logp, adv, per
     if M < 1 or n < M:
         raise ValueError('ops.ppo_update: %d rows do not make %d mini-batches' % (n, M))
     count = ppo_param_floats(N, H, deep)
-    for name, ten in (('params', params), ('m', m), ('v', v)):
-        if tuple(ten.shape) != (count,):
-            raise ValueError('ops.ppo_update: %s is %s, the policy needs (%d,)' % (name, tuple(ten.shape), count))
-    for name, ten in (('actions', actions), ('returns', returns), ('values', values), ('logp', logp), ('adv', adv)):
-        if tuple(ten.shape) != (n,):
-            raise ValueError('ops.ppo_update: %s is %s, the batch needs (%d,)' % (name, tuple(ten.shape), n))
+    for name in ('params', 'm', 'v'):
+        _arg(op, name, floats[name], _F32, dev, (count,), 'policy')
+    for name in ('returns', 'values', 'logp', 'adv'):
+        _arg(op, name, floats[name], _F32, dev, (n,))
+    _arg(op, 'actions', actions, _I32, dev, (n,))
+    _arg(op, 'step', step, _I32, dev)
+    _arg(op, 'perm', perm, _I32, dev)
     if tuple(step.shape) != (1,) or perm.dim() != 2 or perm.shape[1] != n:
         raise ValueError('ops.ppo_update: step must be (1,) and perm (E, %d)' % n)
     E = perm.shape[0]
     max_steps = E * M if max_steps is None else int(max_steps)
     if not 0 <= max_steps <= E * M:
         raise ValueError('ops.ppo_update: max_steps = %d is outside 0 .. %d' % (max_steps, E * M))
-    shapes = {'losses': ((E * M, 3), torch.float32), 'gnorm': ((E * M,), torch.float32), 'status': ((2,), torch.int32)}
+    table = {'losses': ((E * M, 3), _F32), 'gnorm': ((E * M,), _F32), 'status': ((2,), _I32)}
     with torch.cuda.device(dev):
-        if out is None:
-            out = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        for name, (shape, dt) in shapes.items():
-            ten = out.get(name) if isinstance(out, dict) else None
-            if not isinstance(ten, torch.Tensor) or ten.dtype != dt or ten.device != dev or not ten.is_contiguous():
-                raise RuntimeError('ops.ppo_update: out %s must be a contiguous %s tensor on %s' % (name, str(dt).split('.')[-1], dev))
-            if tuple(ten.shape) != shape:
-                raise ValueError('ops.ppo_update: out %s is %s, the update needs %s' % (name, tuple(ten.shape), shape))
+        out = _outputs(op, out, table, dev, 'update')
         if E * M == 0:          # (arrays without elements have no address; the launch needs them)
             out['status'].zero_()
             return out

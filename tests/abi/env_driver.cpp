@@ -15,19 +15,9 @@
 #include <vector>
 
 #include "../../stove_amd/csrc/env_step.h"
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != stove_validate::kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-static int validate() {
+static void validate() {
   using stove_validate::env_step;
   const double* d = dev<const double>(1);
   const int* i = dev<const int>(2);
@@ -52,18 +42,6 @@ static int validate() {
   expect("granularity = -5", env_step(d, d, d, d, i, i, 3, 3, -5, 32), 1);
   expect("res = 0", env_step(d, d, d, d, i, i, 3, 3, 5, 0), 1);
   expect("res = -32", env_step(d, d, d, d, i, i, 3, 3, 5, -32), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
-}
-
-template <typename T>
-static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <typename T>
-static bool write_v(std::FILE* f, const std::vector<T>& v) {
-  return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
 }
 
 // M environments' rows and the per-environment body of env_step_k
@@ -143,7 +121,7 @@ static int run(const char* in_path, const char* out_path) {
 
 // Three environments, the same state in 0 and 2; environment 1 gets an action index of 9, then of -1: status [0, 2, 0], environment 1
 // exactly as handed over (x, v, and its collisions entry), 0 and 2 as in a run where all three actions were fine.
-static int status() {
+static void status() {
   const int M = 3, N = 3;
   Batch b;
   b.M = M;
@@ -183,14 +161,6 @@ static int status() {
     expect("the twins agree", std::memcmp(t.x.data(), t.x.data() + 4 * N, 2 * N * sizeof(double)) != 0, 0);
   }
   expect("premise: the clean step moved environment 0", std::memcmp(clean.x.data(), b.x.data(), 2 * N * sizeof(double)) == 0, 0);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
-int main(int argc, char** argv) {
-  if (argc == 2 && std::strcmp(argv[1], "validate") == 0) return validate();
-  if (argc == 2 && std::strcmp(argv[1], "status") == 0) return status();
-  if (argc == 4 && std::strcmp(argv[1], "run") == 0) return run(argv[2], argv[3]);
-  std::fprintf(stderr, "usage: %s validate | status | run IN OUT\n", argv[0]);
-  return 2;
-}
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}, {"status", status}}, run); }

@@ -17,19 +17,9 @@
 #include <vector>
 
 #include "../../stove_amd/csrc/env_search.h"
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != stove_validate::kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-static int validate() {
+static void validate() {
   const double* d = dev<const double>(1);
   const int* i = dev<const int>(2);
   const double* nd = nullptr;
@@ -67,8 +57,6 @@ static int validate() {
   expect("granularity = 0", call(3, 1, 3, 10, 5, 46, 0), 1);
   expect("R = 0 at M = 0", stove_validate::env_search(nd, nd, nd, nd, ni, ni, ni, ni, ni, ni, nd, ni, nd, ni, ni, 0, 0, 3, 10, 5, 46, 5), 1);
   expect("M R past int", call(1 << 20, 1 << 12, 3, 10, 5, 46, 5), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
 struct OneTree {
@@ -113,16 +101,6 @@ struct Search {
     return out;
   }
 };
-
-template <typename T>
-static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <typename T>
-static bool write_v(std::FILE* f, const std::vector<T>& v) {
-  return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
 
 static int run(const char* in_path, const char* out_path) {
   std::FILE* in = std::fopen(in_path, "rb");
@@ -203,7 +181,7 @@ static Search three(int D, int cap) {
   return s;
 }
 
-static int status() {
+static void status() {
   const int D = 4, runs = 30, cap = 1 + env_search::kActions * runs;
   const std::vector<int32_t> tab = table(runs, D, 12345u);         // the three trees read the same rows
   // the clean run, remembered after every iteration
@@ -291,14 +269,6 @@ static int status() {
     const std::vector<int32_t> a = s.actions();
     expect("an empty search returns action 0", a[0] != 0 || a[1] != 0 || a[2] != 0, 0);
   }
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
-int main(int argc, char** argv) {
-  if (argc == 2 && std::strcmp(argv[1], "validate") == 0) return validate();
-  if (argc == 2 && std::strcmp(argv[1], "status") == 0) return status();
-  if (argc == 4 && std::strcmp(argv[1], "run") == 0) return run(argv[2], argv[3]);
-  std::fprintf(stderr, "usage: %s validate | status | run IN OUT\n", argv[0]);
-  return 2;
-}
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}, {"status", status}}, run); }

@@ -16,19 +16,9 @@
 #include <vector>
 
 #include "../../stove_amd/csrc/plan_tree.h"
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != stove_validate::kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-static int validate() {
+static void validate() {
   using stove_validate::plan_search;
   const float* f = dev<const float>(1);
   const int* i = dev<const int>(2);
@@ -76,18 +66,6 @@ static int validate() {
   expect("app_dim = 13", plan_search(f, i, i, i, i, i, d, i, d, i, i, f, i, f, f, f, f, ws, 3, 22, 9, 4, 2, 3, 13, 5), 1);
   expect("app_dim < 0", plan_search(f, i, i, i, i, i, d, i, d, i, i, f, i, f, f, f, f, ws, 3, 22, 9, 4, 2, 3, -1, 5), 1);
   expect("rows x steps beyond an int's reach", plan_search(f, i, i, i, i, i, d, i, d, i, i, f, i, f, f, f, f, ws, 1 << 20, 22, 9, 1 << 20, 2, 3, 3, 5), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
-}
-
-template <typename T>
-static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <typename T>
-static bool write_v(std::FILE* f, const std::vector<T>& v) {
-  return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
 }
 
 // M trees' arrays and the per-iteration loop of stove_plan_search (a frozen tree is skipped, its sel / child entries stay -1)
@@ -161,7 +139,7 @@ static int run(const char* in_path, const char* out_path) {
 // five of them are damaged, each in its own way, and all go on for R1 more.  A damaged tree must end with status 2 and exactly the
 // arrays it was handed (nothing written, and -- under the address sanitizer -- nothing read outside them); tree 0 must end as in a
 // forest nobody damaged.
-static int corrupt() {
+static void corrupt() {
   const int M = 6, A = 3, D = 8, cap = 1 + A * 12, R0 = 6, R1 = 4;
   std::vector<float> q((size_t)(R0 + R1) * M * A);
   for (size_t k = 0; k < q.size(); ++k) q[k] = -1.0f - 0.37f * (float)((k * 2654435761u >> 7) % 1000) / 1000.0f;
@@ -203,14 +181,6 @@ static int corrupt() {
     expect("status 2 (second set)", g.status[m] != plan_tree::kBad, 0);
     expect("left as handed over (second set)", !g.same_tree(handed2, m), 0);
   }
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
-int main(int argc, char** argv) {
-  if (argc == 2 && std::strcmp(argv[1], "validate") == 0) return validate();
-  if (argc == 2 && std::strcmp(argv[1], "corrupt") == 0) return corrupt();
-  if (argc == 4 && std::strcmp(argv[1], "run") == 0) return run(argv[2], argv[3]);
-  std::fprintf(stderr, "usage: %s validate | corrupt | run IN OUT\n", argv[0]);
-  return 2;
-}
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}, {"corrupt", corrupt}}, run); }

@@ -1,24 +1,14 @@
 // Host-only driver of stove_plan_expand's argument check (stove_amd/csrc/validate.h: plan_expand, plan_dims_bad), built with
 // -fsanitize=address,undefined by tests/test_mcts_cpu.py, in the manner of validate_driver.cpp: fake, never-mapped "device"
-// pointers that the layer must not dereference; one line per failure, exit status = number of failures.
+// pointers that the layer must not dereference.  `plan_validate_driver validate`: one line per failure, exit status = number of failures.
 #include <cstdio>
 #include <cstdint>
 
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
 using namespace stove_validate;
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-int main() {
+static void validate() {
   const float* f = dev<const float>(1);
   const int* i = dev<const int>(2);
   void* ws = dev<void>(3);
@@ -49,6 +39,6 @@ int main() {
   expect("app_dim < 0", plan_expand(f, i, i, i, f, i, f, f, f, f, f, ws, 3, 22, 9, 4, 2, 3, -1), 1);
   expect("cap = A", plan_expand(f, i, i, i, f, i, f, f, f, f, f, ws, 3, 9, 9, 4, 2, 3, 3), 1);
   expect("rows x steps beyond an int's reach", plan_expand(f, i, i, i, f, i, f, f, f, f, f, ws, 1 << 20, 22, 9, 1 << 20, 2, 3, 3), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
+
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}}); }

@@ -17,19 +17,9 @@
 #include <vector>
 
 #include "../../stove_amd/csrc/ppo_policy.h"
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != stove_validate::kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-static int validate() {
+static void validate() {
   const double* d = dev<const double>(1);
   const float* f = dev<const float>(2);
   const int* i = dev<const int>(3);
@@ -65,8 +55,6 @@ static int validate() {
   expect("granularity = 0", call(3, 5, 3, 64, 0), 1);
   expect("N = 7 at B = 0", stove_validate::ppo_collect(nd, nd, nd, nd, nf, nf, nf, ni, nf, nf, nf, nf, nf, ni, 0, 5, 7, 64, 5), 1);
   expect("B (S + 1) 4N past int", call(1 << 20, 1 << 10, 6, 64, 5), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
 // one environment's rows, each vector of exactly its length
@@ -109,16 +97,6 @@ struct Batch {
                                      &e.margin);
   }
 };
-
-template <typename T>
-static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <typename T>
-static bool write_v(std::FILE* f, const std::vector<T>& v) {
-  return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
 
 static int run(const char* in_path, const char* out_path) {
   std::FILE* in = std::fopen(in_path, "rb");
@@ -201,7 +179,7 @@ static Batch three(int H, int deep, int S) {
   return b;
 }
 
-static int status() {
+static void status() {
   for (int deep = 0; deep < 2; ++deep) {
     const int S = 12, H = deep ? 40 : 64;
     const Batch start = three(H, deep, S);
@@ -248,14 +226,6 @@ static int status() {
       expect("S = 0: obs[0] is written", std::memcmp(none.envs[0].obs.data(), o, sizeof(o)) != 0, 0);
     }
   }
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
-int main(int argc, char** argv) {
-  if (argc == 2 && std::strcmp(argv[1], "validate") == 0) return validate();
-  if (argc == 2 && std::strcmp(argv[1], "status") == 0) return status();
-  if (argc == 4 && std::strcmp(argv[1], "run") == 0) return run(argv[2], argv[3]);
-  std::fprintf(stderr, "usage: %s validate | status | run IN OUT\n", argv[0]);
-  return 2;
-}
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}, {"status", status}}, run); }

@@ -17,25 +17,9 @@
 #include <vector>
 
 #include "../../stove_amd/csrc/ppo_update.h"
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != stove_validate::kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-static void check(const char* what, bool ok) {
-  if (!ok) {
-    std::printf("FAIL %s\n", what);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-static int validate() {
+static void validate() {
   const float* f = dev<const float>(2);
   const int* i = dev<const int>(3);
   // (params, m, v, step, obs, actions, returns, values, logp, adv, perm, losses, gnorm, status, n, E, M, max_steps, N, H)
@@ -66,8 +50,6 @@ static int validate() {
   expect("H = 0", call(64, 2, 4, 8, 3, 0), 1);
   expect("H = 129", call(64, 2, 4, 8, 3, 129), 1);
   expect("E n past int", call(1 << 20, 1 << 12, 4, 8, 3, 64), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
 struct Problem {
@@ -92,16 +74,6 @@ struct Problem {
     return same(params, o.params) && same(m, o.m) && same(v, o.v) && step == o.step && same(losses, o.losses) && same(gnorm, o.gnorm);
   }
 };
-
-template <typename T>
-static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <typename T>
-static bool write_v(std::FILE* f, const std::vector<T>& v) {
-  return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-}
 
 static int run(const char* in_path, const char* out_path) {
   std::FILE* in = std::fopen(in_path, "rb");
@@ -164,7 +136,7 @@ static Problem small(int H, int deep) {
   return p;
 }
 
-static int status() {
+static void status() {
   for (int deep = 0; deep < 2; ++deep) {
     const Problem start = small(deep ? 40 : 64, deep);
     Problem clean = start;
@@ -249,14 +221,6 @@ static int status() {
       check("the unclipped value loss runs", plain.status == 0 && fin);
     }
   }
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
 
-int main(int argc, char** argv) {
-  if (argc == 2 && std::strcmp(argv[1], "validate") == 0) return validate();
-  if (argc == 2 && std::strcmp(argv[1], "status") == 0) return status();
-  if (argc == 4 && std::strcmp(argv[1], "run") == 0) return run(argv[2], argv[3]);
-  std::fprintf(stderr, "usage: %s validate | status | run IN OUT\n", argv[0]);
-  return 2;
-}
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}, {"status", status}}, run); }

@@ -1,25 +1,15 @@
 // Host-only driver of the C ABI's argument-validation layer (stove_amd/csrc/validate.h -- the very header libstove_hip.so's entry
-// points call first), built with -fsanitize=address,undefined by tests/test_host_cpu.py and run in the CPU suite: every case is
+// points call first), built with -fsanitize=address,undefined by tests/test_host_cpu.py and run in the CPU suite (`validate_driver validate`): every case is
 // (what, expected code), one line per failure, exit status = number of failures.  "Device" pointers are fake, suitably aligned
 // addresses: the layer must never dereference them (a dereference is an ASan report and a non-zero exit).
 #include <cstdio>
 #include <cstdint>
 
-#include "../../stove_amd/csrc/validate.h"
+#include "driver.h"
 
 using namespace stove_validate;
 
-static int failures = 0;
-static void expect(const char* what, int got, int want) {
-  if ((got != 0) != (want != 0) || (want != 0 && got != kStoveInvalidValue)) {
-    std::printf("FAIL %s: got %d, want %d\n", what, got, want);
-    ++failures;
-  }
-}
-template <typename T>
-static T* dev(uintptr_t k) { return reinterpret_cast<T*>(uintptr_t(0x7000000000ull) + k * 4096); }   // never mapped
-
-int main() {
+static void validate() {
   const float* f = dev<const float>(1);
   float* o = dev<float>(2);
   void* ws = dev<void>(3);
@@ -92,6 +82,6 @@ int main() {
   expect("gemm B not 16-byte aligned", gemm(f, reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(f) + 4), o, 8, 8, 64, 64, 64, 8, 0, 0, 2, 1, nullptr), 1);
   expect("gemm split-K without a workspace", gemm(f, f, o, 8, 8, 64, 64, 64, 8, 0, 0, 2, 4, nullptr), 1);
   expect("gemm nsplit = 4", gemm(f, f, o, 8, 8, 64, 64, 64, 8, 0, 0, 4, 1, nullptr), 1);
-  std::printf("%d failure(s)\n", failures);
-  return failures;
 }
+
+int main(int argc, char** argv) { return driver_main(argc, argv, {{"validate", validate}}); }

@@ -27,6 +27,9 @@ CASES = {
     't1_n1_d2': (1, 1, 2, 1, 5, 0.0, False, (0,)),
     't4_n1_d3': (1, 1, 3, 12, 5, 0.0, False, (0, 1, 2, 3)),
     't4_n3_d3': (1, 3, 3, 12, 5, 0.0, False, (0, 1, 2, 3)),
+    't4_n2_d3': (1, 2, 3, 12, 5, 0.0, False, (0, 1, 2, 3)),          # (with n4 and n5: every object count the kernel is instantiated for)
+    't4_n4_d3': (1, 4, 3, 12, 5, 0.0, False, (0, 1, 2, 3)),
+    't4_n5_d3': (1, 5, 3, 12, 5, 0.0, False, (1, 3, 5, 6)),
     't65_n3_d10': (1, 3, 10, 40, 5, 0.0, False, _R1),
     't130_r2_n3_d10': (2, 3, 10, 40, 5, 0.0, False, _R2),
     't4_n6_d10': (1, 6, 10, 40, 5, 0.0, False, (1, 13, 16, 17)),

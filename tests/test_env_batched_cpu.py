@@ -1,21 +1,17 @@
 """CPU-side checks (-m "not gpu") of the batched avoidance environments and the episode driver: the step of stove_amd/csrc/env_step.h --
 the text the kernel of csrc/env.hip runs -- compiled host-only under sanitizers with contraction off (tests/abi/env_driver.cpp) and
 held to the numpy class BatchedAvoidance bit for bit; the numpy class held to envs.py (BillardsEnv + AvoidanceTask, themselves pinned
-to the reference by g0_envs.npz); play() and its rings; stove_env_step's host-side argument check; the C ABI addition exported,
-declared and bound.  (All fail before the feature: the header, the modules and the symbol do not exist.)"""
+to the reference by g0_envs.npz); play() and its rings; stove_env_step's host-side argument check; the C ABI addition refusing
+host-visible nonsense.  (All fail before the feature: the header, the modules and the symbol do not exist.)"""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import control_harness
 import env_cases as C
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ULP32 = 2.0 ** -23
 # test_numpy_class_against_envs_py: the largest |x| or |v| deviation between the numpy class and envs.py over all cases, measured on
 # the CPU this was written on, was 8.62e-14 (case n2); the smallest branch margin that is not an exact tie was 3.686e-4 (case n3_g50; 3.68e-4 below).
@@ -26,40 +22,18 @@ BAR = min(100 * MEASURED_DEVIATION, 1e-3 * SMALLEST_MARGIN)
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-    """the driver, built once with the flags of tests/test_plan_tree_cpu.py"""
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    exe = str(tmp_path_factory.mktemp('env_driver') / 'env_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-ffp-contract=off',
-                        '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'env_driver.cpp')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return control_harness.build_driver(tmp_path_factory, 'env_driver')
 
 
 def _drive(exe, tmp_path, name, res=32):
     b = C.start(name)
     acts = C.actions(name)
     M, N = b.M, b.n
-    src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.bin')
-    with open(src, 'wb') as fh:
-        fh.write(np.array([M, N, b.granularity, b.drift, acts is not None, C.STEPS, res, b.use_colors], dtype=np.int32).tobytes())
-        fh.write(np.array([b.hw, b.t, b.friction, b.action_force], dtype=np.float64).tobytes())
-        for a in (b.x, b.v, b.r, b.m):
-            fh.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-        if acts is not None:
-            fh.write(np.ascontiguousarray(acts, dtype=np.int32).tobytes())
-    r = subprocess.run([exe, 'run', src, dst], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr                     # (a sanitizer report ends the driver with a non-zero status)
-    raw = open(dst, 'rb').read()
-    out, pos = {}, 0
-    for key, shape, dt in [('x', (C.STEPS, M, N, 2), np.float64), ('v', (C.STEPS, M, N, 2), np.float64), ('collisions', (C.STEPS, M), np.int32),
-                           ('status', (C.STEPS, M), np.int32), ('frame', (M, 3, res, res), np.float32)]:
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[key] = np.frombuffer(raw[pos:pos + n], dtype=dt).reshape(shape)
-        pos += n
-    assert pos == len(raw)
-    return out
+    outputs = [('x', (C.STEPS, M, N, 2), np.float64), ('v', (C.STEPS, M, N, 2), np.float64), ('collisions', (C.STEPS, M), np.int32),
+               ('status', (C.STEPS, M), np.int32), ('frame', (M, 3, res, res), np.float32)]
+    arrays = [np.asarray(a, dtype=np.float64) for a in (b.x, b.v, b.r, b.m)] + ([np.asarray(acts, dtype=np.int32)] if acts is not None else [])
+    return control_harness.run_driver(exe, tmp_path, [M, N, b.granularity, b.drift, acts is not None, C.STEPS, res, b.use_colors],
+                                      [b.hw, b.t, b.friction, b.action_force], arrays, outputs)
 
 
 def _bits(a):
@@ -100,10 +74,7 @@ def test_validation_and_status_two_under_sanitizers(driver):
     """stove_env_step's host-side argument check (csrc/validate.h: env_step) through the driver: every documented bad argument returns
     hipErrorInvalidValue, an empty batch is accepted, nothing is dereferenced; and status 2: an action index of 9, -1 or 2^30 in
     environment 1 of 3 leaves that environment as handed over and its neighbours as in a clean run, nothing read out of bounds."""
-    for mode in ('validate', 'status'):
-        r = subprocess.run([driver, mode], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(driver, ['validate', 'status'])
 
 
 # ------------------------------------------------------------------------------------------------ 2. numpy class against envs.py
@@ -245,21 +216,10 @@ def test_warm_up_is_initialize_img():
 
 
 # ------------------------------------------------------------------------------------------------ 4. bookkeeping
-def test_env_step_symbol_is_exported_declared_and_bound():
+def test_env_step_refuses_host_visible_nonsense_and_public_surface():
     from stove_amd import _lib, build, ops
     build.build_library()
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), 'stove_env_step')
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^int\s+stove_env_step\s*\(([^;]*?)\)\s*;', header, flags=re.M | re.S)
-    assert m, 'stove_env_step is not declared in include/stove_hip.h'
-    params = [a.strip() for a in m.group(1).split(',')]
-    fn = lib.stove_env_step
-    assert fn.restype is ctypes.c_int and len(fn.argtypes) == len(params) == 19
-    for ct, text in zip(fn.argtypes, params):
-        want = ctypes.c_void_p if '*' in text else (ctypes.c_double if text.startswith('double') else ctypes.c_int)
-        assert ct is want, (text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7
+    fn = _lib.load().stove_env_step
     assert callable(ops.env_step)
     # host-visible nonsense is refused before anything touches a device (this machine has none): hipErrorInvalidValue == 1
     P = ctypes.c_void_p

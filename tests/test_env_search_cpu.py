@@ -2,17 +2,15 @@
 stove_amd/mcts/mcts_env.py held to the reference's recorded trees (tests/golden/g23_mcts_env.npz); the text the kernel runs,
 stove_amd/csrc/env_search.h, compiled host-only under sanitizers with contraction off (tests/abi/env_search_driver.cpp) and held to
 EnvForest bit for bit; every branch of the search taken; play(policy='env_mcts'); stove_env_search's host-side argument check; the C ABI
-addition exported, declared and bound.  (All fail before the feature: the header, the module and the symbol do not exist.)"""
+addition refusing host-visible nonsense.  (All fail before the feature: the header, the module and the symbol do not exist.)"""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import control_harness
 import env_cases as C
 import env_search_cases as E
 
@@ -108,43 +106,21 @@ def test_run_mcts_draws_from_the_global_stream():
 # ------------------------------------------------------------------------------------------------ 2. the header on the CPU
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-    """the driver, built once with the flags of tests/test_env_batched_cpu.py"""
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    exe = str(tmp_path_factory.mktemp('env_search_driver') / 'env_search_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-ffp-contract=off',
-                        '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'env_search_driver.cpp')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return control_harness.build_driver(tmp_path_factory, 'env_search_driver')
 
 
 def _drive(exe, tmp_path, name):
     T, R, N, D, runs = E.shape(name)
     b, draws = E.start(name)
     cap = 1 + E.A * runs
-    src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.bin')
-    with open(src, 'wb') as fh:
-        fh.write(np.array([T, R, N, D, runs, cap, b.granularity, b.drift], dtype=np.int32).tobytes())
-        fh.write(np.array([b.hw, b.t, b.friction, b.action_force], dtype=np.float64).tobytes())
-        for a in (b.x, b.v, b.r, b.m):
-            fh.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-        fh.write(np.ascontiguousarray(draws, dtype=np.int32).tobytes())
-    r = subprocess.run([exe, 'run', src, dst], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr                     # (a sanitizer report ends the driver with a non-zero status)
-    raw = open(dst, 'rb').read()
-    out, pos = {}, 0
-    for key, shape, dt in [(k, (T, cap), np.int32) for k in E.ARRAYS[:5]] + [('Qsa', (T, cap), np.float64), ('used', (T,), np.int32),
-                                                                             ('status', (T,), np.int32), ('gap', (T,), np.float64),
-                                                                             ('action', (T // R,), np.int32)]:
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[key] = np.frombuffer(raw[pos:pos + n], dtype=dt).reshape(shape)
-        pos += n
-    assert pos == len(raw)
-    return out
+    outputs = [(k, (T, cap), np.int32) for k in E.ARRAYS[:5]] + [('Qsa', (T, cap), np.float64), ('used', (T,), np.int32), ('status', (T,), np.int32),
+                                                                 ('gap', (T,), np.float64), ('action', (T // R,), np.int32)]
+    arrays = [np.asarray(a, dtype=np.float64) for a in (b.x, b.v, b.r, b.m)] + [np.asarray(draws, dtype=np.int32)]
+    return control_harness.run_driver(exe, tmp_path, [T, R, N, D, runs, cap, b.granularity, b.drift], [b.hw, b.t, b.friction, b.action_force],
+                                      arrays, outputs)
 
 
-# T = 1, 4, 65 (and 130); N = 1, 3, 6; D = 2, 3, 10; R = 1, 2, 4; granularity 5 and 50; a friction case and a drift case
+# T = 1, 4, 65 (and 130); N = 1 .. 6; D = 2, 3, 10; R = 1, 2, 4; granularity 5 and 50; a friction case and a drift case
 @pytest.mark.parametrize('name', [n for n in E.CASES if '_runs' not in n])
 def test_header_equals_the_host_forest_bit_for_bit(driver, tmp_path, name):
     out = _drive(driver, tmp_path, name)
@@ -163,7 +139,7 @@ def test_header_equals_the_host_forest_bit_for_bit(driver, tmp_path, name):
 def test_case_shapes_cover_what_they_claim():
     shapes = {n: E.shape(n) for n in E.CASES}
     assert {s[0] for s in shapes.values()} >= {1, 4, 65, 130} and {s[1] for s in shapes.values()} >= {1, 2, 4}
-    assert {s[2] for s in shapes.values()} == {1, 3, 6}
+    assert {s[2] for s in shapes.values()} == {1, 2, 3, 4, 5, 6}
     assert {(s[3], s[4]) for s in shapes.values()} >= {(D, runs) for D in (2, 3, 10) for runs in (1, 12, 40)}
     assert E.CASES['t4_r4_n3_g50'][4] == 50 and E.CASES['t4_n3_fric'][5] > 0 and E.CASES['t4_n3_drift'][6]
     fric, plain = E.host_search('t4_n3_fric')[0], E.host_search('t4_n3_d10_runs40')[0]
@@ -175,10 +151,7 @@ def test_validation_and_status_under_sanitizers(driver):
     returns hipErrorInvalidValue, empty searches are accepted, nothing is dereferenced; status 2: a draw of 9, -1 or 2^30 in one tree of
     three leaves that tree as it stood at the start of the iteration and its neighbours as in a clean run; status 1: a cap one expansion
     short freezes the tree at its last expansion; nothing read or written out of bounds."""
-    for mode in ('validate', 'status'):
-        r = subprocess.run([driver, mode], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(driver, ['validate', 'status'])
 
 
 def test_host_forest_freezes_like_the_header():
@@ -317,21 +290,10 @@ def test_env_mcts_is_not_below_random():
 
 
 # ------------------------------------------------------------------------------------------------ 5. bookkeeping
-def test_env_search_symbol_is_exported_declared_and_bound():
+def test_env_search_refuses_host_visible_nonsense_and_public_surface():
     from stove_amd import _lib, build, ops
     build.build_library()
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), 'stove_env_search')
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^int\s+stove_env_search\s*\(([^;]*?)\)\s*;', header, flags=re.M | re.S)
-    assert m, 'stove_env_search is not declared in include/stove_hip.h'
-    params = [a.strip() for a in m.group(1).split(',')]
-    fn = lib.stove_env_search
-    assert fn.restype is ctypes.c_int and len(fn.argtypes) == len(params) == 28
-    for ct, text in zip(fn.argtypes, params):
-        want = ctypes.c_void_p if '*' in text else (ctypes.c_double if text.startswith('double') else ctypes.c_int)
-        assert ct is want, (text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7          # an addition: the version stays
+    fn = _lib.load().stove_env_search
     # host-visible nonsense is refused before anything touches a device (this machine may have none): hipErrorInvalidValue == 1
     P = ctypes.c_void_p
     good = ctypes.create_string_buffer(64)

@@ -9,27 +9,12 @@ import pytest
 import torch
 
 import env_cases as C
+from control_harness import guarded, margins_intact
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 ULP32 = 2.0 ** -23
-GUARD = 64
 INVALID = 1          # hipErrorInvalidValue
-
-
-def _guarded(values, fill):
-    """a contiguous device copy of `values` with GUARD elements of `fill` in front of and behind it -> (view, whole buffer)"""
-    flat = values.reshape(-1)
-    buf = torch.full((flat.numel() + 2 * GUARD,), fill, dtype=values.dtype)
-    buf[GUARD:GUARD + flat.numel()] = flat
-    buf = buf.to(DEV)
-    return buf[GUARD:GUARD + flat.numel()].view(values.shape), buf
-
-
-def _margins_intact(buffers):
-    for k, buf in buffers.items():
-        for edge in (buf[:GUARD].cpu(), buf[-GUARD:].cpu()):
-            assert bool(torch.isnan(edge).all()) if buf.dtype.is_floating_point else bool((edge == -77).all()), k
 
 
 def _batch(name, M, res, use_colors):
@@ -46,12 +31,12 @@ def _device_state(b, render=True):
     """guarded device copies of a host batch's arrays and of the outputs"""
     t, buffers = {}, {}
     for k in ('x', 'v', 'r', 'm'):
-        t[k], buffers[k] = _guarded(torch.from_numpy(getattr(b, k).copy()), float('nan'))
-    t['collisions'], buffers['collisions'] = _guarded(torch.full((b.M,), -7, dtype=torch.int32), -77)
-    t['status'], buffers['status'] = _guarded(torch.full((b.M,), -7, dtype=torch.int32), -77)
+        t[k], buffers[k] = guarded(torch.from_numpy(getattr(b, k).copy()), float('nan'))
+    t['collisions'], buffers['collisions'] = guarded(torch.full((b.M,), -7, dtype=torch.int32), -77)
+    t['status'], buffers['status'] = guarded(torch.full((b.M,), -7, dtype=torch.int32), -77)
     t['frames'] = None
     if render:
-        t['frames'], buffers['frames'] = _guarded(torch.full((b.M, 3, b.res, b.res), float('nan')), float('nan'))
+        t['frames'], buffers['frames'] = guarded(torch.full((b.M, 3, b.res, b.res), float('nan')), float('nan'))
     return t, buffers
 
 
@@ -97,7 +82,7 @@ def test_kernel_equals_the_numpy_class(name, M, res, use_colors, render):
     assert worst <= ULP32
     if render:
         assert float(got.max()) > 0.99 and float(got.min()) == 0.0
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 6. status, refusals
@@ -121,7 +106,7 @@ def test_status_two(bad):
     assert torch.equal(t['frames'][[0, 2]].view(torch.int32), clean['frames'][[0, 2]].view(torch.int32))
     assert torch.equal(t['collisions'][[0, 2]], clean['collisions'][[0, 2]])
     assert not _same_bits(t['x'][0].cpu().numpy(), b.x[0])
-    _margins_intact(buffers)
+    margins_intact(buffers)
     # the class: the same through BatchedAvoidance on the device and on the host
     dev, host = BatchedAvoidance([0, 1, 0], device=DEV), BatchedAvoidance([0, 1, 0])
     dev.step([1, bad, 1])
@@ -153,7 +138,7 @@ def test_host_visible_refusals_launch_nothing():
     assert call() == 0                                    # and the valid call still runs
     torch.cuda.synchronize()
     assert t['status'].tolist() == [0, 0, 0]
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 7. graph capture
@@ -190,7 +175,7 @@ def test_captured_step_replays_bit_for_bit():
     for _ in range(3):
         host.step(C.actions('n3')[0, rows])
     assert _same_bits(t['x'].cpu().numpy(), host.x) and _same_bits(t['v'].cpu().numpy(), host.v)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 8. play

@@ -9,26 +9,11 @@ import pytest
 import torch
 
 import env_search_cases as E
+from control_harness import guarded, margins_intact
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-GUARD = 64
 MIN_GAP = 1e-9
-
-
-def _guarded(values, fill):
-    """a contiguous device copy of `values` with GUARD elements of `fill` in front of and behind it -> (view, whole buffer)"""
-    flat = values.reshape(-1)
-    buf = torch.full((flat.numel() + 2 * GUARD,), fill, dtype=values.dtype)
-    buf[GUARD:GUARD + flat.numel()] = flat
-    buf = buf.to(DEV)
-    return buf[GUARD:GUARD + flat.numel()].view(values.shape), buf
-
-
-def _margins_intact(buffers):
-    for k, buf in buffers.items():
-        for edge in (buf[:GUARD].cpu(), buf[-GUARD:].cpu()):
-            assert bool(torch.isnan(edge).all()) if buf.dtype.is_floating_point else bool((edge == -77).all()), k
 
 
 def _device_search(b, draws, forest, R, graph=False):
@@ -37,11 +22,11 @@ def _device_search(b, draws, forest, R, graph=False):
     from stove_amd import ops
     buffers, state = {}, {}
     for k in ('x', 'v', 'r', 'm'):
-        state[k], buffers[k] = _guarded(torch.from_numpy(np.array(getattr(b, k))), float('nan'))
-    table, buffers['draws'] = _guarded(torch.from_numpy(np.array(draws, dtype=np.int32)), -77)
+        state[k], buffers[k] = guarded(torch.from_numpy(np.array(getattr(b, k))), float('nan'))
+    table, buffers['draws'] = guarded(torch.from_numpy(np.array(draws, dtype=np.int32)), -77)
     arrays = {}
     for k, ten in forest.to_device('cpu').items():
-        arrays[k], buffers[k] = _guarded(ten, float('nan') if ten.dtype.is_floating_point else -77)
+        arrays[k], buffers[k] = guarded(ten, float('nan') if ten.dtype.is_floating_point else -77)
     call = lambda: ops.env_search(state['x'], state['v'], state['r'], state['m'], table, arrays, forest.D, b.granularity, b.hw, b.t, b.friction,
                                   b.action_force, b.drift, replicas=R)
     if not graph:
@@ -94,7 +79,7 @@ def test_kernel_equals_the_host_forest_bit_for_bit(name):
     assert np.array_equal(np.isinf(gaps), np.isinf(host.gap)) and np.allclose(gaps[np.isfinite(gaps)], host.gap[np.isfinite(gaps)], rtol=0, atol=1e-12)
     for k in ('x', 'v', 'r', 'm'):                                               # the environment state is bit for bit untouched
         assert np.array_equal(state[k].cpu().numpy().view(np.int64), np.ascontiguousarray(getattr(b, k)).view(np.int64)), k
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the reference's recorded trees
@@ -113,7 +98,7 @@ def test_kernel_reproduces_the_reference_trees(case):
     assert not f.status.any() and action.tolist() == [int(G['action'])] * 3
     for t in range(3):
         E.assert_golden_tree(f, t, G)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 3. frozen trees
@@ -135,7 +120,7 @@ def test_status_two_freezes_the_tree_and_spares_its_wave(bad):
     want = frozen.search(b, table, R)
     assert frozen.status.tolist() == [2 if t == 2 else 0 for t in range(T)] and int(frozen.Ns[2, 0]) == 5
     _assert_equal(arrays, action, frozen, want)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 def test_status_one_freezes_a_tree_out_of_slots():
@@ -149,7 +134,7 @@ def test_status_one_freezes_a_tree_out_of_slots():
     assert short.status.tolist() == [1] * T and (short.used == 1 + 5 * E.A).all()
     arrays, action, _, buffers = _device_search(b, draws, dev, R)
     _assert_equal(arrays, action, short, want)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 def test_status_one_spares_the_wave_mates_of_a_full_tree():
@@ -174,7 +159,7 @@ def test_status_one_spares_the_wave_mates_of_a_full_tree():
             rest = getattr(clean, k)[[0, 1, 3], 55:]
             assert (rest == (-1 if k in ('first', 'parent') else 0)).all(), k
     assert action.cpu().numpy()[[0, 1, 3]].tolist() == clean_action[[0, 1, 3]].tolist()
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 4. empty calls
@@ -186,7 +171,7 @@ def test_empty_searches_are_accepted():
     arrays, action, _, buffers = _device_search(b, np.zeros((4, 0, 3), dtype=np.int32), f, 1)
     assert action.tolist() == [0] * 4 and arrays['used'].tolist() == [1] * 4 and arrays['status'].tolist() == [0] * 4
     assert bool((arrays['first'] == -1).all())
-    _margins_intact(buffers)
+    margins_intact(buffers)
     assert _lib.load().stove_env_search(*([None] * 15), 0, 1, 3, 3, 12, 109, 5, 0, 10.0, 1.0, 0.0, 0.6, None) == 0
     e = torch.zeros(0, 3, 2, dtype=torch.float64, device=DEV)
     s = torch.zeros(0, 3, dtype=torch.float64, device=DEV)
@@ -205,7 +190,7 @@ def test_captured_search_replays_bit_for_bit():
     host, want = E.host_search(name)
     arrays, action, _, buffers = _device_search(b, draws, EnvForest(T, E.A, D, runs), R, graph=True)
     _assert_equal(arrays, action, host, want)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 6. the episode

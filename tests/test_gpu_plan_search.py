@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from control_harness import guarded, margins_intact
 from test_gpu_dynamics import make_cfg
 from test_gpu_plan import A, CFG, DEV, GAMMA, N, _inputs, _model, _weights
 
@@ -66,15 +67,6 @@ def _host_search(D, R, variant='same', acts=None):
     return h, trees, actions, np.stack(leaves) if leaves else np.zeros((0, h.num_mcts), dtype=np.int64)
 
 
-def _guarded(values, guard, fill):
-    """a contiguous device copy of `values` with `guard` elements of `fill` in front of and behind it -> (view, whole buffer)"""
-    flat = values.reshape(-1)
-    buf = torch.full((flat.numel() + 2 * guard,), fill, dtype=values.dtype)
-    buf[guard:guard + flat.numel()] = flat
-    buf = buf.to(DEV)
-    return buf[guard:guard + flat.numel()].view(values.shape), buf
-
-
 def _direct(D, acts, variant='same', cap=None, used0=None, guard=0, trace=True, damage=None):
     """ops.plan_search on fresh trees -> dict(action, sel, pool, arrays..., buffers): everything on the host after one synchronise.
     guard > 0: the pool and every array sit inside larger buffers filled with NaN / a sentinel, returned under 'buffers'.
@@ -92,11 +84,11 @@ def _direct(D, acts, variant='same', cap=None, used0=None, guard=0, trace=True, 
         damage(f)
     pool = torch.zeros(M, cap, N, 18)
     pool[:, 0] = z
-    pool, pool_buf = _guarded(pool, guard * N * 18, float('nan'))
+    pool, pool_buf = guarded(pool, float('nan'), guard * N * 18)
     arrays, buffers = {}, {'pool': pool_buf}
     for k, t in f.to_device('cpu').items():
-        arrays[k], buffers[k] = _guarded(t, guard, float('nan') if t.dtype == torch.float64 else -77)
-    sel, buffers['sel'] = _guarded(torch.full((R, M), -5, dtype=torch.int32), guard, -77) if trace else (None, None)
+        arrays[k], buffers[k] = guarded(t, float('nan') if t.dtype == torch.float64 else -77, guard)
+    sel, buffers['sel'] = guarded(torch.full((R, M), -5, dtype=torch.int32), -77, guard) if trace else (None, None)
     emb_w, emb_b, gnn, rh = _weights(st)
     with torch.no_grad():
         action = ops.plan_search(pool, arrays, app.to(DEV), torch.from_numpy(acts.astype(np.int32)).to(DEV), emb_w, emb_b, gnn, rh, D, 2,
@@ -218,14 +210,7 @@ def test_reproducible_forward_only_and_empty():
 
 # ------------------------------------------------------------------------------------------------ 4. out of slots on the device
 def _margins_intact(out):
-    g = out['guard']
-    for k, buf in out['buffers'].items():
-        gg = g * N * 18 if k == 'pool' else g
-        for edge in (buf[:gg], buf[-gg:]):
-            if buf.dtype.is_floating_point:
-                assert bool(torch.isnan(edge).all()), k
-            else:
-                assert bool((edge == -77).all()), k
+    margins_intact(out['buffers'], {k: out['guard'] * (N * 18 if k == 'pool' else 1) for k in out['buffers']})
 
 
 def test_a_tree_out_of_slots_on_the_device():

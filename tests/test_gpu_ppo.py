@@ -9,26 +9,11 @@ import pytest
 import torch
 
 import ppo_cases as P
+from control_harness import guarded, margins_intact
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-GUARD = 64
 FLOATS = ('obs', 'rewards', 'values', 'logp', 'next_value', 'returns')
-
-
-def _guarded(values, fill):
-    """a contiguous device copy of `values` with GUARD elements of `fill` in front of and behind it -> (view, whole buffer)"""
-    flat = values.reshape(-1)
-    buf = torch.full((flat.numel() + 2 * GUARD,), fill, dtype=values.dtype)
-    buf[GUARD:GUARD + flat.numel()] = flat
-    buf = buf.to(DEV)
-    return buf[GUARD:GUARD + flat.numel()].view(values.shape), buf
-
-
-def _margins_intact(buffers):
-    for k, buf in buffers.items():
-        for edge in (buf[:GUARD].cpu(), buf[-GUARD:].cpu()):
-            assert bool(torch.isnan(edge).all()) if buf.dtype.is_floating_point else bool((edge == -77).all()), k
 
 
 def _device_collect(name, image=None, batch=None, graph=False):
@@ -40,14 +25,14 @@ def _device_collect(name, image=None, batch=None, graph=False):
     image = P.policy(N, H, deep).flat_params() if image is None else image
     buffers, state, out = {}, {}, {}
     for k in ('x', 'v', 'r', 'm'):
-        state[k], buffers[k] = _guarded(torch.from_numpy(np.array(getattr(b, k))), float('nan'))
-    params, buffers['params'] = _guarded(image, float('nan'))
-    u, buffers['u'] = _guarded(torch.from_numpy(np.array(P.table(name))), float('nan'))
+        state[k], buffers[k] = guarded(torch.from_numpy(np.array(getattr(b, k))), float('nan'))
+    params, buffers['params'] = guarded(image, float('nan'))
+    u, buffers['u'] = guarded(torch.from_numpy(np.array(P.table(name))), float('nan'))
     shapes = {'obs': (B, S + 1, 4 * N), 'actions': (B, S), 'rewards': (B, S), 'values': (B, S), 'logp': (B, S), 'next_value': (B,),
               'returns': (B, S), 'status': (B,)}
     for k, shape in shapes.items():
         fill = torch.full(shape, float('nan')) if k in FLOATS else torch.full(shape, -77, dtype=torch.int32)
-        out[k], buffers[k] = _guarded(fill, float('nan') if k in FLOATS else -77)
+        out[k], buffers[k] = guarded(fill, float('nan') if k in FLOATS else -77)
     call = lambda: ops.ppo_collect(state['x'], state['v'], state['r'], state['m'], params, u, H, deep, b.granularity, b.hw, b.t, b.friction,
                                    b.action_force, b.drift, P.DISCOUNT, out=out)
     if not graph:
@@ -93,7 +78,7 @@ def test_kernel_equals_the_host_forest_bit_for_bit(name):
     print(f'{name}: smallest host decision margin {P.host_collect(name)[3].min():.3g}, logp within {worst} ulp')
     for k in ('r', 'm'):
         assert np.array_equal(state[k].cpu().numpy(), getattr(P.envs(name), k)), k
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 2. non-finite outputs
@@ -116,7 +101,7 @@ def test_a_nan_weight_stops_every_environment_with_nothing_written(name):
     assert out['status'].tolist() == [3] * B
     _untouched(out, slice(None))
     assert np.array_equal(state['x'].cpu().numpy(), b.x) and np.array_equal(state['v'].cpu().numpy(), b.v)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 def test_a_non_finite_environment_spares_its_wave_and_block_mates():
@@ -131,7 +116,7 @@ def test_a_non_finite_environment_spares_its_wave_and_block_mates():
     _untouched(out, 1)
     assert np.array_equal(state['x'].cpu().numpy()[1], start_x[1]) and np.array_equal(state['v'].cpu().numpy()[1], start_v[1])
     _assert_equals_host(out, state, name, rows=[0, 2, 3, 4])
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 3. empty calls
@@ -158,7 +143,7 @@ def test_captured_collection_replays_bit_for_bit():
     name = 'b5_s16_n6_h64_deep'
     out, state, buffers = _device_collect(name, graph=True)
     _assert_equals_host(out, state, name)
-    _margins_intact(buffers)
+    margins_intact(buffers)
 
 
 # ------------------------------------------------------------------------------------------------ 5. the runner

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import control_harness
 import stove_oracle as O
 from helpers import GOLDEN, load_golden, t_
 
@@ -29,6 +30,62 @@ def test_library_exports_every_declared_symbol():
     # size queries are pure host functions
     assert _lib.load().stove_objspn_tile_floats(65) == 2 * 100 * 2 * 64
     assert _lib.load().stove_scene_saved_floats(10, 3) > 0
+
+
+# entry points that features added one by one, each of which once had a test of its own for being there
+REQUIRED_SYMBOLS = ('stove_gnn_param_floats_cl', 'stove_gnn_grad_floats_cl', 'stove_gnn_bwd_ws_bytes_cl', 'stove_gnn_fwd_cl', 'stove_gnn_bwd_cl',
+                    'stove_dynloop_fwd_cl', 'stove_dynloop_bwd_cl', 'stove_rollout_fwd_cl', 'stove_rollout_sample_fwd',
+                    'stove_rollout_sample_fwd_cl', 'stove_rollout_bwd_ws_bytes', 'stove_rollout_bwd', 'stove_rollout_bwd_ws_bytes_cl',
+                    'stove_rollout_bwd_cl', 'stove_plan_expand_ws_bytes', 'stove_plan_expand', 'stove_plan_search_ws_bytes',
+                    'stove_plan_search', 'stove_env_step', 'stove_env_search', 'stove_ppo_param_floats', 'stove_ppo_collect', 'stove_ppo_update')
+ARGUMENT_COUNTS = {'stove_env_step': 19, 'stove_env_search': 28, 'stove_ppo_collect': 27, 'stove_ppo_update': 29}
+SCALARS = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'uint32_t': ctypes.c_uint32}
+
+
+def _bound_type(text, is_return=False):
+    """whether a ctypes type fits the header's text of a parameter (type and name) or of a return type -> a predicate"""
+    if '*' in text:
+        return lambda ct: ct in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ct, type) and issubclass(ct, ctypes._Pointer))
+    words = [w for w in text.split() if w != 'const']
+    kind = words[0]
+    if is_return and kind == 'void':
+        return lambda ct: ct is None
+    return lambda ct: ct is SCALARS[kind]
+
+
+def test_binding_table_follows_the_header():
+    """Every stove_* function include/stove_hip.h declares is bound by _lib._declare and nothing else is; every binding has the header's
+    argument count, and its return type and each argument type follow from the header's text (a pointer: c_void_p, c_char_p or a
+    POINTER(...); int, float, double, size_t, uint32_t: their ctypes twins; void: None).  No exceptions."""
+    import types
+    from stove_amd import _lib, build
+    build.build_library()
+
+    class Recorder:                                       # stands in for the loaded library: _declare sets restype / argtypes on it
+        def __init__(self):
+            self.bound = {}
+
+        def __getattr__(self, name):
+            return self.bound.setdefault(name, types.SimpleNamespace())
+    rec = Recorder()
+    _lib._declare(rec)
+    decls = control_harness.header_decls()
+    assert len(decls) >= 134
+    assert set(decls) == set(rec.bound), (sorted(set(decls) - set(rec.bound)), sorted(set(rec.bound) - set(decls)))
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name, (ret, params) in decls.items():
+        fn = rec.bound[name]
+        assert hasattr(raw, name), name
+        assert len(fn.argtypes) == len(params), (name, len(fn.argtypes), len(params))
+        assert _bound_type(ret, is_return=True)(fn.restype), (name, ret, fn.restype)
+        for ct, text in zip(fn.argtypes, params):
+            assert _bound_type(text)(ct), (name, text, ct)
+    for name in REQUIRED_SYMBOLS:
+        assert name in decls, name
+    for name, count in ARGUMENT_COUNTS.items():
+        assert len(decls[name][1]) == len(rec.bound[name].argtypes) == count, name
+    assert control_harness.header_decl('stove_ppo_param_floats') == ('size_t', ['int N', 'int H', 'int deep'])
+    assert _lib.load().stove_abi_version() == _lib.ABI_VERSION == 7
 
 
 @pytest.mark.parametrize('seed', [7, 42])
@@ -172,23 +229,12 @@ def test_recognition_network_row_chunks_cover_the_batch_in_whole_tiles():
         ops.ENC_CHUNKS = saved
 
 
-def test_abi_validation_layer_under_sanitizers(tmp_path):
+def test_abi_validation_layer_under_sanitizers(tmp_path_factory):
     """SURVEY section 5 (sanitizers): the C ABI's argument checks (stove_amd/csrc/validate.h, called first by the library's entry points)
     compiled host-only with -fsanitize=address,undefined and driven with NULL tables, empty and negative sizes, out-of-range object
     counts, bad frame maps, short / misaligned leading dimensions: every case returns the documented code and nothing is dereferenced."""
-    import shutil
-    import subprocess
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'abi', 'validate_driver.cpp')
-    exe = str(tmp_path / 'validate_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall', '-Werror',
-                        '-o', exe, src], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS='detect_leaks=1'))
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert '0 failure(s)' in r.stdout
+    exe = control_harness.build_driver(tmp_path_factory, 'validate_driver')
+    control_harness.run_modes(exe, ['validate'], env=dict(os.environ, ASAN_OPTIONS='detect_leaks=1'))
 
 
 def test_library_entry_points_call_the_validation_layer():

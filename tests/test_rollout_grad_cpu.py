@@ -1,43 +1,11 @@
 """CPU-side checks (-m "not gpu") of the rollout backward's C ABI: the four entry points (stove_rollout_bwd_ws_bytes, stove_rollout_bwd
-and their _cl siblings) are exported by the built library, declared in the public header and bound by stove_amd._lib with the header's
-argument counts and types, and the addition leaves the ABI version where it was.  (Fails before the rollout backward: the symbols do
-not exist.)"""
-import ctypes
-import os
-import re
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('stove_rollout_bwd_ws_bytes', 'stove_rollout_bwd', 'stove_rollout_bwd_ws_bytes_cl', 'stove_rollout_bwd_cl')
-
-
-def _header_decl(name):
-    """the declaration of `name` in include/stove_hip.h -> (return type, [parameter text, ...])"""
-    header = open(os.path.join(ROOT, 'include', 'stove_hip.h')).read()
-    m = re.search(r'^(int|size_t)\s+%s\s*\(([^;]*?)\)\s*;' % re.escape(name), header, flags=re.M | re.S)
-    assert m, name + ' is not declared in include/stove_hip.h'
-    return m.group(1), [a.strip() for a in m.group(2).split(',')]
+and their _cl siblings) take the forward's parameters in the forward's order, and their workspace queries reject what the calls reject.
+(That they are exported, declared and bound with the header's types: tests/test_host_cpu.py, test_binding_table_follows_the_header.)"""
+from control_harness import header_decl
 
 
 def _names(name):
-    return [p.split()[-1].lstrip('*') for p in _header_decl(name)[1]]
-
-
-def test_rollout_backward_symbols_are_exported_declared_and_bound():
-    from stove_amd import _lib, build
-    build.build_library()
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in NEW_SYMBOLS:
-        assert hasattr(raw, name), name
-    lib = _lib.load()                                   # _declare() binds every entry of its table: a missing one raises here
-    for name in NEW_SYMBOLS:
-        fn = getattr(lib, name)
-        ret, params = _header_decl(name)
-        assert fn.restype is (ctypes.c_int if ret == 'int' else ctypes.c_size_t), (name, fn.restype)
-        assert len(fn.argtypes) == len(params), (name, len(fn.argtypes), len(params))
-        for ct, text in zip(fn.argtypes, params):        # pointers, ints and floats in the header's order
-            want = ctypes.c_void_p if '*' in text else (ctypes.c_float if text.startswith('float') else ctypes.c_int)
-            assert ct is want, (name, text, ct)
-    assert lib.stove_abi_version() == _lib.ABI_VERSION == 7
+    return [p.split()[-1].lstrip('*') for p in header_decl(name)[1]]
 
 
 def test_backward_entry_points_follow_the_forward_signatures():
