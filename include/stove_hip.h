@@ -453,6 +453,33 @@ int stove_ppo_collect(double* x, double* v, const double* r, const double* m, co
                       int S, int N, int H, int deep, int granularity, int drift, double hw, double t, double friction,
                       double action_force, double discount, void* stream);
 
+/* ---- The model-based PPO arm: S imagined steps of B trajectories on the learned, action-conditioned cl = 32 model under that policy,
+ * next_value and the discounted returns in one launch (csrc/ppo_model.hip; reference runners.py: run_pretrained_batch).  One workgroup
+ * per trajectory, laid out as the small-graph rollout (one object: as the general rollout, which is what stove_rollout_fwd runs there);
+ * 1 <= N <= 6, 1 <= H <= 128, nine actions, 20 + app_dim <= 32.
+ * z0 (B, N, 18) the start states [sx, sy, x, y, vx, vy, latent]; app (B, N, app_dim) the appearance rows (NULL with app_dim == 0);
+ * policy_params the image of stove_ppo_param_floats(N, H, deep); emb_w (4N, 9), emb_b (4N) the action embedding Linear; gnn_params the
+ * stove_gnn_param_floats() image, rh_params the stove_reward_head_param_floats() one; u (B, S) uniforms in [0, 1).
+ * Step s of trajectory b, from the state z (z0 at s == 0, else z_pred[b][s - 1]):
+ *   obs[b][s][4i + c] = (z[i][2 + c] + 1.0f) / 2.0f * hw for c < 2 (positions), z[i][2 + c] / 2.0f * hw for c = 2, 3 (velocities), every
+ *   operation rounded to float32 on its own, hw rounded to float32 once;
+ *   values[b][s], actions[b][s], logp[b][s] from the policy on that row exactly as stove_ppo_collect computes them;
+ *   the model's extra inputs [embedding column of the action + bias (the bits of stove_small_linear on a one-hot row) | app];
+ *   z_pred[b][s], pred[b][s] (optional, NULL to skip): the bits of stove_rollout_fwd with num = A = S on those inputs;
+ *   rewards[b][s] = r - 1.0f with r the bits of stove_reward_head_fwd on pred[b][s].
+ * After step S - 1: obs[b][S], next_value[b], returns[b][s] = returns[b][s + 1] * discount + rewards[b][s] in float32 (no episode ends).
+ * pos_var, vel_std, lat_std are the model's scales; this rollout puts out no deviations and does not read them.
+ * status (B,): 0 collected; 3 a value or logit was not finite at some step (a NaN in z0, say): nothing of that step or after it is
+ * written (no obs row, no z_pred, no next_value, no returns), the other trajectories are unaffected.  One launch on `stream`, no
+ * synchronisation (the call can be captured), no atomics, deterministic.  A NULL required array, B < 0, S < 0, N outside 1 .. 6, H
+ * outside 1 .. 128, app_dim outside 0 .. 12, lim_enc outside 0 .. 32: hipErrorInvalidValue, nothing launched.  B == 0 is a valid empty
+ * call; with S == 0 only obs (B, 1, 4N), next_value and status are written (the (B, S) arrays and z_pred may then be NULL). */
+int stove_ppo_collect_model(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
+                            const float* gnn_params, const float* rh_params, const float* u, float* z_pred, float* pred, float* obs,
+                            int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status, int B,
+                            int S, int N, int H, int deep, int app_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
+                            float hw, float discount, void* stream);
+
 /* ---- The PPO arm's update: every epoch and mini-batch of PPOAgent.update (stove_amd/rl/agents.py, the specification), E x M
  * dependent optimiser steps, in ONE launch of one workgroup (csrc/ppo_update.hip, csrc/ppo_update.h).  params: the image above, in/out;
  * m, v: Adam's moments in the image's layout, in/out; step (1,) in/out: the optimiser's step count.  obs (n, 4N) float; actions (n,)

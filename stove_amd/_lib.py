@@ -95,6 +95,7 @@ def _declare(lib):
         'stove_env_search': (I, [P] * 15 + [I] * 8 + [ctypes.c_double] * 4 + [P]),
         'stove_ppo_param_floats': (S, [I, I, I]),
         'stove_ppo_collect': (I, [P] * 14 + [I] * 7 + [ctypes.c_double] * 5 + [P]),
+        'stove_ppo_collect_model': (I, [P] * 18 + [I] * 8 + [F] * 5 + [P]),
         'stove_ppo_update': (I, [P] * 14 + [I] * 7 + [F] * 6 + [I, P]),
         'stove_gnn_param_floats_cl': (S, [I]),
         'stove_gnn_grad_floats_cl': (S, [I]),

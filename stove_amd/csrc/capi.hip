@@ -41,6 +41,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "env.hip"
 #include "env_search.hip"
 #include "ppo_collect.hip"
+#include "ppo_model.hip"
 #include "ppo_update.hip"
 
 namespace stove {
@@ -184,7 +185,8 @@ extern "C" {
 //     stove_env_search -- tree search on those environments themselves, one launch per planning step (env_search.hip);
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in;
 //     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
-//     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip))
+//     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip);
+//     stove_ppo_collect_model -- the model-based PPO arm: a batch of imagined trajectories in one launch (ppo_model.hip))
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1623,6 +1625,31 @@ int stove_ppo_collect(double* x, double* v, const double* r, const double* m, co
   return with_flag(ppo_staged(n), [&](auto staged) {
     return STOVE_LAUNCH_LDS(ppo_collect_k<decltype(staged)::value>, grid, block, lds, (hipStream_t)stream, x, v, r, m, params, u, obs, actions, rewards,
                             values, logp, next_value, returns, status, p, sh, B, S, (float)discount, (int)n);
+  });
+}
+
+// ---------------------------------------------------------------- the model-based PPO arm: imagined trajectories in one launch (ppo_model.hip)
+int stove_ppo_collect_model(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
+                            const float* gnn_params, const float* rh_params, const float* u, float* z_pred, float* pred, float* obs,
+                            int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status, int B,
+                            int S, int N, int H, int deep, int app_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
+                            float hw, float discount, void* stream) {
+  STOVE_VALIDATE(ppo_collect_model(z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, obs, actions, rewards, values, logp,
+                                   next_value, returns, status, B, S, N, H, app_dim, lim_enc));
+  if (B == 0) return 0;
+  (void)pos_var; (void)vel_std; (void)lat_std;          // (the scales of the predicted deviations, which this rollout does not put out)
+  const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
+  const size_t n = ppo_policy::param_floats(sh);
+  if (!small_graph(N))          // one object: gnn_forward's arithmetic, as stove_rollout_fwd steps it
+    return STOVE_LAUNCH_LDS(ppo_collect_model_one_k, dim3(B), dim3(256), kPm1LdsBytes, (hipStream_t)stream, z0, app, policy_params, emb_w, emb_b,
+                            gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards, values, logp, next_value, returns, status, sh, B, S,
+                            app_dim, lim_enc, elu != 0 ? 1 : 0, hw, discount);
+  return with_small_graph<false>(N, elu != 0, false, [&](auto nmx, auto e, auto nt) {
+    constexpr int NMX = decltype(nmx)::value;
+    return STOVE_LAUNCH_LDS((ppo_collect_model_k<NMX, decltype(e)::value, decltype(nt)::value>), dim3(B), dim3(64 * kSmWaves), pm_lds_bytes<NMX>(n),
+                            (hipStream_t)stream, z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards,
+                            values, logp, next_value, returns, status, sh, B, S, N, app_dim, lim_enc, elu, hw, discount, (int)n,
+                            pm_staged<NMX>(n) ? 1 : 0);
   });
 }
 

@@ -54,6 +54,19 @@ PPO_FN float observe(const double* x, const double* v, int k) {
   return (float)(c < 2 ? x[2 * i + c] : v[2 * i + c - 2]);
 }
 
+// The model-based arm's observation (stove_ppo_collect_model; reference runners.py:241-243): entry c of a node's (x, y, vx, vy) from
+// column 2 + c of its model state z, positions from [-1, 1] to [0, hw], velocities scaled alike; every operation rounded on its own
+PPO_FN float observe_model(float z, int c, float hw) {
+  PPO_NO_CONTRACT
+  if (c < 2) {
+    const float shifted = z + 1.0f;
+    const float half = shifted / 2.0f;
+    return half * hw;
+  }
+  const float half = z / 2.0f;
+  return half * hw;
+}
+
 // neuron j of a layer (in -> out): bias, then + w[k] * x[k] for k ascending; relu keeps a NaN
 PPO_FN float neuron(const float* wT, const float* bias, const float* x, int in, int out, int j, bool relu) {
   PPO_NO_CONTRACT

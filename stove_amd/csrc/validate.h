@@ -283,6 +283,25 @@ inline int ppo_collect(const double* x, const double* v, const double* r, const 
   return 0;
 }
 
+// ---- stove_ppo_collect_model: S imagined steps of B trajectories of N objects on the cl = 32 action-conditioned model under a policy of
+// head width H (csrc/ppo_model.hip).  B == 0 is a valid empty call; with S == 0 only obs (B, 1, 4N), next_value and status are written
+// and the (B, S) arrays and z_pred may be NULL.  pred is optional, app is required where app_dim > 0.  The state width 20 + app_dim
+// stays within 32, as for stove_plan_expand; 0 <= lim_enc <= 32.
+inline int ppo_collect_model(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
+                             const float* gnn_params, const float* rh_params, const float* u, const float* z_pred, const float* obs,
+                             const int* actions, const float* rewards, const float* values, const float* logp, const float* next_value,
+                             const float* returns, const int* status, int B, int S, int N, int H, int app_dim, int lim_enc) {
+  if (B < 0 || S < 0 || N < 1 || N > kEnvMaxObjects || H < 1 || H > kPpoMaxHidden || app_dim < 0 || 20 + app_dim > 32 || lim_enc < 0 ||
+      lim_enc > 32)
+    return kStoveInvalidValue;
+  if ((long long)B * ((long long)S + 1) * N * 32 > 0x7fffffffLL) return kStoveInvalidValue;
+  if (B == 0) return 0;          // (arrays without elements have no address)
+  if (null_any(z0, policy_params, emb_w, emb_b, gnn_params, rh_params, obs, next_value) || status == nullptr) return kStoveInvalidValue;
+  if (app_dim > 0 && app == nullptr) return kStoveInvalidValue;
+  if (S > 0 && (null_any(u, z_pred, rewards, values, logp, returns) || actions == nullptr)) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_ppo_update: up to max_steps of E x M optimiser steps on n collected rows (csrc/ppo_update.hip).  E == 0 and max_steps == 0
 // are valid empty calls (one launch that writes status only).  Everything the pointers name is device memory: the indices of perm and
 // the actions are checked by the kernel (status 2), a non-finite loss or norm is found there too (status 3).

@@ -1131,6 +1131,56 @@ def ppo_collect(x, v, r, m, params, u, hidden, deep, granularity, hw, t=1.0, fri
     return out
 
 
+def ppo_collect_model(z0, app, params, emb_w, emb_b, gnn_params, rh_params, u, hidden, deep, lim_enc, elu, consts, hw, discount=0.95,
+                      want_pred=False, out=None):
+    """The model-based PPO arm's collection (stove_ppo_collect_model, csrc/ppo_model.hip; forward only): S = u.shape[1] imagined steps
+    of B trajectories on the action-conditioned cl = 32 model under Policy(base='control') with head width `hidden`, the reward
+    head, next_value and the discounted returns in one launch, nothing synchronised.  z0 (B, N, 18) float32 start states; app
+    (B, N, app_dim) or None; params the float32 image of ppo_param_floats(N, hidden, deep) entries; emb_w (4N, 9), emb_b (4N) the
+    action embedding; gnn_params the cl = 32 image; rh_params the reward head's 2785 floats; u (B, S) float32 uniforms in [0, 1);
+    consts (pos_var, vel_std, lat_std); hw the environment's width, which scales the observations.
+    out: a dict of the tensors to write into (z_pred (B, S, N, 18) [, pred (B, S, N, 32) with want_pred], obs (B, S + 1, 4N), rewards,
+    values, logp, returns (B, S), next_value (B,) float32, actions (B, S), status (B,) int32); None allocates them (zeros).
+    -> that dict; status 3: a value or logit of that trajectory was not finite, nothing of that step or after it was written."""
+    op = 'ppo_collect_model'
+    if not isinstance(z0, torch.Tensor) or z0.dim() != 3 or z0.shape[2] != 18:
+        raise ValueError('ops.%s: z0 must be a (B, N, 18) tensor' % op)
+    z0, app, emb_w, emb_b, gnn_params, rh_params = _plan_model(op, z0, app, emb_w, emb_b, gnn_params, rh_params)
+    B, N, dev = z0.shape[0], z0.shape[1], z0.device
+    H, deep = int(hidden), int(bool(deep))
+    if not 1 <= N <= 6 or not 1 <= H <= 128:
+        raise ValueError('ops.%s: the kernel serves 1 .. 6 objects and head widths 1 .. 128, not N = %d, hidden = %d' % (op, N, H))
+    app_dim = app.shape[-1] if app is not None else 0
+    if 20 + app_dim > 32 or not 0 <= int(lim_enc) <= 32:
+        raise ValueError('ops.%s: the cl = 32 model takes 20 + app_dim <= 32 inputs and lim_enc in 0 .. 32' % op)
+    if tuple(emb_w.shape) != (4 * N, 9):
+        raise ValueError('ops.%s: emb_w is %s, nine actions on %d objects need %s' % (op, tuple(emb_w.shape), N, (4 * N, 9)))
+    if app is not None:
+        _arg(op, 'app', app, _F32, dev, (B, N, app_dim))
+    _arg(op, 'emb_b', emb_b, _F32, dev, (4 * N,), 'model')
+    _arg(op, 'u', u, _F32, dev)
+    if u.dim() != 2 or u.shape[0] != B:
+        raise ValueError('ops.%s: u is %s, the batch needs (%d, S)' % (op, tuple(u.shape), B))
+    S = u.shape[1]
+    lib = _lib.load()
+    _arg(op, 'params', params, _F32, dev, (ppo_param_floats(N, H, deep),), 'policy')
+    _arg(op, 'gnn_params', gnn_params.reshape(-1), _F32, dev, (int(lib.stove_gnn_param_floats()),), 'model')
+    _arg(op, 'rh_params', rh_params.reshape(-1), _F32, dev, (int(lib.stove_reward_head_param_floats()),), 'model')
+    table = {'z_pred': ((B, S, N, 18), _F32), 'pred': ((B, S, N, 32), _F32), 'obs': ((B, S + 1, 4 * N), _F32), 'actions': ((B, S), _I32),
+             'rewards': ((B, S), _F32), 'values': ((B, S), _F32), 'logp': ((B, S), _F32), 'next_value': ((B,), _F32),
+             'returns': ((B, S), _F32), 'status': ((B,), _I32)}          # (in the C call's order)
+    if not (want_pred if out is None else out.get('pred') is not None):
+        del table['pred']
+    _on_gpu(op, 'z0', z0, 'the composed loop of rl.runners.PPORunner.run_pretrained_batch(fused=False)')
+    with torch.cuda.device(dev):
+        out = _outputs(op, out, table, dev, 'batch')
+        outs = [ptr(out.get(k)) for k in ('z_pred', 'pred')] + [ptr(out[k]) for k in list(table)[-8:]]
+        check(lib.stove_ppo_collect_model(ptr(z0), ptr(app), ptr(params), ptr(emb_w), ptr(emb_b), ptr(gnn_params), ptr(rh_params), ptr(u), *outs,
+                                          B, S, N, H, deep, app_dim, int(lim_enc), int(bool(elu)), *[float(c) for c in consts], float(hw),
+                                          float(discount), stream()), 'stove_ppo_collect_model')
+    return out
+
+
 def ppo_update(params, m, v, step, obs, actions, returns, values, logp, adv, perm, num_mini_batch, hidden, deep, clip, value_coef, entropy_coef,
                lr, eps, max_grad_norm, clipped_value_loss=True, max_steps=None, out=None):
     """The PPO arm's update (stove_ppo_update, csrc/ppo_update.hip): the E = perm.shape[0] epochs of num_mini_batch optimiser steps of

@@ -97,6 +97,34 @@ class PolicyForest:
             out[:, s] = run
         return out
 
+    # ------------------------------------------------------------------------------------------------ the model-based arm's policy half
+    @staticmethod
+    def observe_model(z, hw):
+        """(K, N, 18) float32 model states -> (K, 4N) float32: ppo_policy.h's observe_model, positions (z + 1) / 2 * hw, velocities
+        z / 2 * hw, every operation rounded to float32 on its own, hw rounded once (reference runners.py:241-243)"""
+        z = np.asarray(z, dtype=np.float32)
+        hw, one, two = np.float32(hw), np.float32(1), np.float32(2)
+        with np.errstate(invalid='ignore', over='ignore'):
+            pos = (z[:, :, 2:4] + one) / two * hw
+            vel = z[:, :, 4:6] / two * hw
+        obs = np.concatenate([pos, vel], axis=2).reshape(z.shape[0], -1)
+        assert obs.dtype == np.float32
+        return obs
+
+    def decide_model(self, z, hw, u):
+        """One decision per model state: z (K, N, 18) float32, u (K,) float32 uniforms -> (obs (K, 4N), values (K,), actions (K,) int32,
+        logp (K,) float32, margin (K,) float64): the specification of what stove_ppo_collect_model does between two steps of the model."""
+        z = np.asarray(z, dtype=np.float32)
+        if z.ndim != 3 or z.shape[1:] != (self.N, 18):
+            raise ValueError('z is %s, the policy reads (K, %d, 18)' % (z.shape, self.N))
+        u = np.asarray(u)
+        if u.dtype != np.float32 or u.shape != (z.shape[0],):
+            raise ValueError('u must be a float32 vector of %d uniforms' % z.shape[0])
+        obs = self.observe_model(z, hw)
+        heads = self.forward(obs)
+        actions, logp, margin = self.draw(heads[:, 1:], u)
+        return obs, heads[:, 0], actions, logp, margin
+
     # ------------------------------------------------------------------------------------------------ the collection
     def collect(self, batch, u, discount=0.95):
         """S = u.shape[1] steps of the host BatchedAvoidance `batch` (stepped in place) -> dict of obs (B, S + 1, 4N), rewards, values,

@@ -1,7 +1,11 @@
-"""Train the model-free PPO arm (counterpart of the reference's model/rl/main_rl.py): `parse_args` carries the reference's flags,
-`main` serves `--use-states` on the billiards environment under the avoidance task.  `--device-envs` keeps the batch of environments
-on the GPU, where a batch of trajectories is one launch (stove_ppo_collect); without it the collection runs on the host
-(collect.PolicyForest) and only the update uses the device.  The image, gym and pretrained-model variants are not part of this package."""
+"""Train the PPO arms (counterpart of the reference's model/rl/main_rl.py): `parse_args` carries the reference's flags, `main` serves
+`--use-states`, the model-free arm, and `--use-pretrained-model`, the model-based one, on the billiards environment under the
+avoidance task.  `--device-envs` keeps the batch of environments on the GPU, where a batch of trajectories is one launch
+(stove_ppo_collect); without it the collection runs on the host (collect.PolicyForest) and only the update uses the device.
+`--use-pretrained-model` trains on trajectories imagined by the learned dynamics model restored from `--checkpoint DIR`, started
+from the states that model infers on the recorded sequences of `--data PKL` (pretrained.load_and_encode; the reference hard-codes
+both paths); on a GPU a batch of imagined trajectories is one launch (stove_ppo_collect_model).  The real environment only scores
+the policy after each update.  The image, gym and distance-task variants are not part of this package."""
 import argparse
 import json
 import os
@@ -52,6 +56,8 @@ def parse_args(args):
     parser.add_argument('--fused-update', action='store_true', default=False,
                         help='run the PPO update on the GPU in one launch (needs the policy and the batch there)')
     parser.add_argument('--device', default=None, help='device of the policy (default: cuda when there is one)')
+    parser.add_argument('--checkpoint', default=None, help='run directory of the trained dynamics model (--use-pretrained-model)')
+    parser.add_argument('--data', default=None, help='pickle of recorded sequences with actions to start from (--use-pretrained-model)')
     args = parser.parse_args(args)
     assert args.task in ['avoidance', 'maxdist', 'mindist']
     assert not (args.gym and args.use_states)
@@ -67,11 +73,22 @@ def save_args(args, path):
         json.dump(vars(args), fp, sort_keys=True, indent=4)
 
 
+def load_model(checkpoint, data, device):
+    """the trained action-conditioned Stove of run directory `checkpoint`, on `device`, in eval mode"""
+    from ..main import restore_model
+    model = restore_model(checkpoint, extras={'nolog': True, 'traindata': data, 'testdata': data}).to(device)
+    for p in model.parameters():
+        p.requires_grad_(False)
+    return model.eval()
+
+
 def build(args, writer=None):
     """-> (runner, actor_critic) for parsed `args`"""
-    if not args.use_states or args.gym or args.use_pretrained_model or args.task != 'avoidance':
-        raise NotImplementedError('this package trains the avoidance task on states (--use-states); the image, gym, pretrained-model '
-                                  'and distance-task variants are not part of it')
+    if not (args.use_states or args.use_pretrained_model) or args.gym or args.task != 'avoidance':
+        raise NotImplementedError('this package trains the avoidance task on states (--use-states) or on the learned model '
+                                  '(--use-pretrained-model); the image, gym and distance-task variants are not part of it')
+    if args.use_pretrained_model and (args.checkpoint is None or args.data is None):
+        raise ValueError('--use-pretrained-model needs --checkpoint DIR (the trained dynamics model) and --data PKL (its sequences)')
     env = BillardsEnv(n=args.num_balls, r=args.radius, granularity=args.gran, t=args.dt, seed=args.seed)
     task = AvoidanceTask(env, num_stacked=args.num_stacked_frames, action_force=args.action_force, greyscale=False)
     shape = env.get_state_shape()
@@ -103,8 +120,15 @@ def main(args, writer=None):
     save = lambda i: torch.save(actor_critic.state_dict(), os.path.join(model_path, 'model' + str(i) + '.pt'))
     i = 0
     try:
+        if args.use_pretrained_model:
+            from .pretrained import load_and_encode
+            state_model = load_model(args.checkpoint, args.data, runner.device)
+            encoded, apps = load_and_encode(args.data, state_model, runner.device)          # (once per run, not once per batch)
         for i in range(num_batches):
-            runner.run_batch_states()
+            if args.use_pretrained_model:
+                runner.run_pretrained_batch(state_model, encoded, apps)
+            else:
+                runner.run_batch_states()
             if i % args.save_interval == 0:
                 save(i)
     except BaseException:

@@ -168,6 +168,97 @@ class PPORunner(Runner):
         self.batch_counter += 1
         return out
 
+    # ------------------------------------------------------------------------------------------------ the model-based arm
+    def fused_serves_model(self, state_model):
+        """whether stove_ppo_collect_model serves this policy on `state_model`: a device, a policy with a kernel_shape(), a float32
+        cl = 32 action-conditioned model with nine actions on the policy's 1 .. 6 objects"""
+        from ..mcts.mcts_stove import BatchedMCTSHandler
+        c, shape = state_model.c, self.actor_critic.kernel_shape()
+        return (self.device.type == 'cuda' and shape is not None and not BatchedMCTSHandler._fused_unserved(state_model)
+                and bool(c.action_conditioned) and c.action_space == 9 and shape[0] == c.num_obj)
+
+    def collect_model(self, state_model, z0, apps, fused=None, u=None):
+        """S = num_steps imagined steps from the model states z0 (B, N, 18) with appearances apps (B, N, app_dim) or None -> dict of
+        z_pred (B, S, N, 18), obs (B, S + 1, 4N), rewards, values, logp, returns (B, S), next_value (B,) float32, actions (B, S),
+        status (B,) on the runner's device.  u: the (B, S) float32 table of uniforms, drawn from numpy's global stream when None."""
+        B, S = z0.shape[0], self.num_steps
+        if u is None:
+            u = np.random.random_sample((B, S)).astype(np.float32).clip(max=np.float32(1) - np.float32(2) ** -24)
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape != (B, S):
+            raise ValueError('u is %s, the batch needs %s' % (u.shape, (B, S)))
+        serves = self.fused_serves_model(state_model)
+        if fused and not serves:
+            raise ValueError('fused=True needs the policy and a float32 cl = 32 action-conditioned model with nine actions on a GPU, and '
+                             'Policy(base="control") on the model\'s 1 .. 6 objects with a head of width 1 .. 128')
+        ut = torch.from_numpy(u).to(self.device)
+        z0 = z0.to(self.device).float().contiguous()
+        apps = None if apps is None else apps.to(self.device).float().contiguous()
+        if not (fused or (fused is None and serves)):
+            return self._collect_model_composed(state_model, z0, apps, ut)
+        from .. import ops
+        from ..mcts.mcts_stove import BatchedMCTSHandler
+        _, H, deep = self.actor_critic.kernel_shape()
+        dyn = state_model.dyn
+        with torch.no_grad():
+            emb_w, emb_b, gnn, rh = BatchedMCTSHandler._fused_weights(state_model)
+            return ops.ppo_collect_model(z0, apps, self.actor_critic.flat_params(), emb_w, emb_b, gnn, rh, ut, H, deep, 2, dyn.use_elu,
+                                         dyn.loop_consts(), self.env.hw, self.discount)
+
+    def _observe_model(self, z):
+        """model states (B, N, 18) -> the policy's rows (B, 4N): positions and velocities in the environment's units (reference
+        runners.py:241-243)"""
+        phys = z[:, :, 2:6].clone()
+        phys[:, :, :2] = ((phys[:, :, :2] + 1) / 2) * self.env.hw
+        phys[:, :, 2:] = phys[:, :, 2:] / 2 * self.env.hw
+        return phys.reshape(z.shape[0], -1)
+
+    @torch.no_grad()
+    def _collect_model_composed(self, state_model, z0, apps, u):
+        B, S = u.shape
+        n_actions = self.task.get_action_space()
+        storage = BatchStorage(B, S, (4 * z0.shape[1],), self.device)
+        state, states = z0, []
+        storage.obs[:, 0] = self._observe_model(state)
+        for step in range(S):
+            value, action, logp = self.actor_critic.act(storage.obs[:, step], u=u[:, step])
+            one_hot = torch.nn.functional.one_hot(action.long(), n_actions).unsqueeze(1).float()
+            z_pred, r = state_model.rollout(state, 1, actions=one_hot, appearance=apps)
+            state = z_pred[:, 0]
+            states.append(state)
+            storage.insert_batch(step, self._observe_model(state), action.reshape(B, 1), (r[:, 0] - 1).reshape(B, 1), value, 0., logp)
+        next_value = self.actor_critic.get_value(storage.obs[:, -1])
+        returns = self._calculate_returns(next_value, storage.rewards, storage.dones)
+        z_pred = torch.stack(states, 1) if states else z0.new_zeros((B, 0) + tuple(z0.shape[1:]))
+        return {'z_pred': z_pred, 'obs': storage.obs, 'actions': storage.actions[:, :, 0].to(torch.int32), 'rewards': storage.rewards[:, :, 0],
+                'values': storage.values[:, :, 0], 'logp': storage.action_log_probs[:, :, 0], 'next_value': next_value[:, 0],
+                'returns': returns[:, :, 0], 'status': torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def run_pretrained_batch(self, state_model, encoded_states, apps, fused=None, u=None):
+        """One batch of the model-based arm (reference runners.py: run_pretrained_batch): batch_size start states drawn from the encoded
+        ones, num_steps steps imagined on `state_model` under the policy with the reward head's rewards, one PPO update on them, then
+        the policy's mean reward over 16 x 32 steps of the real environment.  fused: None -- one launch (stove_ppo_collect_model)
+        where fused_serves_model holds, else the composed loop; True -- the launch or a ValueError; False -- the loop: per step one
+        batched Policy.act, one Stove.rollout of one step, one insert.  -> the collection (see collect_model) with 'test_reward'."""
+        randints = torch.randint(0, len(encoded_states) - 1, (self.batch_size,)).long()
+        z0 = encoded_states[randints.to(encoded_states.device)].clone()
+        app0 = None if apps is None else apps[randints.to(apps.device)].clone()
+        out = self.collect_model(state_model, z0, app0, fused, u)
+        if bool(out['status'].any()):
+            bad = torch.nonzero(out['status']).reshape(-1).tolist()
+            raise RuntimeError('the policy put out a non-finite value or logit in trajectories %s (status %s)'
+                               % (bad, out['status'][bad].tolist()))
+        three = lambda a: a.unsqueeze(-1)
+        values, returns = three(out['values']), three(out['returns'])
+        adv_targ = (returns - values).detach()
+        losses = self._train_ppo(out['obs'][:, :-1], three(out['actions']).long(), returns, values, three(out['logp']), adv_targ)
+        out['losses'] = losses
+        out['test_reward'] = self._test_actorcritic(16, 32)
+        self._log_to_tb({'/losses/value_loss': losses[0], '/losses/action_loss': losses[1], '/losses/entropy': losses[2],
+                         '/info/test_reward': out['test_reward']})
+        self.batch_counter += 1
+        return out
+
     def _test_actorcritic(self, batch_size, num_steps, fused=None, u=None):
         """the mean reward of a fresh collection, without an update"""
         out, _ = self.collect(batch_size, num_steps, fused, u)

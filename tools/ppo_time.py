@@ -17,7 +17,18 @@ times the update alone, both ways in this one process on the same collected batc
   torch_update_ms   PPOAgent.update as above (the code path of fused=None, unchanged by the fused one)
   fused_update_ms   PPOAgent(fused=True).update: the permutations, their upload, the image, one stove_ppo_update launch, the image
                     written back into the policy, and the one read of the losses and the status
-  fused_launch_ms   ops.ppo_update alone on prepared tensors"""
+  fused_launch_ms   ops.ppo_update alone on prepared tensors
+
+    python tools/ppo_time.py --model [--reps 5] [--model-out profiles/ppo_model.json]
+
+times the model-based arm's collection (PPORunner.collect_model) of 32 x 128 and 256 x 128 imagined steps on an untrained, seeded
+action-conditioned cl = 32 model of three objects with appearances (the arithmetic does not depend on the weights), both ways in this
+one process from the same start states and uniforms (writes profiles/ppo_model.json):
+  composed_ms   the composed loop: per step one batched Policy.act, one Stove.rollout of one step (embedding, rollout and reward-head
+                launches) and one insert -- calls that all predate the one-launch collection, which is what makes it the baseline
+  fused_ms      the one-launch collection (ops.ppo_collect_model), the policy's and the model's images built included
+  fused_launch_ms   ops.ppo_collect_model alone on prepared images
+and per imagined step of a trajectory, fused_launch_ms / 128, as step_us."""
 import argparse
 import json
 import os
@@ -36,6 +47,8 @@ def main():
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_collect.json'))
     ap.add_argument('--update', action='store_true', help='time the update alone: torch against the one-launch update')
     ap.add_argument('--update-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_update.json'))
+    ap.add_argument('--model', action='store_true', help='time the model-based collection: the composed loop against the one launch')
+    ap.add_argument('--model-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_model.json'))
     args = ap.parse_args()
     build.build_library()
     import numpy as np
@@ -61,6 +74,53 @@ def main():
         return statistics.median(times)
 
     result = {'device': torch.cuda.get_device_name(0), 'reps': args.reps, 'policy': {'N': 3, 'H': 64, 'deep': False}, 'batches': {}}
+    if args.model:
+        from stove_amd.mcts.mcts_stove import BatchedMCTSHandler
+        from stove_amd.video_prediction.config import StoveConfig
+        from stove_amd.video_prediction.stove import Stove
+        cfg = StoveConfig()
+        cfg.num_obj, cfg.width, cfg.height, cfg.debug = 3, 32, 32, True
+        cfg.device, cfg.dtype, cfg.random_seed = torch.device(dev), torch.float32, 42
+        cfg.action_conditioned, cfg.action_space, cfg.debug_core_appearance = True, 9, True
+        torch.manual_seed(0)
+        model = Stove(cfg).to(dev)
+        for p in model.parameters():
+            p.requires_grad_(False)
+        result['model'] = {'cl': 32, 'num_obj': 3, 'app_dim': 3, 'action_space': 9}
+        for B, S in ((32, 128), (256, 128)):
+            torch.manual_seed(0)
+            np.random.seed(0)
+            env = envs.BillardsEnv(n=3, granularity=2, seed=0)
+            task = envs.AvoidanceTask(env, action_force=.3)
+            policy = Policy(12, 9, hidden_size=64, base='control')
+            agent = PPOAgent(policy, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40)
+            runner = PPORunner(env, task, None, dev, agent, policy, num_steps=S, batch_size=B, discount=.95)
+            u = np.random.random_sample((B, S)).astype(np.float32)
+            rs = np.random.RandomState(1)
+            z = np.concatenate([np.full((B, 3, 2), 0.1), rs.uniform(-0.7, 0.7, (B, 3, 2)), rs.uniform(-0.1, 0.1, (B, 3, 2)),
+                                rs.uniform(-0.5, 0.5, (B, 3, 12))], axis=2).astype(np.float32)
+            z0 = torch.from_numpy(z).to(dev)
+            apps = torch.from_numpy(rs.uniform(0, 1, (B, 3, 3)).astype(np.float32)).to(dev)
+            assert runner.fused_serves_model(model)
+            row = {'composed_ms': timed(lambda: runner.collect_model(model, z0, apps, fused=False, u=u), args.reps),
+                   'fused_ms': timed(lambda: runner.collect_model(model, z0, apps, fused=True, u=u), args.reps)}
+            with torch.no_grad():
+                emb_w, emb_b, gnn, rh = BatchedMCTSHandler._fused_weights(model)
+            image, ut = policy.flat_params(), torch.from_numpy(u).to(dev)
+            launch = lambda out=None: ops.ppo_collect_model(z0, apps, image, emb_w, emb_b, gnn, rh, ut, 64, False, 2, model.dyn.use_elu,
+                                                            model.dyn.loop_consts(), env.hw, .95, out=out)
+            outs = launch()
+            row['fused_launch_ms'] = timed(lambda: launch(outs), args.reps)
+            row['step_us'] = row['fused_launch_ms'] * 1e3 / S
+            row['fused_status_any'] = bool(outs['status'].any())
+            composed = runner.collect_model(model, z0, apps, fused=False, u=u)
+            row['actions_agree'] = float((composed['actions'] == outs['actions']).float().mean())
+            result['batches']['%dx%d' % (B, S)] = row
+            print('%dx%d' % (B, S), json.dumps(row), flush=True)
+        os.makedirs(os.path.dirname(args.model_out), exist_ok=True)
+        with open(args.model_out, 'w') as fh:
+            json.dump(result, fh, indent=1, sort_keys=True)
+        return
     for B, S in ((32, 128), (256, 128)):
         torch.manual_seed(0)
         np.random.seed(0)

@@ -1,9 +1,11 @@
-"""Train the model-free PPO arm on states (stove_amd/rl/main_rl.py):
+"""Train a PPO arm (stove_amd/rl/main_rl.py), the model-free one on states or the model-based one on the learned dynamics:
 
     python tools/run_ppo.py --use-states --experiment_id run0 [--device-envs] [--fused-update] [--num-env-steps 409600]
+    python tools/run_ppo.py --use-pretrained-model --checkpoint RUN_DIR --data SEQUENCES.pkl --experiment_id run1 [--fused-update]
 
 The reference's `python -m model.rl.main_rl --use-states` with the same flags; `--device-envs` keeps the environments on the GPU, where a
-batch of trajectories is collected in one launch; `--fused-update` runs the PPO update there in one launch too (off by default)."""
+batch of trajectories is collected in one launch; `--fused-update` runs the PPO update there in one launch too (off by default).
+`--use-pretrained-model` imagines the trajectories on the trained action-conditioned model of RUN_DIR, one launch per batch on a GPU."""
 import os
 import sys
 
