@@ -480,6 +480,36 @@ int stove_ppo_collect_model(const float* z0, const float* app, const float* poli
                             int S, int N, int H, int deep, int app_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
                             float hw, float discount, void* stream);
 
+/* ---- The model-free PPO arm on images: `warm` warm-up steps and S steps of B of those environments under the image policy, next_value
+ * and the discounted returns in one launch (csrc/ppo_image.hip, csrc/ppo_image.h; the host forest ImageForest of
+ * stove_amd/rl/collect.py is the specification).  The policy is Policy((32, 32, 3F), 9) of stove_amd/rl/rl_model.py: frame / 255.0f,
+ * Conv2d(3F, 32, 4, stride 2), ReLU, Conv2d(32, 32, 3, stride 2), ReLU, flatten, Linear(1568, H), ReLU [with `deep`: Linear(H, H), ReLU,
+ * Linear(H, H), ReLU], then the value and nine logits; 1 <= F <= 4, 1 <= H <= 512, 1 <= N <= 6; frames are 32 x 32.
+ * params: stove_ppo_image_param_floats(F, H, deep) floats (0 for an F or H outside its range), the layers in that order, each as its
+ * TRANSPOSED weight wT[k * out + j] followed by its bias (out): conv1 (48F -> 32) with k = (c * 4 + ky) * 4 + kx and input channel
+ * c = f * 3 + ch, f counted from the oldest frame of the window; conv2 (288 -> 32) with k = (c * 3 + ky) * 3 + kx; head.main
+ * (1568 -> H) with k = c * 49 + y * 7 + x; the deep layers; the two heads side by side as for stove_ppo_collect
+ * (Policy.flat_image_params() writes it).
+ * frames (B, F + S, 3, 32, 32) float, each row in the layout stove_env_step writes.  Before step 0 the environment takes `warm` >= 1 steps
+ * with action 0 whose rewards are dropped; rows 0 .. F - 1, the first window, are the last min(warm, F) frames rendered after them, zeros
+ * before those.  Step s of environment b reads rows s .. s + F - 1 (the stacked observation is never stored): every convolution output
+ * and neuron is one float32 sum that starts at its bias and adds w[k] * in[k] for k ascending, uncontracted; values[b][s] the value;
+ * the action drawn with u[b][s] and logp as stove_ppo_collect does; then stove_env_step's step, rewards[b][s] = -collisions, and the new
+ * frame, row F + s.  After step S - 1: next_value[b] the value on rows S .. S + F - 1, returns as for stove_ppo_collect.
+ * x, v (B, N, 2) double in/out; r, m (B, N) double; u, rewards, values, logp, returns (B, S) float; actions (B, S) int32; next_value
+ * (B,) float.
+ * status (B,): 0 collected; 3 a value or logit was not finite at some step s: nothing of that step or after it is written (with s == 0
+ * not even the first window), x and v stand as the steps before -- the warm-up included -- left them, the other environments are
+ * unaffected.  One launch on `stream`, one workgroup per environment, no synchronisation (the call can be captured), no atomics.  A NULL
+ * array, B < 0, S < 0, N outside 1 .. 6, F outside 1 .. 4, H outside 1 .. 512, warm < 1, granularity < 1: hipErrorInvalidValue, nothing
+ * launched.  B == 0 is a valid empty call; with S == 0 only the first window (frames (B, F, 3, 32, 32)), next_value and status are written
+ * (the (B, S) arrays may then be NULL). */
+size_t stove_ppo_image_param_floats(int F, int H, int deep);
+int stove_ppo_collect_images(double* x, double* v, const double* r, const double* m, const float* params, const float* u, float* frames,
+                             int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status,
+                             int B, int S, int N, int F, int H, int deep, int warm, int granularity, int drift, int use_colors, double hw,
+                             double t, double friction, double action_force, double discount, void* stream);
+
 /* ---- The PPO arm's update: every epoch and mini-batch of PPOAgent.update (stove_amd/rl/agents.py, the specification), E x M
  * dependent optimiser steps, in ONE launch of one workgroup (csrc/ppo_update.hip, csrc/ppo_update.h).  params: the image above, in/out;
  * m, v: Adam's moments in the image's layout, in/out; step (1,) in/out: the optimiser's step count.  obs (n, 4N) float; actions (n,)

@@ -43,6 +43,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "ppo_collect.hip"
 #include "ppo_model.hip"
 #include "ppo_update.hip"
+#include "ppo_image.hip"
 
 namespace stove {
 
@@ -186,7 +187,8 @@ extern "C" {
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in;
 //     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
 //     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip);
-//     stove_ppo_collect_model -- the model-based PPO arm: a batch of imagined trajectories in one launch (ppo_model.hip))
+//     stove_ppo_collect_model -- the model-based PPO arm: a batch of imagined trajectories in one launch (ppo_model.hip);
+//     stove_ppo_image_param_floats, stove_ppo_collect_images -- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip))
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1651,6 +1653,26 @@ int stove_ppo_collect_model(const float* z0, const float* app, const float* poli
                             values, logp, next_value, returns, status, sh, B, S, N, app_dim, lim_enc, elu, hw, discount, (int)n,
                             pm_staged<NMX>(n) ? 1 : 0);
   });
+}
+
+// ---------------------------------------------------------------- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip)
+static_assert(stove_validate::kImgMaxFrames == ppo_image::kMaxFrames && stove_validate::kImgMaxHidden == ppo_image::kMaxHidden,
+              "validate.h admits what ppo_image.h holds");
+size_t stove_ppo_image_param_floats(int F, int H, int deep) {
+  const ppo_image::Shape sh{F, H, deep != 0 ? 1 : 0};
+  return ppo_image::served(sh) ? ppo_image::param_floats(sh) : 0;
+}
+int stove_ppo_collect_images(double* x, double* v, const double* r, const double* m, const float* params, const float* u, float* frames,
+                             int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status, int B,
+                             int S, int N, int F, int H, int deep, int warm, int granularity, int drift, int use_colors, double hw, double t,
+                             double friction, double action_force, double discount, void* stream) {
+  STOVE_VALIDATE(ppo_collect_images(x, v, r, m, params, u, frames, actions, rewards, values, logp, next_value, returns, status, B, S, N, F, H,
+                                    warm, granularity));
+  if (B == 0) return 0;
+  const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
+  const ppo_image::Shape sh{F, H, deep != 0 ? 1 : 0};
+  return STOVE_LAUNCH_LDS(ppo_collect_images_k, dim3(B), dim3(kImgThreads), img_lds_bytes(F), (hipStream_t)stream, x, v, r, m, params, u, frames,
+                          actions, rewards, values, logp, next_value, returns, status, p, sh, S, warm, use_colors != 0 ? 1 : 0, (float)discount);
 }
 
 // ---------------------------------------------------------------- the PPO arm: the whole update in one launch (ppo_update.hip)

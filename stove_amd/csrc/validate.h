@@ -302,6 +302,23 @@ inline int ppo_collect_model(const float* z0, const float* app, const float* pol
   return 0;
 }
 
+// ---- stove_ppo_collect_images: `warm` warm-up steps and S steps of B environments of N balls under the image policy of F stacked
+// frames and head width H (csrc/ppo_image.hip).  B == 0 is a valid empty call; with S == 0 only the first window frames (B, F, 3, 32, 32),
+// next_value and status are written and the (B, S) arrays may be NULL.
+constexpr int kImgMaxFrames = 4, kImgMaxHidden = 512;
+inline int ppo_collect_images(const double* x, const double* v, const double* r, const double* m, const float* params, const float* u,
+                              const float* frames, const int* actions, const float* rewards, const float* values, const float* logp,
+                              const float* next_value, const float* returns, const int* status, int B, int S, int N, int F, int H, int warm,
+                              int granularity) {
+  if (B < 0 || S < 0 || N < 1 || N > kEnvMaxObjects || F < 1 || F > kImgMaxFrames || H < 1 || H > kImgMaxHidden || warm < 1 || granularity < 1)
+    return kStoveInvalidValue;
+  if ((long long)B * ((long long)S + F) > 0x7fffffffLL) return kStoveInvalidValue;
+  if (B == 0) return 0;          // (arrays without elements have no address)
+  if (null_any(x, v, r, m) || null_any(params, frames, next_value) || status == nullptr) return kStoveInvalidValue;
+  if (S > 0 && (null_any(u, rewards, values, logp, returns) || actions == nullptr)) return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_ppo_update: up to max_steps of E x M optimiser steps on n collected rows (csrc/ppo_update.hip).  E == 0 and max_steps == 0
 // are valid empty calls (one launch that writes status only).  Everything the pointers name is device memory: the indices of perm and
 // the actions are checked by the kernel (status 2), a non-finite loss or norm is found there too (status 3).

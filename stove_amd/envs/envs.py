@@ -207,13 +207,30 @@ class AvoidanceTask:
         self.env = env
         self.env.m[0] = 10000            # the controlled ball is quasi-static
         self.action_force = action_force
+        # the last num_stacked frames side by side along the channel axis, newest last (greyscale: one weighted channel per frame)
+        self.greyscale = bool(greyscale)
+        self.frame_channels = 1 if greyscale else env.get_obs_shape()[2]
+        self.frame_buffer = np.zeros((*env.get_obs_shape()[:2], self.frame_channels * num_stacked))
 
     def get_action_space(self):
         return len(self.action_selection)
 
+    def get_framebuffer_shape(self):
+        return self.frame_buffer.shape
+
     def step(self, action_idx):
         img, state, done = self.env.step(self.action_selection[action_idx] * self.action_force)
         return img, state, -self.env.collisions, done
+
+    def step_frame_buffer(self, action_idx=None):
+        """step(), then the frame buffer shifted by one frame with the new frame last -> (the buffer itself, state, reward, done)"""
+        img, state, reward, done = self.step(action_idx)
+        if self.greyscale:
+            img = np.sum(img * [[[0.3, 0.59, 0.11]]], 2, keepdims=True)
+        c = self.frame_channels
+        self.frame_buffer[:, :, :-c] = self.frame_buffer[:, :, c:]
+        self.frame_buffer[:, :, -c:] = img
+        return self.frame_buffer, state, reward, done
 
 
 class MonteCarloActionPolicy:

@@ -1131,6 +1131,44 @@ def ppo_collect(x, v, r, m, params, u, hidden, deep, granularity, hw, t=1.0, fri
     return out
 
 
+def ppo_image_param_floats(F, H, deep):
+    """length of the parameter image stove_ppo_collect_images reads (Policy.flat_image_params() writes it)"""
+    return int(_lib.load().stove_ppo_image_param_floats(int(F), int(H), int(bool(deep))))
+
+
+def ppo_collect_images(x, v, r, m, params, u, frames_stacked, hidden, deep, warm, granularity, hw, t=1.0, friction=0.0, action_force=0.3,
+                       use_colors=True, drift=False, discount=0.95, out=None):
+    """The PPO arm's collection on images (stove_ppo_collect_images, csrc/ppo_image.hip): `warm` steps with action 0, then S = u.shape[1]
+    steps of B avoidance environments under Policy((32, 32, 3 F), 9) with F = frames_stacked and head width `hidden`, next_value and the
+    discounted returns in one launch, nothing synchronised.  x, v (B, N, 2) float64 device tensors are updated in place; r, m (B, N)
+    float64; params the float32 image of ppo_image_param_floats(F, hidden, deep) entries (Policy.flat_image_params()); u (B, S) float32
+    uniforms in [0, 1), one per draw.
+    out: a dict of the tensors to write into (frames (B, F + S, 3, 32, 32), rewards, values, logp, returns (B, S), next_value (B,)
+    float32, actions (B, S), status (B,) int32); None allocates them (zeros).  -> that dict; the observation of step s is
+    frames[:, s:s + F]; status 3: a value or logit of that environment was not finite, nothing of that step or after it was written."""
+    lib = _lib.load()
+    B, N, dev = _env_state('ppo_collect_images', x, v, r, m, 'rl.collect.ImageForest', 'B')
+    F, H, deep, warm = int(frames_stacked), int(hidden), int(bool(deep)), int(warm)
+    if not 1 <= N <= 6 or not 1 <= F <= 4 or not 1 <= H <= 512:
+        raise ValueError('ops.ppo_collect_images: the kernel serves 1 .. 6 objects, 1 .. 4 stacked frames and head widths 1 .. 512, not '
+                         'N = %d, F = %d, hidden = %d' % (N, F, H))
+    if warm < 1:
+        raise ValueError('ops.ppo_collect_images: the collection starts with at least one warm-up step, not warm = %d' % warm)
+    _arg('ppo_collect_images', 'u', u, _F32, dev)
+    _arg('ppo_collect_images', 'params', params, _F32, dev, (ppo_image_param_floats(F, H, deep),), 'policy')
+    if u.dim() != 2 or u.shape[0] != B:
+        raise ValueError('ops.ppo_collect_images: u is %s, the batch needs (%d, S)' % (tuple(u.shape), B))
+    S = u.shape[1]
+    table = {'frames': ((B, F + S, 3, 32, 32), _F32), 'actions': ((B, S), _I32), 'rewards': ((B, S), _F32), 'values': ((B, S), _F32),
+             'logp': ((B, S), _F32), 'next_value': ((B,), _F32), 'returns': ((B, S), _F32), 'status': ((B,), _I32)}          # (in the C call's order)
+    with torch.cuda.device(dev):
+        out = _outputs('ppo_collect_images', out, table, dev, 'batch')
+        check(lib.stove_ppo_collect_images(ptr(x), ptr(v), ptr(r), ptr(m), ptr(params), ptr(u), *[ptr(out[k]) for k in table], B, S, N, F, H,
+                                           deep, warm, int(granularity), int(bool(drift)), int(bool(use_colors)), float(hw), float(t),
+                                           float(friction), float(action_force), float(discount), stream()), 'stove_ppo_collect_images')
+    return out
+
+
 def ppo_collect_model(z0, app, params, emb_w, emb_b, gnn_params, rh_params, u, hidden, deep, lim_enc, elu, consts, hw, discount=0.95,
                       want_pred=False, out=None):
     """The model-based PPO arm's collection (stove_ppo_collect_model, csrc/ppo_model.hip; forward only): S = u.shape[1] imagined steps

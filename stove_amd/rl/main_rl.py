@@ -5,7 +5,11 @@ avoidance task.  `--device-envs` keeps the batch of environments on the GPU, whe
 `--use-pretrained-model` trains on trajectories imagined by the learned dynamics model restored from `--checkpoint DIR`, started
 from the states that model infers on the recorded sequences of `--data PKL` (pretrained.load_and_encode; the reference hard-codes
 both paths); on a GPU a batch of imagined trajectories is one launch (stove_ppo_collect_model).  The real environment only scores
-the policy after each update.  The image, gym and distance-task variants are not part of this package."""
+the policy after each update.  `--use-images` is the model-free arm on rendered frames, the baseline the learned model is measured
+against: the CNN policy on the task's frame buffer, a batch of trajectories in one launch with `--device-envs`
+(stove_ppo_collect_images), else a composed loop of batched steps; its update is torch autograd.  The reference runs this arm when no
+flag is given; here the flag is required and a bare call raises NotImplementedError.  The gym and distance-task variants are not part
+of this package."""
 import argparse
 import json
 import os
@@ -51,6 +55,8 @@ def parse_args(args):
     parser.add_argument('--num-stacked-frames', type=int, default=4, help='number of frames stacked as inputs')
     parser.add_argument('--use-grid', action='store_true', default=False, help='add grid information to the visual input')
     parser.add_argument('--use-pretrained-model', action='store_true', default=False, help='use the pretrained model as world model')
+    parser.add_argument('--use-images', action='store_true', default=False,
+                        help='the model-free arm on rendered frames (what the reference runs when no flag is given)')
     parser.add_argument('--device-envs', action='store_true', default=False,
                         help='keep the environments on the GPU: a batch of trajectories is one launch')
     parser.add_argument('--fused-update', action='store_true', default=False,
@@ -63,6 +69,7 @@ def parse_args(args):
     assert not (args.gym and args.use_states)
     assert not (args.gym and args.use_pretrained_model)
     assert not (args.use_states and args.use_pretrained_model)
+    assert not (args.use_images and (args.use_states or args.use_pretrained_model or args.gym))
     if not args.gym:
         assert args.env in ['billards']
     return args
@@ -84,15 +91,23 @@ def load_model(checkpoint, data, device):
 
 def build(args, writer=None):
     """-> (runner, actor_critic) for parsed `args`"""
-    if not (args.use_states or args.use_pretrained_model) or args.gym or args.task != 'avoidance':
-        raise NotImplementedError('this package trains the avoidance task on states (--use-states) or on the learned model '
-                                  '(--use-pretrained-model); the image, gym and distance-task variants are not part of it')
+    use_images = getattr(args, 'use_images', False)
+    if not (args.use_states or args.use_pretrained_model or use_images) or args.gym or args.task != 'avoidance':
+        raise NotImplementedError('this package trains the avoidance task on states (--use-states), on the learned model '
+                                  '(--use-pretrained-model) or on rendered frames (--use-images; the reference runs those when no flag '
+                                  'is given, here the flag is required); the gym and distance-task variants are not part of it')
     if args.use_pretrained_model and (args.checkpoint is None or args.data is None):
         raise ValueError('--use-pretrained-model needs --checkpoint DIR (the trained dynamics model) and --data PKL (its sequences)')
+    if use_images and args.fused_update:
+        raise ValueError('--fused-update serves the policy on states; the update of the image policy is torch autograd')
     env = BillardsEnv(n=args.num_balls, r=args.radius, granularity=args.gran, t=args.dt, seed=args.seed)
     task = AvoidanceTask(env, num_stacked=args.num_stacked_frames, action_force=args.action_force, greyscale=False)
-    shape = env.get_state_shape()
-    actor_critic = Policy(shape[0] * shape[1], task.get_action_space(), hidden_size=64, base='control')
+    if use_images:
+        actor_critic = Policy(task.get_framebuffer_shape(), task.get_action_space(), hidden_size=args.hidden_size,
+                              stacked_frames=args.num_stacked_frames, use_grid=args.use_grid, use_deep_layers=args.use_deep_layers)
+    else:
+        shape = env.get_state_shape()
+        actor_critic = Policy(shape[0] * shape[1], task.get_action_space(), hidden_size=64, base='control')
     agent = PPOAgent(actor_critic, args.clip_param, args.num_ppo_epochs, args.num_ppo_mb, args.value_loss_coef, args.entropy_coef, args.lr,
                      args.eps, args.max_grad_norm, fused=True if args.fused_update else None)
     device = args.device or ('cuda' if torch.cuda.is_available() else 'cpu')
@@ -127,6 +142,8 @@ def main(args, writer=None):
         for i in range(num_batches):
             if args.use_pretrained_model:
                 runner.run_pretrained_batch(state_model, encoded, apps)
+            elif args.use_images:
+                runner.run_batch()
             else:
                 runner.run_batch_states()
             if i % args.save_interval == 0:

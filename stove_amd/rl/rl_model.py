@@ -1,8 +1,10 @@
 """The policy networks of the model-free PPO arm (counterpart of the reference's model/rl/rl_model.py): same constructor arguments,
 same act / get_value / evaluate_actions, same state_dict keys, so a reference checkpoint loads.  Plain torch modules: they run on the
 CPU and on a GPU.  `Policy(base='control')` -- SimpleControlBase under DiscreteActionHead -- is the network the one-launch collection
-serves (stove_ppo_collect, csrc/ppo_policy.h): `flat_params()` writes the image that kernel reads.  SimpleCNNBase exists so that image
-checkpoints load; the image variant of the runner is not part of this package."""
+serves (stove_ppo_collect, csrc/ppo_policy.h): `flat_params()` writes the image that kernel reads.  `Policy((32, 32, 3 F), 9)` --
+SimpleCNNBase without use_grid under the same head -- is the network of the arm on images (PPORunner.run_batch); the one-launch
+collection on images serves it for F in 1 .. 4 and head widths up to 512 (stove_ppo_collect_images, csrc/ppo_image.h):
+`flat_image_params()` writes that kernel's image.  With use_grid the composed loop of the runner collects instead."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -141,6 +143,60 @@ class Policy(nn.Module):
         if not 1 <= H <= 128 or h.actor_head.out_features != 9:
             return None
         return n_in // 4, H, bool(h.use_deep_layers)
+
+    def image_kernel_shape(self):
+        """(F, H, deep) when stove_ppo_collect_images serves this policy -- SimpleCNNBase without use_grid on 3 F channels, F in 1 .. 4,
+        a head of width 1 .. 512 on its 1568 features and nine actions --, else None"""
+        b, h = self.base, self.head
+        if not isinstance(b, SimpleCNNBase) or b.use_grid or not isinstance(h, DiscreteActionHead):
+            return None
+        c, H = b.main[0].in_channels, h.main.out_features
+        if c % 3 or not 1 <= c // 3 <= 4 or h.main.in_features != 32 * 7 * 7 or not 1 <= H <= 512 or h.actor_head.out_features != 9:
+            return None
+        return c // 3, H, bool(h.use_deep_layers)
+
+    def _image_layers(self):
+        if self.image_kernel_shape() is None:
+            raise ValueError('the one-launch collection on images serves Policy((32, 32, 3 F), 9) without use_grid, F in 1 .. 4, with a '
+                             'head of width 1 .. 512 and nine actions')
+        b, h = self.base, self.head
+        return [b.main[0], b.main[2], h.main] + ([h.in_between[0], h.in_between[2]] if h.use_deep_layers else [])
+
+    def flat_image_params(self):
+        """the float32 image stove_ppo_collect_images reads (include/stove_hip.h, next to stove_ppo_image_param_floats): base.main.0
+        (48 F -> 32, k = (c * 4 + ky) * 4 + kx), base.main.2 (288 -> 32, k = (c * 3 + ky) * 3 + kx), head.main (1568 -> H) [, the two
+        in_between layers with use_deep_layers], then the two heads side by side -- each as its transposed weight (in, out), row-major,
+        followed by its bias (out)."""
+        h = self.head
+        layers = [(l.weight.reshape(l.weight.shape[0], -1), l.bias) for l in self._image_layers()]
+        layers.append((torch.cat([h.values_head.weight, h.actor_head.weight], 0), torch.cat([h.values_head.bias, h.actor_head.bias], 0)))
+        with torch.no_grad():
+            return torch.cat([p for w, bias in layers for p in (w.t().reshape(-1), bias.reshape(-1))]).float().contiguous()
+
+    def load_flat_image_params(self, image):
+        """the inverse of flat_image_params(): the layers' weights and biases written from the image, in place"""
+        layers, h = self._image_layers(), self.head
+        H = h.main.out_features
+        if not isinstance(image, torch.Tensor) or image.dim() != 1 or \
+                image.numel() != sum(l.weight.numel() + l.bias.numel() for l in layers) + (H + 1) * 10:
+            raise ValueError('load_flat_image_params: the image does not have the length of flat_image_params()')
+        at = 0
+
+        def take(count):
+            nonlocal at
+            at += count
+            return image[at - count:at]
+        with torch.no_grad():
+            for layer in layers:
+                out, k = layer.weight.shape[0], layer.weight[0].numel()
+                layer.weight.copy_(take(out * k).reshape(k, out).t().reshape(layer.weight.shape))
+                layer.bias.copy_(take(out))
+            heads = take(H * 10).reshape(H, 10).t()
+            h.values_head.weight.copy_(heads[:1])
+            h.actor_head.weight.copy_(heads[1:])
+            bias = take(10)
+            h.values_head.bias.copy_(bias[:1])
+            h.actor_head.bias.copy_(bias[1:])
 
     def flat_params(self):
         """the float32 image stove_ppo_collect reads (include/stove_hip.h, next to stove_ppo_param_floats): the layers in order -- base.main.0,

@@ -7,6 +7,11 @@ them (`reset()` plus one step with action 0 on the one environment object, in or
   composed: per step one batched `policy.act` and one `BatchedAvoidance.step(render=False)`, nothing synchronised;
   on the host, `collect.PolicyForest`, the numpy specification of that kernel.
 
+The arm on images (`run_batch`, the reference's default) has the same shape: the start states are drawn with `env.reset()`, the four
+steps with action 0 that fill the frame buffer and the S steps on rendered frames are one ops.ppo_collect_images launch
+(stove_ppo_collect_images) on a device when the policy is one that kernel serves, else a composed loop of batched `policy.act` and
+`BatchedAvoidance.step(render=True)` calls, on the device or on the host; `collect.ImageForest` is that kernel's numpy specification.
+
 All three draw action s of environment b from the same uniform u[b][s] (collect.py says why the reference's stream is not
 reproduced), so they agree action for action wherever no draw sits within rounding of a boundary.  Logging goes to an optional
 `writer` with an `add_scalar(key, value, step)` method (a tensorboardX SummaryWriter fits); none is required."""
@@ -71,9 +76,16 @@ class Runner:
         for key, value in log_dict.items():
             self.summary_writer.add_scalar(key, value, counter)
 
-    def reset(self):
-        """a new configuration and one step with action 0, as the reference starts every trajectory -> (frame, state)"""
+    def reset(self, frame_buffer=False):
+        """a new configuration and one step with action 0, as the reference starts every trajectory -> (frame, state).
+        frame_buffer: the image arm's start -- the task's frame buffer zeroed and filled by four steps with action 0 -> what the last
+        step_frame_buffer returns (buffer, state, reward, done)"""
         self.env.reset()
+        if frame_buffer:
+            self.task.frame_buffer[:] = 0.
+            for _ in range(3):
+                self.task.step_frame_buffer(0)
+            return self.task.step_frame_buffer(0)
         img, state, _, _ = self.task.step(0)
         return img, state
 
@@ -92,11 +104,16 @@ class PPORunner(Runner):
             raise ValueError('device_envs needs the policy on a GPU')
 
     # ------------------------------------------------------------------------------------------------ the collection
-    def start_batch(self, batch_size):
-        """batch_size start states drawn one after the other from the runner's environment -> a host BatchedAvoidance holding them"""
+    def start_batch(self, batch_size, frame_buffer=False):
+        """batch_size start states drawn one after the other from the runner's environment -> a host BatchedAvoidance holding them.
+        frame_buffer: the image arm's start states, drawn with env.reset() only -- the four warm-up steps that fill the frame buffer
+        belong to the collection (collect_images), which steps the whole batch through them together"""
         xs, vs = [], []
         for _ in range(batch_size):
-            self.reset()
+            if frame_buffer:
+                self.env.reset()
+            else:
+                self.reset()
             xs.append(np.array(self.env.x, dtype=np.float64))
             vs.append(np.array(self.env.v, dtype=np.float64))
         batch = BatchedAvoidance.from_tasks([self.task] * batch_size)
@@ -167,6 +184,108 @@ class PPORunner(Runner):
                          '/info/rewards': float(out['rewards'].mean())})
         self.batch_counter += 1
         return out
+
+    # ------------------------------------------------------------------------------------------------ the arm on images
+    WARM = 4          # steps with action 0 that fill the frame buffer before step 0 (the reference's reset(frame_buffer=True))
+
+    def fused_serves_images(self):
+        """whether stove_ppo_collect_images serves this runner: device environments that render 32 x 32 colour frames for a policy
+        with an image_kernel_shape() on the task's number of stacked frames"""
+        shape = self.actor_critic.image_kernel_shape()
+        return (self.env_device.type == 'cuda' and shape is not None and self.env.res == 32 and not self.task.greyscale
+                and self.task.get_framebuffer_shape()[2] == 3 * shape[0])
+
+    def collect_images(self, batch_size, num_steps, fused=None, u=None):
+        """-> (dict of frames (B, F + S, C, res, res) -- C = 3, or 1 with a greyscale task --, rewards, values, logp, returns (B, S),
+        next_value (B,) float32, actions (B, S), status (B,), as tensors on the runner's device; the stepped BatchedAvoidance).  The
+        observation of step s is frames[:, s:s + F], channels frame by frame, oldest first.  u: the (B, S) float32 table of uniforms,
+        drawn from numpy's global stream when None.  fused: None -- one launch (stove_ppo_collect_images) where fused_serves_images
+        holds, else the composed loop; True -- the launch or a ValueError; False -- the loop, on the device or on the host."""
+        if u is None:
+            u = np.random.random_sample((batch_size, num_steps)).astype(np.float32).clip(max=np.float32(1) - np.float32(2) ** -24)
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape != (batch_size, num_steps):
+            raise ValueError('u is %s, the batch needs %s' % (u.shape, (batch_size, num_steps)))
+        serves = self.fused_serves_images()
+        if fused and not serves:
+            raise ValueError('fused=True needs a device batch of 32 x 32 colour frames and a policy stove_ppo_collect_images serves: '
+                             'Policy((32, 32, 3 F), 9) without use_grid, F in 1 .. 4, with a head of width 1 .. 512 and nine actions')
+        batch = self.start_batch(batch_size, frame_buffer=True)
+        ut = torch.from_numpy(u).to(self.device)
+        if self.env_device.type == 'cuda':
+            batch.to(self.device)
+        if fused or (fused is None and serves):
+            from .. import ops
+            F, H, deep = self.actor_critic.image_kernel_shape()
+            out = ops.ppo_collect_images(batch.x, batch.v, batch.r, batch.m, self.actor_critic.flat_image_params(), ut, F, H, deep, self.WARM,
+                                         batch.granularity, batch.hw, batch.t, batch.friction, batch.action_force, batch.use_colors,
+                                         batch.drift, self.discount)
+            return out, batch
+        return self._collect_images_composed(batch, ut), batch
+
+    def _frame_rows(self, frames):
+        """a step's rendered frames (B, 3, res, res), numpy or tensor -> float32 rows (B, C, res, res) on the runner's device"""
+        rows = torch.as_tensor(frames).to(self.device)
+        if self.task.greyscale:
+            weights = torch.tensor([0.3, 0.59, 0.11], dtype=torch.float64, device=self.device).reshape(1, 3, 1, 1)
+            rows = (rows.double() * weights).sum(1, keepdim=True).float()
+        return rows
+
+    @staticmethod
+    def stacked(frames, F):
+        """frames (B, R, C, res, res) -> the R - F + 1 windows (B, R - F + 1, F C, res, res): channel f C + c, oldest frame first"""
+        B, R, C, h, w = frames.shape
+        return frames.unfold(1, F, 1).permute(0, 1, 5, 2, 3, 4).reshape(B, R - F + 1, F * C, h, w)
+
+    @torch.no_grad()
+    def _collect_images_composed(self, batch, u):
+        B, S = u.shape
+        C = self.task.frame_channels
+        F = self.task.get_framebuffer_shape()[2] // C
+        frames = torch.zeros((B, F + S, C, batch.res, batch.res), device=self.device)
+        zero = np.zeros(B, dtype=np.int64)
+        for w in range(self.WARM):
+            img, _ = batch.step(zero, render=F - self.WARM + w >= 0)
+            if img is not None:
+                frames[:, F - self.WARM + w] = self._frame_rows(img)
+        storage = BatchStorage(B, S, (), self.device)
+        window = lambda s: frames[:, s:s + F].reshape(B, F * C, batch.res, batch.res)
+        for step in range(S):
+            value, action, logp = self.actor_critic.act(window(step), u=u[:, step])
+            img, reward = batch.step(action if batch.device is not None else action.cpu().numpy(), render=True)
+            frames[:, F + step] = self._frame_rows(img)
+            storage.rewards[:, step] = torch.as_tensor(reward).to(self.device).reshape(B, 1)
+            storage.actions[:, step], storage.values[:, step], storage.action_log_probs[:, step] = action.reshape(B, 1), value, logp
+        next_value = self.actor_critic.get_value(window(S))
+        returns = self._calculate_returns(next_value, storage.rewards, storage.dones)
+        return {'frames': frames, 'actions': storage.actions[:, :, 0].to(torch.int32), 'rewards': storage.rewards[:, :, 0],
+                'values': storage.values[:, :, 0], 'logp': storage.action_log_probs[:, :, 0], 'next_value': next_value[:, 0],
+                'returns': returns[:, :, 0], 'status': torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def run_batch(self, fused=None, u=None):
+        """One batch of the image arm (reference runners.py: PPORunner.run_batch): collect batch_size trajectories of num_steps on rendered
+        frames, then one PPO update on the stacked observations (B S, F C, res, res) -> the collection (see collect_images) with 'losses'"""
+        out, batch = self.collect_images(self.batch_size, self.num_steps, fused, u)
+        if bool(out['status'].any()):
+            bad = torch.nonzero(out['status']).reshape(-1).tolist()
+            raise RuntimeError('the policy put out a non-finite value or logit in environments %s (status %s)'
+                               % (bad, out['status'][bad].tolist()))
+        self.last_batch = batch
+        F = out['frames'].shape[1] - self.num_steps
+        obs = self.stacked(out['frames'], F)[:, :-1]
+        three = lambda a: a.unsqueeze(-1)
+        values, returns = three(out['values']), three(out['returns'])
+        adv_targ = (returns - values).detach()
+        out['losses'] = self._train_ppo(obs, three(out['actions']).long(), returns, values, three(out['logp']), adv_targ)
+        self._log_to_tb({'/losses/value_loss': out['losses'][0], '/losses/action_loss': out['losses'][1], '/losses/entropy': out['losses'][2],
+                         '/info/rewards': float(out['rewards'].mean())})
+        self.batch_counter += 1
+        return out
+
+    def _test_actorcritic_images(self, batch_size, num_steps, fused=None, u=None):
+        """the mean reward of a fresh collection on images, without an update"""
+        out, _ = self.collect_images(batch_size, num_steps, fused, u)
+        return float(out['rewards'].mean())
 
     # ------------------------------------------------------------------------------------------------ the model-based arm
     def fused_serves_model(self, state_model):

@@ -28,7 +28,17 @@ one process from the same start states and uniforms (writes profiles/ppo_model.j
                 launches) and one insert -- calls that all predate the one-launch collection, which is what makes it the baseline
   fused_ms      the one-launch collection (ops.ppo_collect_model), the policy's and the model's images built included
   fused_launch_ms   ops.ppo_collect_model alone on prepared images
-and per imagined step of a trajectory, fused_launch_ms / 128, as step_us."""
+and per imagined step of a trajectory, fused_launch_ms / 128, as step_us.
+
+    python tools/ppo_time.py --images [--reps 5] [--images-hidden 512] [--images-out profiles/ppo_image.json]
+
+times the arm on images (PPORunner.collect_images) at 32 x 128 and 256 x 128 steps with N = 3, F = 4 stacked frames and head width
+512, both ways in this one process from the same start states and uniforms (writes profiles/ppo_image.json):
+  start_ms          drawing the batch's start states on the host (env.reset() each)
+  fused_launch_ms   ops.ppo_collect_images alone on a prepared image, the four warm-up steps included; step_us: that per step of the 132
+  fused_ms          collect_images(fused=True): the start states, their upload and the image included
+  composed_ms       the composed device loop: per step one batched Policy.act on the window and one stove_env_step with its frame
+  update_ms         for context: PPOAgent.update on the collected batch (4 epochs x 32 mini-batches, torch autograd + Adam), once"""
 import argparse
 import json
 import os
@@ -49,6 +59,9 @@ def main():
     ap.add_argument('--update-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_update.json'))
     ap.add_argument('--model', action='store_true', help='time the model-based collection: the composed loop against the one launch')
     ap.add_argument('--model-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_model.json'))
+    ap.add_argument('--images', action='store_true', help='time the collection on images: the composed loop against the one launch')
+    ap.add_argument('--images-hidden', type=int, default=512, help='head width of the image policy (main_rl\'s default 512)')
+    ap.add_argument('--images-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_image.json'))
     args = ap.parse_args()
     build.build_library()
     import numpy as np
@@ -119,6 +132,57 @@ def main():
             print('%dx%d' % (B, S), json.dumps(row), flush=True)
         os.makedirs(os.path.dirname(args.model_out), exist_ok=True)
         with open(args.model_out, 'w') as fh:
+            json.dump(result, fh, indent=1, sort_keys=True)
+        return
+    if args.images:
+        result['policy'] = {'F': 4, 'H': args.images_hidden, 'deep': False}
+        for B, S in ((32, 128), (256, 128)):
+            torch.manual_seed(0)
+            np.random.seed(0)
+            env = envs.BillardsEnv(n=3, granularity=2, seed=0)
+            task = envs.AvoidanceTask(env, num_stacked=4, action_force=.3)
+            policy = Policy(task.get_framebuffer_shape(), 9, hidden_size=args.images_hidden, stacked_frames=4)
+            agent = PPOAgent(policy, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40)
+            runner = PPORunner(env, task, None, dev, agent, policy, num_steps=S, batch_size=B, discount=.95)
+            assert runner.fused_serves_images()
+            u = np.random.random_sample((B, S)).astype(np.float32)
+            ut = torch.from_numpy(u).to(dev)
+            row = {'start_ms': timed(lambda: runner.start_batch(B, frame_buffer=True), args.reps)}
+            start = runner.start_batch(B, frame_buffer=True).to(dev)
+            x0, v0 = start.x.clone(), start.v.clone()
+            image = policy.flat_image_params()
+
+            def rewind():
+                start.x.copy_(x0)
+                start.v.copy_(v0)
+
+            def launch(out=None):
+                rewind()
+                return ops.ppo_collect_images(start.x, start.v, start.r, start.m, image, ut, 4, args.images_hidden, False, runner.WARM,
+                                              start.granularity, start.hw, start.t, start.friction, start.action_force, start.use_colors,
+                                              start.drift, .95, out=out)
+
+            def composed():
+                rewind()
+                return runner._collect_images_composed(start, ut)
+
+            outs = launch()
+            row['fused_launch_ms'] = timed(lambda: launch(outs), args.reps)
+            row['step_us'] = row['fused_launch_ms'] * 1e3 / (S + runner.WARM)
+            row['fused_ms'] = timed(lambda: runner.collect_images(B, S, fused=True, u=u), args.reps)
+            row['composed_ms'] = timed(composed, args.reps)
+            row['fused_status_any'] = bool(outs['status'].any())
+            row['actions_agree'] = float((composed()['actions'] == launch()['actions']).float().mean())
+            out = launch()
+            three = lambda a: a.unsqueeze(-1)
+            flat = lambda a: a.reshape((-1, *a.size()[2:]))
+            batch = [flat(runner.stacked(out['frames'], 4)[:, :-1]), flat(three(out['actions']).long()), flat(three(out['returns'])),
+                     flat(three(out['values'])), flat(three(out['logp'])), flat(three(out['returns'] - out['values']))]
+            row['update_ms'] = timed(lambda: agent.update(*batch), 1)
+            result['batches']['%dx%d' % (B, S)] = row
+            print('%dx%d' % (B, S), json.dumps(row), flush=True)
+        os.makedirs(os.path.dirname(args.images_out), exist_ok=True)
+        with open(args.images_out, 'w') as fh:
             json.dump(result, fh, indent=1, sort_keys=True)
         return
     for B, S in ((32, 128), (256, 128)):
