@@ -533,6 +533,29 @@ int stove_ppo_update(float* params, float* m, float* v, int* step, const float* 
                      int n, int E, int M, int max_steps, int N, int H, int deep, float clip, float value_coef, float entropy_coef, float lr,
                      float eps, float max_grad_norm, int clipped_value_loss, void* stream);
 
+/* ---- The update of the PPO arm on images: every epoch and mini-batch of PPOAgent.update for the image policy above, E x M dependent
+ * optimiser steps, as one call that enqueues a fixed chain of launches per step on `stream` (csrc/ppo_image_update.hip): nothing is
+ * synchronised or allocated inside, so the call can be captured as a linear chain.  params, m, v: stove_ppo_image_param_floats(F, H, deep)
+ * floats in the layout of stove_ppo_collect_images, in/out; step (1,) in/out.  Row r of the n rows has its observation, the window of
+ * 3072 F floats (3F, 32, 32) with pixels in the frames' scale (the division by 255 happens on the way in), at
+ * obs + (r / S) env_stride + (r % S) 3072 floats: frames (B, F + S, 3, 32, 32) as stove_ppo_collect_images wrote them with
+ * env_stride = (F + S) 3072 and n = B S, or a dense (n, 3F, 32, 32) tensor with S = 1, env_stride = 3072 F.  actions (n,) int32; returns,
+ * values, logp, adv (n,) float; perm (E, n) int32.  Steps, mini-batches, losses, the gradient as autograd gives it, the norm, the clip
+ * factor and Adam are those of stove_ppo_update; losses (E M, 3), gnorm (E M,), max_steps and status (2,) mean what they mean there
+ * (status 2: an index or action out of range; 3: a loss or norm not finite; that step and all after it change nothing; [1] the steps
+ * completed).  The three wide products of each layer run on the float32 matrix instructions; every sum has a fixed order (no atomics),
+ * so equal inputs give equal bits.  grad: NULL, or stove_ppo_image_param_floats floats that receive the unclipped gradient image of the
+ * last step completed, in the parameters' layout.  ws: stove_ppo_update_images_ws_bytes(n, M, F, H, deep) bytes of device memory, 16-byte
+ * aligned (0 for a shape that is not served).  A NULL array, n < M, M < 1, S < 1, E < 0, max_steps outside 0 .. E M, F outside 1 .. 4,
+ * H outside 1 .. 512: hipErrorInvalidValue, nothing launched.  E M == 0 and max_steps == 0 are valid empty calls: one launch that writes
+ * status; the other arrays and ws may then be NULL. */
+size_t stove_ppo_update_images_ws_bytes(int n, int M, int F, int H, int deep);
+int stove_ppo_update_images(float* params, float* m, float* v, int* step, const float* obs, const int* actions, const float* returns,
+                            const float* values, const float* logp, const float* adv, const int* perm, float* losses, float* gnorm,
+                            float* grad, int* status, void* ws, int n, int S, int env_stride, int E, int M, int max_steps, int F, int H,
+                            int deep, float clip, float value_coef, float entropy_coef, float lr, float eps, float max_grad_norm,
+                            int clipped_value_loss, void* stream);
+
 /* ---- The GNN step, the inference recursion and the rollout at state-code lengths other than 32 (csrc/gnn_cl.hip): cl = 16 or 64,
  * 1 <= N <= 6, cl/2 <= sin_dim <= cl.  Same conventions as their cl = 32 siblings above with every width derived from cl:
  * params is the image [W | W^T | vectors] of stove_gnn_param_floats_cl(cl) floats (no packed sections), result / pred (B,N,cl),

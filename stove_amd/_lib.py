@@ -99,6 +99,8 @@ def _declare(lib):
         'stove_ppo_image_param_floats': (S, [I, I, I]),
         'stove_ppo_collect_images': (I, [P] * 14 + [I] * 10 + [ctypes.c_double] * 5 + [P]),
         'stove_ppo_update': (I, [P] * 14 + [I] * 7 + [F] * 6 + [I, P]),
+        'stove_ppo_update_images_ws_bytes': (S, [I] * 5),
+        'stove_ppo_update_images': (I, [P] * 16 + [I] * 9 + [F] * 6 + [I, P]),
         'stove_gnn_param_floats_cl': (S, [I]),
         'stove_gnn_grad_floats_cl': (S, [I]),
         'stove_gnn_bwd_ws_bytes_cl': (S, [I, I, I]),

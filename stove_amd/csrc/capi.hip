@@ -44,6 +44,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "ppo_model.hip"
 #include "ppo_update.hip"
 #include "ppo_image.hip"
+#include "ppo_image_update.hip"
 
 namespace stove {
 
@@ -188,7 +189,8 @@ extern "C" {
 //     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
 //     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip);
 //     stove_ppo_collect_model -- the model-based PPO arm: a batch of imagined trajectories in one launch (ppo_model.hip);
-//     stove_ppo_image_param_floats, stove_ppo_collect_images -- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip))
+//     stove_ppo_image_param_floats, stove_ppo_collect_images -- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip);
+//     stove_ppo_update_images_ws_bytes, stove_ppo_update_images -- its update, every epoch and mini-batch in one call (ppo_image_update.hip))
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1692,6 +1694,25 @@ int stove_ppo_update(float* params, float* m, float* v, int* step, const float* 
                               returns, values, logp, adv, perm, losses, gnorm, status, sh, hy, n, M, max_steps);
     });
   });
+}
+
+// ---------------------------------------------------------------- the PPO arm on images: the whole update in one call (ppo_image_update.hip)
+size_t stove_ppo_update_images_ws_bytes(int n, int M, int F, int H, int deep) {
+  const ppo_image::Shape sh{F, H, deep != 0 ? 1 : 0};
+  if (!ppo_image::served(sh) || M < 1 || n < M) return 0;
+  return piu_ws(n / M, sh).bytes;
+}
+int stove_ppo_update_images(float* params, float* m, float* v, int* step, const float* obs, const int* actions, const float* returns,
+                            const float* values, const float* logp, const float* adv, const int* perm, float* losses, float* gnorm, float* grad,
+                            int* status, void* ws, int n, int S, int env_stride, int E, int M, int max_steps, int F, int H, int deep, float clip,
+                            float value_coef, float entropy_coef, float lr, float eps, float max_grad_norm, int clipped_value_loss,
+                            void* stream) {
+  STOVE_VALIDATE(ppo_update_images(params, m, v, step, obs, actions, returns, values, logp, adv, perm, losses, gnorm, status, ws, n, S, env_stride,
+                                   E, M, max_steps, F, H));
+  const ppo_image::Shape sh{F, H, deep != 0 ? 1 : 0};
+  const ppo_update::Hyper hy{clip, value_coef, entropy_coef, lr, eps, max_grad_norm, clipped_value_loss != 0 ? 1 : 0};
+  return piu_run(params, m, v, step, obs, actions, returns, values, logp, adv, perm, losses, gnorm, grad, status, ws, n, S, env_stride, M,
+                 max_steps, sh, hy, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- stream ordering / graph replay helpers

@@ -331,6 +331,24 @@ inline int ppo_update(const float* params, const float* m, const float* v, const
   return 0;
 }
 
+// ---- stove_ppo_update_images: up to max_steps of E x M optimiser steps of the image policy on n rows whose observations are windows
+// of 3072 F floats at obs + (r / S) env_stride + (r % S) 3072 (csrc/ppo_image_update.hip).  E M == 0 and max_steps == 0 are valid empty
+// calls (status alone is written; every other array and ws may then be NULL).  grad may be NULL.  Indices, actions and non-finite
+// losses are the kernels' to find (status 2, 3).
+inline int ppo_update_images(const float* params, const float* m, const float* v, const int* step, const float* obs, const int* actions,
+                             const float* returns, const float* values, const float* logp, const float* adv, const int* perm,
+                             const float* losses, const float* gnorm, const int* status, const void* ws, int n, int S, int env_stride, int E,
+                             int M, int max_steps, int F, int H) {
+  if (F < 1 || F > kImgMaxFrames || H < 1 || H > kImgMaxHidden || M < 1 || n < M || S < 1 || E < 0 || max_steps < 0 || env_stride < 0)
+    return kStoveInvalidValue;
+  if ((long long)max_steps > (long long)E * M || (long long)E * n > 0x7fffffffLL || (long long)n * 225 > 0x7fffffffLL) return kStoveInvalidValue;
+  if (status == nullptr) return kStoveInvalidValue;
+  if (max_steps == 0) return 0;
+  if (null_any(params, m, v, obs, returns, values, logp, adv, losses, gnorm) || null_any(step, actions, perm) || ws == nullptr)
+    return kStoveInvalidValue;
+  return 0;
+}
+
 // ---- stove_gemm_bf16: C (M x N) = A (M x K) B^T (N x K) [+ bias + add]; leading dimensions cover their rows, B float4-addressable
 inline int gemm(const float* A, const float* B, const float* C, int M, int N, int K, int lda, int ldb, int ldc, int a_kmajor, int b_kmajor,
                 int nsplit, int splitk, const float* ws) {

@@ -1270,6 +1270,73 @@ def ppo_update(params, m, v, step, obs, actions, returns, values, logp, adv, per
     return out
 
 
+_PPO_IMAGE_WS = {}          # (device, n, M, F, H, deep) -> the workspace of ppo_update_images
+
+
+def ppo_update_images(params, m, v, step, obs, actions, returns, values, logp, adv, perm, num_mini_batch, frames_stacked, hidden, deep, clip,
+                      value_coef, entropy_coef, lr, eps, max_grad_norm, clipped_value_loss=True, max_steps=None, steps_per_env=None, out=None,
+                      want_grad=False):
+    """The update of the PPO arm on images (stove_ppo_update_images, csrc/ppo_image_update.hip): the E = perm.shape[0] epochs of
+    num_mini_batch optimiser steps of PPOAgent.update for Policy((32, 32, 3 F), 9), F = frames_stacked, on n rows, enqueued as one
+    chain of launches, nothing synchronised.  params (the float32 image, Policy.flat_image_params()), m, v (Adam's moments, same
+    layout) and step (1,) int32 are updated in place.  obs: with steps_per_env None a dense (n, 3F, 32, 32) float32 tensor; with
+    steps_per_env = S the frames (B, F + S, 3, 32, 32) of ops.ppo_collect_images, row b S + s being the window frames[b, s:s + F]
+    (n = B S; nothing is copied).  returns, values, logp, adv (n,) float32; actions (n,) int32; perm (E, n) int32.  max_steps: stop
+    after that many steps (None: all).  out: a dict of the tensors to write into (losses (E * M, 3), gnorm (E * M,) float32, status
+    (2,) int32 [, grad like params with want_grad: the unclipped gradient image of the last step completed]); None allocates them
+    (zeros).  -> that dict; status as for ppo_update.  The workspace is kept per shape."""
+    lib = _lib.load()
+    op, host = 'ppo_update_images', 'rl.agents.PPOAgent without fused_images'
+    floats = {'params': params, 'm': m, 'v': v, 'obs': obs, 'returns': returns, 'values': values, 'logp': logp, 'adv': adv}
+    for name, ten in floats.items():
+        _on_gpu(op, name, ten, host)
+    dev = params.device
+    _arg(op, 'obs', obs, _F32, dev)
+    F, H, deep, M = int(frames_stacked), int(hidden), int(bool(deep)), int(num_mini_batch)
+    if not 1 <= F <= 4 or not 1 <= H <= 512:
+        raise ValueError('ops.ppo_update_images: the kernels serve 1 .. 4 stacked frames and head widths 1 .. 512, not F = %d, hidden = %d' % (F, H))
+    if steps_per_env is None:
+        if obs.dim() != 4 or tuple(obs.shape[1:]) != (3 * F, 32, 32):
+            raise ValueError('ops.ppo_update_images: obs is %s, F = %d stacked frames need (n, %d, 32, 32)' % (tuple(obs.shape), F, 3 * F))
+        n, S, env_stride = obs.shape[0], 1, 3072 * F
+    else:
+        S = int(steps_per_env)
+        if S < 1 or obs.dim() != 5 or tuple(obs.shape[1:]) != (F + S, 3, 32, 32):
+            raise ValueError('ops.ppo_update_images: obs is %s, frames of S = %d steps and F = %d need (B, %d, 3, 32, 32)'
+                             % (tuple(obs.shape), S, F, F + S))
+        n, env_stride = obs.shape[0] * S, 3072 * (F + S)
+    if M < 1 or n < M:
+        raise ValueError('ops.ppo_update_images: %d rows do not make %d mini-batches' % (n, M))
+    count = ppo_image_param_floats(F, H, deep)
+    for name in ('params', 'm', 'v'):
+        _arg(op, name, floats[name], _F32, dev, (count,), 'policy')
+    for name in ('returns', 'values', 'logp', 'adv'):
+        _arg(op, name, floats[name], _F32, dev, (n,))
+    _arg(op, 'actions', actions, _I32, dev, (n,))
+    _arg(op, 'step', step, _I32, dev)
+    _arg(op, 'perm', perm, _I32, dev)
+    if tuple(step.shape) != (1,) or perm.dim() != 2 or perm.shape[1] != n:
+        raise ValueError('ops.ppo_update_images: step must be (1,) and perm (E, %d)' % n)
+    E = perm.shape[0]
+    max_steps = E * M if max_steps is None else int(max_steps)
+    if not 0 <= max_steps <= E * M:
+        raise ValueError('ops.ppo_update_images: max_steps = %d is outside 0 .. %d' % (max_steps, E * M))
+    table = {'losses': ((E * M, 3), _F32), 'gnorm': ((E * M,), _F32), 'status': ((2,), _I32)}
+    if want_grad if out is None else out.get('grad') is not None:
+        table['grad'] = ((count,), _F32)
+    with torch.cuda.device(dev):
+        out = _outputs(op, out, table, dev, 'update')
+        key = (dev, n, M, F, H, deep)
+        if key not in _PPO_IMAGE_WS:
+            _PPO_IMAGE_WS[key] = _ws(lib.stove_ppo_update_images_ws_bytes(n, M, F, H, deep), dev)
+        check(lib.stove_ppo_update_images(ptr(params), ptr(m), ptr(v), ptr(step), ptr(obs), ptr(actions), ptr(returns), ptr(values), ptr(logp),
+                                          ptr(adv), ptr(perm), ptr(out['losses']), ptr(out['gnorm']), ptr(out.get('grad')), ptr(out['status']),
+                                          ptr(_PPO_IMAGE_WS[key]), n, S, env_stride, E, M, max_steps, F, H, deep, float(clip), float(value_coef),
+                                          float(entropy_coef), float(lr), float(eps), float(max_grad_norm), int(bool(clipped_value_loss)),
+                                          stream()), 'stove_ppo_update_images')
+    return out
+
+
 MATCH_MODES = {'3_only': 0, 'greedy': 1, 'volatile': 2, '3_only_serial': 3}
 
 

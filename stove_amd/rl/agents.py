@@ -1,7 +1,9 @@
 """Proximal policy optimisation on a collected batch (counterpart of the reference's model/rl/agents.py): the same arithmetic in torch
 autograd with torch.optim.Adam -- ppo_epoch passes over num_mini_batch slices of a fresh torch.randperm each.  With fused=True the
 same update is one launch on the device (ops.ppo_update, csrc/ppo_update.hip): the permutations are drawn exactly where the torch path
-draws them, so a torch seed selects the same mini-batches on both paths."""
+draws them, so a torch seed selects the same mini-batches on both paths.  With fused_images=True the update of the image policy
+runs on the device as well (ops.ppo_update_images, csrc/ppo_image_update.hip), on a dense observation tensor (`update`) or straight on
+the frames the collection wrote (`update_windows`)."""
 import torch
 import torch.nn as nn
 import torch.optim as optim
@@ -17,7 +19,7 @@ class Agent:
 
 class PPOAgent(Agent):
     def __init__(self, actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=None, eps=None,
-                 max_grad_norm=None, use_clipped_value_loss=True, fused=None):
+                 max_grad_norm=None, use_clipped_value_loss=True, fused=None, fused_images=None):
         super().__init__(actor_critic)
         self.actor_critic = actor_critic
         self.clip_param = clip_param
@@ -33,7 +35,15 @@ class PPOAgent(Agent):
             shape = getattr(actor_critic, 'kernel_shape', lambda: None)()
             if shape is None:
                 raise ValueError('PPOAgent: fused=True needs a policy stove_ppo_update serves: Policy(base="control") on 1 .. 6 objects with '
-                                 'a head of width 1 .. 128 and nine actions')
+                                 'a head of width 1 .. 128 and nine actions (the image policy takes fused_images=True)')
+        self.fused_images = bool(fused_images)
+        if self.fused_images:
+            if self.fused:
+                raise ValueError('PPOAgent: fused=True and fused_images=True name two different policies')
+            if getattr(actor_critic, 'image_kernel_shape', lambda: None)() is None:
+                raise ValueError('PPOAgent: fused_images=True needs a policy stove_ppo_update_images serves: Policy((32, 32, 3 F), 9) '
+                                 'without use_grid, F in 1 .. 4, with a head of width 1 .. 512 and nine actions')
+        if self.fused or self.fused_images:
             self.lr, self.eps = lr, eps
             self._moments = None          # (m, v, step) as flat device tensors, made at the first update where the policy then lives
 
@@ -42,6 +52,8 @@ class PPOAgent(Agent):
         (The advantages handed in are used as they are: the normalised ones the reference computes first are never read there either.)"""
         if self.fused:
             return self._update_fused(obs, actions, returns, values, action_log_probs, adv_targ)
+        if self.fused_images:
+            return self._update_fused_images('update', obs, None, actions, returns, values, action_log_probs, adv_targ)
         value_loss_epoch = action_loss_epoch = dist_entropy_epoch = 0.
         n = obs.size(0)
         mb = int(n / self.num_mini_batch)
@@ -99,6 +111,60 @@ class PPOAgent(Agent):
                              flat(action_log_probs), flat(adv_targ), perm.to(device=dev, dtype=torch.int32), self.num_mini_batch, H, deep,
                              self.clip_param, self.value_loss_coef, self.entropy_coef, self.lr, self.eps, self.max_grad_norm, True)
         self.actor_critic.load_flat_params(image)
+        steps = self.ppo_epoch * self.num_mini_batch
+        if steps == 0:
+            return 0., 0., 0.
+        host = torch.cat([out['losses'].sum(0).double(), out['status'].double()]).cpu()          # (the one synchronisation)
+        if int(host[3]) != 0:
+            raise RuntimeError('PPOAgent.update: optimiser step %d of %d stopped the fused update with status %d (3: a loss or the '
+                               'gradient norm was not finite; 2: an index out of range); the policy stands as the step before left it'
+                               % (int(host[4]), steps, int(host[3])))
+        return float(host[0]) / steps, float(host[1]) / steps, float(host[2]) / steps
+
+    def update_windows(self, frames, S, actions, returns, values, action_log_probs, adv_targ):
+        """the update of a fused_images agent straight on the collection's frames (B, F + S, 3, 32, 32): row b S + s of the n = B S rows
+        is the window frames[b, s:s + F], which is never copied -> as update"""
+        if not self.fused_images:
+            raise ValueError('PPOAgent.update_windows: the agent was not built with fused_images=True')
+        return self._update_fused_images('update_windows', frames, int(S), actions, returns, values, action_log_probs, adv_targ)
+
+    def _update_fused_images(self, who, obs, S, actions, returns, values, action_log_probs, adv_targ):
+        """S None: obs dense (n, 3F, 32, 32); else obs the frames (B, F + S, 3, 32, 32)"""
+        from .. import ops
+        F, H, deep = self.actor_critic.image_kernel_shape()
+        for name, ten in (('obs' if S is None else 'frames', obs), ('actions', actions), ('returns', returns), ('values', values),
+                          ('action_log_probs', action_log_probs), ('adv_targ', adv_targ)):
+            if not isinstance(ten, torch.Tensor) or not ten.is_cuda:
+                raise RuntimeError('PPOAgent.%s: fused_images=True needs %s as a tensor on the GPU (fused_images=None updates on the host)'
+                                   % (who, name))
+        if S is None:
+            if obs.dim() != 4 or tuple(obs.shape[1:]) != (3 * F, 32, 32):
+                raise ValueError('PPOAgent.update: fused_images=True takes obs (n, %d, 32, 32)' % (3 * F))
+            n = obs.size(0)
+        else:
+            if S < 1 or obs.dim() != 5 or tuple(obs.shape[1:]) != (F + S, 3, 32, 32):
+                raise ValueError('PPOAgent.update_windows: frames of S = %d steps must be (B, %d, 3, 32, 32)' % (S, F + S))
+            n = obs.size(0) * S
+        if any(t.numel() != n for t in (actions, returns, values, action_log_probs, adv_targ)):
+            raise ValueError('PPOAgent.%s: %d rows need as many actions, returns, values, log-probabilities and advantages' % (who, n))
+        if any(t.is_floating_point() and t.dtype != torch.float32 for t in (obs, returns, values, action_log_probs, adv_targ)):
+            raise ValueError('PPOAgent.%s: fused_images=True takes float32 tensors' % who)
+        if n < self.num_mini_batch:
+            raise ValueError('PPOAgent.%s: %d rows do not make %d mini-batches' % (who, n, self.num_mini_batch))
+        dev = obs.device
+        perm = torch.stack([torch.randperm(n) for _ in range(self.ppo_epoch)]) if self.ppo_epoch else torch.zeros((0, n), dtype=torch.int64)
+        image = self.actor_critic.flat_image_params()
+        if image.device != dev:
+            raise ValueError('PPOAgent.%s: the policy lives on %s, the batch on %s' % (who, image.device, dev))
+        if self._moments is None or self._moments[0].device != dev:
+            self._moments = (torch.zeros_like(image), torch.zeros_like(image), torch.zeros(1, dtype=torch.int32, device=dev))
+        m, v, step = self._moments
+        flat = lambda t: t.detach().reshape(n).contiguous()
+        out = ops.ppo_update_images(image, m, v, step, obs.detach().contiguous(), flat(actions).to(torch.int32), flat(returns), flat(values),
+                                    flat(action_log_probs), flat(adv_targ), perm.to(device=dev, dtype=torch.int32), self.num_mini_batch, F, H,
+                                    deep, self.clip_param, self.value_loss_coef, self.entropy_coef, self.lr, self.eps, self.max_grad_norm, True,
+                                    steps_per_env=S)
+        self.actor_critic.load_flat_image_params(image)
         steps = self.ppo_epoch * self.num_mini_batch
         if steps == 0:
             return 0., 0., 0.

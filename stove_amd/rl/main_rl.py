@@ -7,7 +7,8 @@ from the states that model infers on the recorded sequences of `--data PKL` (pre
 both paths); on a GPU a batch of imagined trajectories is one launch (stove_ppo_collect_model).  The real environment only scores
 the policy after each update.  `--use-images` is the model-free arm on rendered frames, the baseline the learned model is measured
 against: the CNN policy on the task's frame buffer, a batch of trajectories in one launch with `--device-envs`
-(stove_ppo_collect_images), else a composed loop of batched steps; its update is torch autograd.  The reference runs this arm when no
+(stove_ppo_collect_images), else a composed loop of batched steps; its update is torch autograd, or with `--fused-update` one chain
+of launches on the frames the collection wrote (stove_ppo_update_images).  The reference runs this arm when no
 flag is given; here the flag is required and a bare call raises NotImplementedError.  The gym and distance-task variants are not part
 of this package."""
 import argparse
@@ -60,7 +61,7 @@ def parse_args(args):
     parser.add_argument('--device-envs', action='store_true', default=False,
                         help='keep the environments on the GPU: a batch of trajectories is one launch')
     parser.add_argument('--fused-update', action='store_true', default=False,
-                        help='run the PPO update on the GPU in one launch (needs the policy and the batch there)')
+                        help='run the PPO update on the GPU without host round trips (needs the policy and the batch there)')
     parser.add_argument('--device', default=None, help='device of the policy (default: cuda when there is one)')
     parser.add_argument('--checkpoint', default=None, help='run directory of the trained dynamics model (--use-pretrained-model)')
     parser.add_argument('--data', default=None, help='pickle of recorded sequences with actions to start from (--use-pretrained-model)')
@@ -98,9 +99,13 @@ def build(args, writer=None):
                                   'is given, here the flag is required); the gym and distance-task variants are not part of it')
     if args.use_pretrained_model and (args.checkpoint is None or args.data is None):
         raise ValueError('--use-pretrained-model needs --checkpoint DIR (the trained dynamics model) and --data PKL (its sequences)')
-    if use_images and args.fused_update:
-        raise ValueError('--fused-update serves the policy on states; the update of the image policy is torch autograd')
-    env = BillardsEnv(n=args.num_balls, r=args.radius, granularity=args.gran, t=args.dt, seed=args.seed)
+    device = args.device or ('cuda' if torch.cuda.is_available() else 'cpu')
+    if args.fused_update and torch.device(device).type != 'cuda':
+        raise ValueError('--fused-update needs a GPU')
+    if use_images and args.fused_update and (args.use_grid or not 1 <= args.num_stacked_frames <= 4 or not 1 <= args.hidden_size <= 512):
+        raise ValueError('--use-images --fused-update serves the policy without --use-grid on 1 .. 4 stacked frames with a head of width '
+                         '1 .. 512 (stove_ppo_update_images)')
+    env =BillardsEnv(n=args.num_balls, r=args.radius, granularity=args.gran, t=args.dt, seed=args.seed)
     task = AvoidanceTask(env, num_stacked=args.num_stacked_frames, action_force=args.action_force, greyscale=False)
     if use_images:
         actor_critic = Policy(task.get_framebuffer_shape(), task.get_action_space(), hidden_size=args.hidden_size,
@@ -109,10 +114,8 @@ def build(args, writer=None):
         shape = env.get_state_shape()
         actor_critic = Policy(shape[0] * shape[1], task.get_action_space(), hidden_size=64, base='control')
     agent = PPOAgent(actor_critic, args.clip_param, args.num_ppo_epochs, args.num_ppo_mb, args.value_loss_coef, args.entropy_coef, args.lr,
-                     args.eps, args.max_grad_norm, fused=True if args.fused_update else None)
-    device = args.device or ('cuda' if torch.cuda.is_available() else 'cpu')
-    if args.fused_update and torch.device(device).type != 'cuda':
-        raise ValueError('--fused-update needs a GPU')
+                     args.eps, args.max_grad_norm, fused=True if args.fused_update and not use_images else None,
+                     fused_images=True if args.fused_update and use_images else None)
     if args.device_envs and torch.device(device).type != 'cuda':
         raise ValueError('--device-envs needs a GPU')
     runner = PPORunner(env=env, task=task, summary_path=os.path.join(args.summary_dir, args.experiment_id), device=device, agent=agent,

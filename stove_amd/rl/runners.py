@@ -264,7 +264,8 @@ class PPORunner(Runner):
 
     def run_batch(self, fused=None, u=None):
         """One batch of the image arm (reference runners.py: PPORunner.run_batch): collect batch_size trajectories of num_steps on rendered
-        frames, then one PPO update on the stacked observations (B S, F C, res, res) -> the collection (see collect_images) with 'losses'"""
+        frames, then one PPO update on the stacked observations (B S, F C, res, res) -- with a fused_images agent on the frames themselves,
+        no stacked observation built -> the collection (see collect_images) with 'losses'"""
         out, batch = self.collect_images(self.batch_size, self.num_steps, fused, u)
         if bool(out['status'].any()):
             bad = torch.nonzero(out['status']).reshape(-1).tolist()
@@ -272,11 +273,15 @@ class PPORunner(Runner):
                                % (bad, out['status'][bad].tolist()))
         self.last_batch = batch
         F = out['frames'].shape[1] - self.num_steps
-        obs = self.stacked(out['frames'], F)[:, :-1]
         three = lambda a: a.unsqueeze(-1)
         values, returns = three(out['values']), three(out['returns'])
         adv_targ = (returns - values).detach()
-        out['losses'] = self._train_ppo(obs, three(out['actions']).long(), returns, values, three(out['logp']), adv_targ)
+        if getattr(self.agent, 'fused_images', False):          # (the windows are read where the collection wrote them)
+            out['losses'] = self.agent.update_windows(out['frames'], self.num_steps, out['actions'], out['returns'], out['values'], out['logp'],
+                                                      adv_targ)
+        else:
+            obs = self.stacked(out['frames'], F)[:, :-1]
+            out['losses'] = self._train_ppo(obs, three(out['actions']).long(), returns, values, three(out['logp']), adv_targ)
         self._log_to_tb({'/losses/value_loss': out['losses'][0], '/losses/action_loss': out['losses'][1], '/losses/entropy': out['losses'][2],
                          '/info/rewards': float(out['rewards'].mean())})
         self.batch_counter += 1

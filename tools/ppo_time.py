@@ -38,7 +38,16 @@ times the arm on images (PPORunner.collect_images) at 32 x 128 and 256 x 128 ste
   fused_launch_ms   ops.ppo_collect_images alone on a prepared image, the four warm-up steps included; step_us: that per step of the 132
   fused_ms          collect_images(fused=True): the start states, their upload and the image included
   composed_ms       the composed device loop: per step one batched Policy.act on the window and one stove_env_step with its frame
-  update_ms         for context: PPOAgent.update on the collected batch (4 epochs x 32 mini-batches, torch autograd + Adam), once"""
+  update_ms         for context: PPOAgent.update on the collected batch (4 epochs x 32 mini-batches, torch autograd + Adam), once
+
+    python tools/ppo_time.py --images-update [--reps 5] [--images-update-out profiles/ppo_image_update.json]
+
+times the update of the image policy (N = 3, F = 4, head widths 512 and 64, 4 epochs x 32 mini-batches) at 32 x 128 and 256 x 128, three
+ways in this one process on the same collected batch (writes profiles/ppo_image_update.json):
+  torch_update_ms     what PPORunner.run_batch does with a torch agent: the stacked windows built from the frames, then PPOAgent.update
+  update_windows_ms   PPOAgent(fused_images=True).update_windows on the frames: the permutations, their upload, the image, the chain of
+                      launches of stove_ppo_update_images, the image written back and the one read of the losses and the status
+  launch_ms           ops.ppo_update_images alone on prepared tensors; step_us: that per optimiser step of the 128"""
 import argparse
 import json
 import os
@@ -62,6 +71,9 @@ def main():
     ap.add_argument('--images', action='store_true', help='time the collection on images: the composed loop against the one launch')
     ap.add_argument('--images-hidden', type=int, default=512, help='head width of the image policy (main_rl\'s default 512)')
     ap.add_argument('--images-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_image.json'))
+    ap.add_argument('--images-update', action='store_true', help='time the update of the image policy: torch against the device chain')
+    ap.add_argument('--images-update-out',
+                    default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_image_update.json'))
     args = ap.parse_args()
     build.build_library()
     import numpy as np
@@ -132,6 +144,53 @@ def main():
             print('%dx%d' % (B, S), json.dumps(row), flush=True)
         os.makedirs(os.path.dirname(args.model_out), exist_ok=True)
         with open(args.model_out, 'w') as fh:
+            json.dump(result, fh, indent=1, sort_keys=True)
+        return
+    if args.images_update:
+        result['policy'] = {'F': 4, 'deep': False}
+        result['update'] = {'epochs': 4, 'mini_batches': 32}
+        for H in (512, 64):
+            for B, S in ((32, 128), (256, 128)):
+                torch.manual_seed(0)
+                np.random.seed(0)
+                env = envs.BillardsEnv(n=3, granularity=2, seed=0)
+                task = envs.AvoidanceTask(env, num_stacked=4, action_force=.3)
+                policy = Policy(task.get_framebuffer_shape(), 9, hidden_size=H, stacked_frames=4)
+                agent = PPOAgent(policy, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40)
+                runner = PPORunner(env, task, None, dev, agent, policy, num_steps=S, batch_size=B, discount=.95)
+                u = np.random.random_sample((B, S)).astype(np.float32)
+                out, _ = runner.collect_images(B, S, fused=True, u=u)
+                three = lambda a: a.unsqueeze(-1)
+                flat = lambda a: a.reshape((-1, *a.size()[2:]))
+                adv = out['returns'] - out['values']
+
+                def torch_update():          # (what run_batch does without fused_images: the stacked windows are built per update)
+                    obs = flat(runner.stacked(out['frames'], 4)[:, :-1])
+                    return agent.update(obs, flat(three(out['actions']).long()), flat(three(out['returns'])), flat(three(out['values'])),
+                                        flat(three(out['logp'])), flat(three(adv)))
+
+                row = {'torch_update_ms': timed(torch_update, args.reps)}
+                twin = Policy(task.get_framebuffer_shape(), 9, hidden_size=H, stacked_frames=4).to(dev)
+                twin.load_state_dict(policy.state_dict())
+                fused_agent = PPOAgent(twin, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40, fused_images=True)
+                row['update_windows_ms'] = timed(lambda: fused_agent.update_windows(out['frames'], S, out['actions'], out['returns'], out['values'],
+                                                                                    out['logp'], adv), args.reps)
+                n = B * S
+                image = twin.flat_image_params()
+                m, v, step = torch.zeros_like(image), torch.zeros_like(image), torch.zeros(1, dtype=torch.int32, device=dev)
+                perm = torch.stack([torch.randperm(n) for _ in range(4)]).to(device=dev, dtype=torch.int32)
+                rows = [out['actions'].reshape(n)] + [t.reshape(n).contiguous() for t in (out['returns'], out['values'], out['logp'], adv)]
+                launch = lambda o=None: ops.ppo_update_images(image, m, v, step, out['frames'], *rows, perm, 32, 4, H, False, .1, .5, .01, 2e-4, 1e-5,
+                                                              40., steps_per_env=S, out=o)
+                outs = launch()
+                row['launch_ms'] = timed(lambda: launch(outs), args.reps)
+                row['step_us'] = row['launch_ms'] * 1e3 / 128
+                row['status'] = outs['status'].tolist()
+                row['workspace_mb'] = ops._PPO_IMAGE_WS[(image.device, n, 32, 4, H, 0)].numel() * 4 / 2 ** 20
+                result['batches']['h%d_%dx%d' % (H, B, S)] = row
+                print('h%d_%dx%d' % (H, B, S), json.dumps(row), flush=True)
+        os.makedirs(os.path.dirname(args.images_update_out), exist_ok=True)
+        with open(args.images_update_out, 'w') as fh:
             json.dump(result, fh, indent=1, sort_keys=True)
         return
     if args.images:
