@@ -404,6 +404,24 @@ int stove_env_step(double* x, double* v, const double* r, const double* m, const
                    float* frames, int M, int N, int granularity, int res, int use_colors, int drift, double hw, double t,
                    double friction, double action_force, void* stream);
 
+/* ---- Data synthesis: B whole sequences of T steps in one launch (csrc/env_sequences.hip, csrc/env_step.h, csrc/env_gravity.h;
+ * stove_amd/envs/synth.py's numpy arithmetic is the specification, itself held to stove_amd/envs/envs.py).  x0, v0 (B, N, 2), r, m (B, N)
+ * double, the start states: read only; 1 <= N <= 6.  kind 0: billiards, stepped as stove_env_step steps, with actions (B, T) -- step s of
+ * sequence b takes actions[b][s] -- or NULL for plain billiards.  kind 1: gravity (PhysicsEnv.step with the centre-of-mass shift +
+ * GravityEnv.simulate_physics: G = 0.5, softening 1e-5, the pull to the middle, forces clipped to [-1, 1]); it takes no actions, and r is
+ * used by the frames only.  y (B, T, N, 4): (x, v) after each step.  frames (B, T, 3, res, res) float or NULL: the frame of y[b][s], as
+ * stove_env_step paints it.  collisions (B, T): 1 if step s had a controlled collision (0 for gravity).  in_bounds (B,): the number of
+ * (step, ball, axis) position coordinates strictly inside (0, hw), the integer behind the reference's acceptance rule for generated runs.
+ * The states equal the specification's bit for bit (IEEE double add, multiply, divide, sqrt, uncontracted; norms as sqrt(a a + b b), cubes
+ * as d d d); frames agree to one float32 ulp.
+ * status (B,): 0 done; 2 one of the sequence's T action indices is outside [0, 9) -- none of its y, frames, collisions or in_bounds rows
+ * is written, the other sequences are unaffected.  One launch on `stream`, one workgroup per sequence, no synchronisation, no atomics.
+ * A NULL x0, v0, r, m, y, collisions, in_bounds or status, B < 0, N outside 1 .. 6, T < 1, granularity < 1, res < 1 or res^2 >= 2^28, kind
+ * outside {0, 1}, kind 1 with actions: hipErrorInvalidValue, nothing launched.  B == 0 is a valid empty call. */
+int stove_env_sequences(const double* x0, const double* v0, const double* r, const double* m, const int* actions, double* y,
+                        float* frames, int* collisions, int* in_bounds, int* status, int B, int N, int T, int granularity, int res,
+                        int use_colors, int drift, int kind, double hw, double t, double friction, double action_force, void* stream);
+
 /* ---- Tree search on those environments themselves (csrc/env_search.hip, csrc/env_search.h; the host forest EnvForest of
  * stove_amd/mcts/mcts_env.py is the specification): R independent trees per environment, T = M R, tree e R + k searching from
  * environment e's state x, v (M, N, 2), r, m (M, N) double, which is read only.  Nine actions, c = 1, rollout depth D >= 2.  Trees as in

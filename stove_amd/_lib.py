@@ -92,6 +92,7 @@ def _declare(lib):
         'stove_plan_search_ws_bytes': (S, [I] * 5),
         'stove_plan_search': (I, [P] * 19 + [I] * 9 + [F] * 4 + [I, P]),
         'stove_env_step': (I, [P] * 8 + [I] * 6 + [ctypes.c_double] * 4 + [P]),
+        'stove_env_sequences': (I, [P] * 10 + [I] * 8 + [ctypes.c_double] * 4 + [P]),
         'stove_env_search': (I, [P] * 15 + [I] * 8 + [ctypes.c_double] * 4 + [P]),
         'stove_ppo_param_floats': (S, [I, I, I]),
         'stove_ppo_collect': (I, [P] * 14 + [I] * 7 + [ctypes.c_double] * 5 + [P]),

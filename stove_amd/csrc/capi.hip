@@ -39,6 +39,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "plan_tree.hip"
 #include "render.hip"
 #include "env.hip"
+#include "env_sequences.hip"
 #include "env_search.hip"
 #include "ppo_collect.hip"
 #include "ppo_model.hip"
@@ -185,6 +186,7 @@ extern "C" {
 //     stove_plan_search_ws_bytes, stove_plan_search -- a whole search of a batch of trees, the trees on the device;
 //     stove_env_step -- a batch of avoidance / billiards environments stepped and rendered in place (env.hip);
 //     stove_env_search -- tree search on those environments themselves, one launch per planning step (env_search.hip);
+//     stove_env_sequences -- whole training sequences, billiards or gravity, every state and frame in one launch (env_sequences.hip);
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in;
 //     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
 //     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip);
@@ -1581,6 +1583,19 @@ int stove_env_step(double* x, double* v, const double* r, const double* m, const
   const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
   STOVE_LAUNCH(env_step_k, dim3(M), dim3(kEnvThreads), 0, (hipStream_t)stream, x, v, r, m, action, collisions, status, frames, p, res,
                use_colors != 0 ? 1 : 0);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- data synthesis: whole sequences in one launch (env_sequences.hip)
+int stove_env_sequences(const double* x0, const double* v0, const double* r, const double* m, const int* actions, double* y, float* frames,
+                        int* collisions, int* in_bounds, int* status, int B, int N, int T, int granularity, int res, int use_colors,
+                        int drift, int kind, double hw, double t, double friction, double action_force, void* stream) {
+  STOVE_VALIDATE(env_sequences(x0, v0, r, m, actions, y, collisions, in_bounds, status, B, N, T, granularity, res, kind));
+  if (B == 0) return 0;
+  const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
+  STOVE_LAUNCH(env_sequences_k, dim3(B), dim3(kSeqThreads), 0, (hipStream_t)stream, x0, v0, r, m, actions, y, frames, collisions, in_bounds,
+               status, p, T, res, use_colors != 0 ? 1 : 0, kind);
   STOVE_LAUNCH_CHECK();
   return 0;
 }

@@ -250,6 +250,19 @@ inline int env_step(const double* x, const double* v, const double* r, const dou
   return (null_any(x, v, r, m) || null_any(collisions, status)) ? kStoveInvalidValue : 0;
 }
 
+// ---- stove_env_sequences: B whole sequences of T steps of N balls, billiards (kind 0) or gravity (kind 1), every state and frame written
+// out (csrc/env_sequences.hip).  B == 0 is a valid empty call; actions and frames are optional, and gravity takes no actions.  The action
+// indices are device memory and are checked by the kernel (status).
+inline int env_sequences(const double* x0, const double* v0, const double* r, const double* m, const int* actions, const double* y,
+                         const int* collisions, const int* in_bounds, const int* status, int B, int N, int T, int granularity, int res,
+                         int kind) {
+  if (B < 0 || N < 1 || N > kEnvMaxObjects || T < 1 || granularity < 1 || res < 1 || kind < 0 || kind > 1) return kStoveInvalidValue;
+  if (kind == 1 && actions != nullptr) return kStoveInvalidValue;
+  if ((long long)res * res > 0x0fffffffLL) return kStoveInvalidValue;          // (a frame's pixels are counted in int)
+  if (B == 0) return 0;          // (arrays without elements have no address)
+  return (null_any(x0, v0, r, m, y) || null_any(collisions, in_bounds, status)) ? kStoveInvalidValue : 0;
+}
+
 // ---- stove_env_search: R trees per environment searched on M environments of N balls (csrc/env_search.hip).  M == 0 is a valid empty
 // call, and so is runs == 0 (only `action` is written; draws may be NULL).  The table and the trees are device memory and are checked
 // by the kernel (status).

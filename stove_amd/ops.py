@@ -1072,6 +1072,37 @@ def env_step(x, v, r, m, action, granularity, res, hw, t=1.0, friction=0.0, acti
     return frames, collisions, status
 
 
+def env_sequences(x0, v0, r, m, actions, t_len, granularity, res, hw, t=1.0, friction=0.0, action_force=0.6, use_colors=True, drift=False,
+                  gravity=False, render=True, out=None):
+    """B whole sequences of t_len steps in one launch (stove_env_sequences, csrc/env_sequences.hip).  x0, v0 (B, N, 2), r, m (B, N)
+    float64 device tensors, the start states: read only.  actions (B, t_len) int32 indices into the nine directions, or None (plain
+    billiards; gravity takes none).  out: dict of tensors to write into (y (B, T, N, 4) float64, frames (B, T, 3, res, res) float32 --
+    absent or None: no frames --, collisions (B, T), in_bounds (B,), status (B,) int32); None allocates them.
+    -> that dict (frames None with render=False); status 2: one of the sequence's action indices was outside [0, 9) and nothing else of
+    it was written."""
+    lib = _lib.load()
+    B, N, dev = _env_state('env_sequences', x0, v0, r, m, 'synth.synth_sequences_batched(device=None)', count='B')
+    T = int(t_len)
+    if T < 1:
+        raise ValueError('ops.env_sequences: t_len must be at least 1')
+    if actions is not None:
+        if gravity:
+            raise ValueError('ops.env_sequences: gravity takes no actions')
+        _arg('env_sequences', 'actions', actions, _I32, dev, (B, T))
+    table = {'y': ((B, T, N, 4), _F64), 'frames': ((B, T, 3, res, res), _F32), 'collisions': ((B, T), _I32), 'in_bounds': ((B,), _I32),
+             'status': ((B,), _I32)}
+    if not (render if out is None else out.get('frames') is not None):          # (no frame is written through a null pointer)
+        del table['frames']
+    with torch.cuda.device(dev):
+        out = _outputs('env_sequences', out, table, dev, 'batch', torch.empty)
+        check(lib.stove_env_sequences(ptr(x0), ptr(v0), ptr(r), ptr(m), ptr(actions), ptr(out['y']), ptr(out.get('frames')),
+                                      ptr(out['collisions']), ptr(out['in_bounds']), ptr(out['status']), B, N, T, int(granularity), int(res),
+                                      int(bool(use_colors)), int(bool(drift)), int(bool(gravity)), float(hw), float(t), float(friction),
+                                      float(action_force), stream()), 'stove_env_sequences')
+    out.setdefault('frames', None)
+    return out
+
+
 def env_search(x, v, r, m, draws, arrays, depth, granularity, hw, t=1.0, friction=0.0, action_force=0.6, drift=False, replicas=1):
     """Tree search on M avoidance environments themselves (stove_env_search, csrc/env_search.hip): `replicas` trees per environment,
     T = M replicas, all draws.shape[1] iterations in one launch, nothing synchronised.  x, v (M, N, 2), r, m (M, N) float64 device
