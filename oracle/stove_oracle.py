@@ -555,13 +555,24 @@ def dynamics_forward(c, params, s, actions=None, app=None, lim_enc=2, core=0, wi
 
     reward = 0
     if c.action_conditioned:
-        q = _lin(params, 'dyn.reward_head0.2', torch.relu(_lin(params, 'dyn.reward_head0.0', pred))).sum(1)
-        q = torch.relu(_lin(params, 'dyn.reward_head1.0', q))
-        q = torch.relu(_lin(params, 'dyn.reward_head1.2', q))
-        reward = torch.sigmoid(_lin(params, 'dyn.reward_head1.4', q).view(-1, 1))
+        reward = reward_head(params, pred)
     if with_pred:
         return result, reward, pred
     return result, reward
+
+
+def reward_head(params, pred, saved=False):
+    """The reward head, dynamics.py:254-263: pred (B,N,cl) -> reward (B,1) = sigmoid(head1(sum_objects head0(pred))).
+    saved: also the four activations a backward pass keeps -- H0 (B,N,cl) = relu(head0.0), Q (B,cl) the object sum,
+    A1 (B,cl/2) = relu(head1.0), A2 (B,cl/4) = relu(head1.2)."""
+    h0 = torch.relu(_lin(params, 'dyn.reward_head0.0', pred))
+    q = _lin(params, 'dyn.reward_head0.2', h0).sum(1)
+    a1 = torch.relu(_lin(params, 'dyn.reward_head1.0', q))
+    a2 = torch.relu(_lin(params, 'dyn.reward_head1.2', a1))
+    reward = torch.sigmoid(_lin(params, 'dyn.reward_head1.4', a2).view(-1, 1))
+    if saved:
+        return reward, h0, q, a1, a2
+    return reward
 
 
 def constrain_z_dyn(c, z, z_std=None):

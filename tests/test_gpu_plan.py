@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-import stove_oracle as O
+import plan_cases
 from gpu_helpers import check, err, fill_analytic, regime_bar
 from helpers import oracle_setup
 from test_gpu_dynamics import CASES, make_cfg
@@ -78,37 +78,16 @@ def _expand(st, pool, leaf, child, len_s, app, acts, D):
 
 
 def _one_hot_actions(acts, trees=M):
-    """(trees A, 1 + L, A): action a of the row first, then its random actions"""
-    first = torch.arange(A).repeat(trees)[:, None]
-    return torch.nn.functional.one_hot(torch.cat([first, acts.long()], 1), A)
+    return plan_cases.one_hot_actions(acts, A, trees)
 
 
 def _oracle_rollout(regime, dtype, z, app, acts):
     c, params = _oracle(regime, dtype)
-    with torch.no_grad():
-        zs, rew = O.rollout(c, params, z.repeat_interleave(A, 0).to(dtype), 1 + acts.shape[1], _one_hot_actions(acts).to(dtype),
-                            app.repeat_interleave(A, 0).to(dtype))
-    return zs, rew[..., 0]
+    return plan_cases.oracle_rollout(c, params, z, app, acts, A)
 
 
 def _value(rew, len_s, D, dtype):
-    """the reference's backpropagate value, written out per row in `dtype`: rew (M A, 1 + L) -> (M, A)"""
-    rew = rew.numpy().astype(dtype)
-    L = rew.shape[1] - 1
-    q = np.zeros((M, A), dtype=dtype)
-    g = dtype(GAMMA)
-    for m in range(M):
-        n = min(2 * D - len_s[m] + 1, L)
-        s2 = dtype(0)
-        for j in range(len_s[m], D):
-            s2 += g ** dtype(j)
-        for a in range(A):
-            r = rew[m * A + a]
-            s1 = dtype(0)
-            for k in range(n):
-                s1 += r[1 + k] - dtype(1)
-            q[m, a] = (r[0] - dtype(1)) * g ** dtype(len_s[m]) + s1 * s2
-    return q
+    return plan_cases.value(rew, len_s, D, dtype, M, A, GAMMA)
 
 
 # ------------------------------------------------------------------------------------------------ 1. the float64 oracle
