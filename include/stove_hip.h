@@ -609,6 +609,30 @@ int stove_rollout_bwd_cl(const float* z_last, const float* extra, const float* p
                          float* g_params, void* ws, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
                          float pos_var, float vel_std, float lat_std, void* stream);
 
+/* ---- Planning at state-code lengths other than 32 (csrc/plan.hip, csrc/plan_tree.hip): stove_plan_expand and stove_plan_search with
+ * every width derived from cl = 16 or 64 -- z_pool (M, cap, N, cl/2 + 2); gnn_params the stove_gnn_param_floats_cl(cl) image that
+ * stove_rollout_fwd_cl takes, which is the rollout behind these calls (child states bit for bit its z_pred); a node's input row is
+ * [state cl/2 | action embedding 4 | appearance], so 1 <= N <= 6 and app_dim <= cl/2 - 4 (4 at cl = 16, 28 at cl = 64).
+ * rh_params: the reward head at that width, head0 = Linear(cl,cl) ReLU Linear(cl,cl) summed over the objects, head1 =
+ * Linear(cl,cl/2) ReLU Linear(cl/2,cl/4) ReLU Linear(cl/4,1), the ten tensors in module order, nn.Linear layout:
+ * stove_reward_head_param_floats_cl(cl) = 2 cl^2 + 2 cl + cl^2/2 + cl/2 + cl^2/8 + cl/4 + cl/4 + 1 floats (721 / 10945; 0 for any
+ * other cl).  Launch counts, outputs, the value formula, status and the treatment of bad device indices are those of the cl = 32
+ * calls; forward only.  Any other cl (32 included: it has its own entry points), and what those calls reject at this width's limits:
+ * hipErrorInvalidValue, nothing launched; the workspace queries then return 0. */
+size_t stove_reward_head_param_floats_cl(int cl);
+size_t stove_plan_expand_ws_bytes_cl(int cl, int M, int A, int L, int N, int app_dim);
+int stove_plan_expand_cl(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app,
+                         const int* acts, const float* emb_w, const float* emb_b, const float* gnn_params,
+                         const float* rh_params, float* q, float* r_first, float* r_roll, void* ws,
+                         int cl, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                         float pos_var, float vel_std, float lat_std, float gamma, void* stream);
+size_t stove_plan_search_ws_bytes_cl(int cl, int M, int A, int L, int N, int app_dim);
+int stove_plan_search_cl(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used,
+                         double* min_gap, int* status, int* action, int* sel_trace, const float* app, const int* acts,
+                         const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, void* ws,
+                         int cl, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                         float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream);
+
 /* ---- Stove._3_only_match_objects / _greedy_match_objects / _volatile_match_objects
  * (stove.py:200-329, 432-514, 331-430): the T-serial nearest-neighbour re-ordering of objects.
  * feat (B,T,N,F) matching features in [-1,1] (positions [, appearance]); mode 0 = '3_only',

@@ -91,6 +91,11 @@ def _declare(lib):
         'stove_plan_expand': (I, [P] * 14 + [I] * 9 + [F] * 4 + [P]),
         'stove_plan_search_ws_bytes': (S, [I] * 5),
         'stove_plan_search': (I, [P] * 19 + [I] * 9 + [F] * 4 + [I, P]),
+        'stove_reward_head_param_floats_cl': (S, [I]),
+        'stove_plan_expand_ws_bytes_cl': (S, [I] * 6),
+        'stove_plan_expand_cl': (I, [P] * 14 + [I] * 10 + [F] * 4 + [P]),
+        'stove_plan_search_ws_bytes_cl': (S, [I] * 6),
+        'stove_plan_search_cl': (I, [P] * 19 + [I] * 10 + [F] * 4 + [I, P]),
         'stove_env_step': (I, [P] * 8 + [I] * 6 + [ctypes.c_double] * 4 + [P]),
         'stove_env_sequences': (I, [P] * 10 + [I] * 8 + [ctypes.c_double] * 4 + [P]),
         'stove_env_search': (I, [P] * 15 + [I] * 8 + [ctypes.c_double] * 4 + [P]),

@@ -1468,47 +1468,59 @@ int stove_small_linear(const float* x, const float* W, const float* b, float* y,
 }
 
 // ---------------------------------------------------------------- planning: one expansion of M search trees (plan.hip)
+size_t stove_reward_head_param_floats_cl(int cl) { return cl == 16 ? RhCl<16>::kParams : (cl == 64 ? RhCl<64>::kParams : 0); }
+
 namespace {
 struct PlanWs {
   size_t z_in, extra, z_pred, pred, ok, bytes;          // byte offsets
-  PlanWs(int M, int A, int L, int N, int app_dim) {
-    const size_t rows = (size_t)M * A, steps = 1 + (size_t)L;
+  PlanWs(int cl, int M, int A, int L, int N, int app_dim) {
+    const size_t rows = (size_t)M * A, steps = 1 + (size_t)L, zw = (size_t)cl / 2 + 2;
     z_in = 0;
-    extra = z_in + align64(rows * N * 18 * sizeof(float));
+    extra = z_in + align64(rows * N * zw * sizeof(float));
     z_pred = extra + align64(rows * steps * N * (4 + app_dim) * sizeof(float));
-    pred = z_pred + align64(rows * steps * N * 18 * sizeof(float));
-    ok = pred + align64(rows * steps * N * 32 * sizeof(float));
+    pred = z_pred + align64(rows * steps * N * zw * sizeof(float));
+    ok = pred + align64(rows * steps * N * cl * sizeof(float));
     bytes = ok + align64((size_t)M * sizeof(int));
   }
 };
 }  // namespace
 
 size_t stove_plan_expand_ws_bytes(int M, int A, int L, int N, int app_dim) {
-  return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanWs(M, A, L, N, app_dim).bytes;
+  return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanWs(32, M, A, L, N, app_dim).bytes;
+}
+size_t stove_plan_expand_ws_bytes_cl(int cl, int M, int A, int L, int N, int app_dim) {
+  return stove_validate::plan_dims_bad(M, A, L, N, app_dim, stove_validate::gnn_limits_cl(cl)) ? 0 : PlanWs(cl, M, A, L, N, app_dim).bytes;
 }
 
-// the three launches of one expansion (arguments validated by the caller)
+// the three launches of one expansion at state-code length cl = 16 / 32 / 64 (arguments validated by the caller)
 static int plan_expand_launch(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
                               const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, float* q, float* r_first,
-                              float* r_roll, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                              float* r_roll, void* ws, int cl, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
                               float pos_var, float vel_std, float lat_std, float gamma, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const PlanWs w(M, A, L, N, app_dim);
+  const PlanWs w(cl, M, A, L, N, app_dim);
   char* base = (char*)ws;
   float* z_in = (float*)(base + w.z_in);
   float* extra = (float*)(base + w.extra);
   float* z_pred = (float*)(base + w.z_pred);
   float* pred = (float*)(base + w.pred);
   int* ok = (int*)(base + w.ok);
-  const int rows = M * A;
+  const int rows = M * A, sin_dim = cl / 2 + 4 + app_dim;
   STOVE_LAUNCH(plan_prep_k, dim3(M), dim3(kPlanPrepThreads), 0, st, (const float*)z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, z_in, extra,
-               ok, cap, A, L, D, N, app_dim);
+               ok, cap, A, L, D, N, app_dim, cl / 2 + 2);
   STOVE_LAUNCH_CHECK();
-  const int rc = stove_rollout_fwd(z_in, extra, gnn_params, z_pred, nullptr, pred, rows, 1 + L, 1 + L, N, 20 + app_dim, lim_enc, elu, pos_var,
-                                   vel_std, lat_std, stream);
+  const int rc = cl == 32 ? stove_rollout_fwd(z_in, extra, gnn_params, z_pred, nullptr, pred, rows, 1 + L, 1 + L, N, sin_dim, lim_enc, elu, pos_var,
+                                              vel_std, lat_std, stream)
+                          : stove_rollout_fwd_cl(z_in, extra, gnn_params, z_pred, nullptr, pred, cl, rows, 1 + L, 1 + L, N, sin_dim, lim_enc, elu,
+                                                 pos_var, vel_std, lat_std, stream);
   if (rc) return rc;
-  STOVE_LAUNCH(plan_finish_k, dim3(reward_head_blocks(rows)), dim3(64 * kRhWaves), 0, st, (const float*)pred, (const float*)z_pred, rh_params,
-               (const int*)ok, child, len_s, z_pool, q, r_first, r_roll, rows, cap, A, L, D, N, gamma);
+#define STOVE_PLAN_FINISH(CL)                                                                                                               \
+  STOVE_LAUNCH(plan_finish_k<CL>, dim3(reward_head_blocks(rows)), dim3(64 * kRhWaves), 0, st, (const float*)pred, (const float*)z_pred, rh_params, \
+               (const int*)ok, child, len_s, z_pool, q, r_first, r_roll, rows, cap, A, L, D, N, gamma)
+  if (cl == 32) STOVE_PLAN_FINISH(32);
+  else if (cl == 16) STOVE_PLAN_FINISH(16);
+  else STOVE_PLAN_FINISH(64);
+#undef STOVE_PLAN_FINISH
   STOVE_LAUNCH_CHECK();
   return 0;
 }
@@ -1518,16 +1530,26 @@ int stove_plan_expand(float* z_pool, const int* leaf, const int* child, const in
                       float* r_roll, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu, float pos_var,
                       float vel_std, float lat_std, float gamma, void* stream) {
   STOVE_VALIDATE(plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, ws, M, cap, A, L, D, N, app_dim));
-  return plan_expand_launch(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, r_first, r_roll, ws, M, cap, A, L, D, N,
-                            app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
+  return plan_expand_launch(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, r_first, r_roll, ws, 32, M, cap, A, L, D,
+                            N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
+}
+
+int stove_plan_expand_cl(float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
+                         const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, float* q, float* r_first,
+                         float* r_roll, void* ws, int cl, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
+                         float pos_var, float vel_std, float lat_std, float gamma, void* stream) {
+  STOVE_VALIDATE(plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, ws, M, cap, A, L, D, N, app_dim,
+                             stove_validate::gnn_limits_cl(cl)));
+  return plan_expand_launch(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, q, r_first, r_roll, ws, cl, M, cap, A, L, D,
+                            N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
 }
 
 // ---------------------------------------------------------------- planning: a whole search, the trees on the device (plan_tree.hip)
 namespace {
 struct PlanSearchWs {          // the expansion's workspace, then q (M, A), the index vectors select writes and its walk's gap (M,) double
   size_t q, leaf, child, len_s, gap, bytes;
-  PlanSearchWs(int M, int A, int L, int N, int app_dim) {
-    q = PlanWs(M, A, L, N, app_dim).bytes;
+  PlanSearchWs(int cl, int M, int A, int L, int N, int app_dim) {
+    q = PlanWs(cl, M, A, L, N, app_dim).bytes;
     leaf = q + align64((size_t)M * A * sizeof(float));
     child = leaf + align64((size_t)M * sizeof(int));
     len_s = child + align64((size_t)M * sizeof(int));
@@ -1538,31 +1560,34 @@ struct PlanSearchWs {          // the expansion's workspace, then q (M, A), the 
 }  // namespace
 
 size_t stove_plan_search_ws_bytes(int M, int A, int L, int N, int app_dim) {
-  return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanSearchWs(M, A, L, N, app_dim).bytes;
+  return stove_validate::plan_dims_bad(M, A, L, N, app_dim) ? 0 : PlanSearchWs(32, M, A, L, N, app_dim).bytes;
+}
+size_t stove_plan_search_ws_bytes_cl(int cl, int M, int A, int L, int N, int app_dim) {
+  return stove_validate::plan_dims_bad(M, A, L, N, app_dim, stove_validate::gnn_limits_cl(cl)) ? 0 : PlanSearchWs(cl, M, A, L, N, app_dim).bytes;
 }
 
-int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap,
-                      int* status, int* action, int* sel_trace, const float* app, const int* acts, const float* emb_w, const float* emb_b,
-                      const float* gnn_params, const float* rh_params, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim,
-                      int lim_enc, int elu, float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream) {
-  STOVE_VALIDATE(plan_search(z_pool, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, app, acts, emb_w, emb_b, gnn_params,
-                             rh_params, ws, M, cap, A, L, D, N, app_dim, R));
+// the 5 R + 1 launches of one search at state-code length cl (arguments validated by the caller)
+static int plan_search_launch(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap,
+                              int* status, int* action, int* sel_trace, const float* app, const int* acts, const float* emb_w,
+                              const float* emb_b, const float* gnn_params, const float* rh_params, void* ws, int cl, int M, int cap, int A, int L,
+                              int D, int N, int app_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std, float gamma, int R,
+                              void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const PlanSearchWs w(M, A, L, N, app_dim);
+  const PlanSearchWs w(cl, M, A, L, N, app_dim);
   char* base = (char*)ws;
   float* q = (float*)(base + w.q);
   int* leaf = (int*)(base + w.leaf);
   int* child = (int*)(base + w.child);
   int* len_s = (int*)(base + w.len_s);
   double* gap = (double*)(base + w.gap);
-  const int* ok = (const int*)(base + PlanWs(M, A, L, N, app_dim).ok);
+  const int* ok = (const int*)(base + PlanWs(cl, M, A, L, N, app_dim).ok);
   const double c = 1.0;          // the reference's exploration constant (MCTS.c)
   for (int i = 0; i < R; ++i) {
     STOVE_LAUNCH(plan_tree_select_k, dim3(M), dim3(64), 0, st, first, parent, depth, Ns, Nsa, Qsa, used, gap, status, leaf, child, len_s,
                  sel_trace != nullptr ? sel_trace + (size_t)i * M : nullptr, c, cap, A, D);
     STOVE_LAUNCH_CHECK();
     const int rc = plan_expand_launch(z_pool, leaf, child, len_s, app, acts + (size_t)i * M * A * L, emb_w, emb_b, gnn_params, rh_params, q, nullptr,
-                                      nullptr, ws, M, cap, A, L, D, N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
+                                      nullptr, ws, cl, M, cap, A, L, D, N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, stream);
     if (rc) return rc;
     STOVE_LAUNCH(plan_tree_backprop_k, dim3(M), dim3(64), 0, st, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, (const int*)leaf,
                  (const int*)child, (const double*)gap, (const float*)q, ok, cap, A, D);
@@ -1571,6 +1596,26 @@ int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* N
   STOVE_LAUNCH(plan_tree_action_k, dim3((M + 63) / 64), dim3(64), 0, st, first, Nsa, action, M, cap, A);
   STOVE_LAUNCH_CHECK();
   return 0;
+}
+
+int stove_plan_search(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap,
+                      int* status, int* action, int* sel_trace, const float* app, const int* acts, const float* emb_w, const float* emb_b,
+                      const float* gnn_params, const float* rh_params, void* ws, int M, int cap, int A, int L, int D, int N, int app_dim,
+                      int lim_enc, int elu, float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream) {
+  STOVE_VALIDATE(plan_search(z_pool, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, app, acts, emb_w, emb_b, gnn_params,
+                             rh_params, ws, M, cap, A, L, D, N, app_dim, R));
+  return plan_search_launch(z_pool, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, sel_trace, app, acts, emb_w, emb_b,
+                            gnn_params, rh_params, ws, 32, M, cap, A, L, D, N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, R, stream);
+}
+
+int stove_plan_search_cl(float* z_pool, int* first, int* parent, int* depth, int* Ns, int* Nsa, double* Qsa, int* used, double* min_gap,
+                         int* status, int* action, int* sel_trace, const float* app, const int* acts, const float* emb_w, const float* emb_b,
+                         const float* gnn_params, const float* rh_params, void* ws, int cl, int M, int cap, int A, int L, int D, int N,
+                         int app_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream) {
+  STOVE_VALIDATE(plan_search(z_pool, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, app, acts, emb_w, emb_b, gnn_params,
+                             rh_params, ws, M, cap, A, L, D, N, app_dim, R, stove_validate::gnn_limits_cl(cl)));
+  return plan_search_launch(z_pool, first, parent, depth, Ns, Nsa, Qsa, used, min_gap, status, action, sel_trace, app, acts, emb_w, emb_b,
+                            gnn_params, rh_params, ws, cl, M, cap, A, L, D, N, app_dim, lim_enc, elu, pos_var, vel_std, lat_std, gamma, R, stream);
 }
 
 // ---------------------------------------------------------------- the environments the planner plays: step and frame (env.hip)

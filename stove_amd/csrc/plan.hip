@@ -4,8 +4,10 @@
 // Three launches on one stream, nothing synchronised:
 //   plan_prep_k    gathers the leaf states by index and writes the per-step [action embedding | appearance] rows the rollout reads
 //                  (column `action` of the embedding Linear plus its bias -- no one-hot, no tiled copies, no embedding GEMM),
-//   the cl = 32 rollout launcher (stove_rollout_fwd: the kernels of gnn_small.hip / gnn.hip as they are),
+//   the rollout launcher of the model's state-code length cl (stove_rollout_fwd at cl = 32: the kernels of gnn_small.hip / gnn.hip;
+//                  stove_rollout_fwd_cl at cl = 16 / 64: gnn_cl.hip -- as they are),
 //   plan_finish_k  reward head per step without saved activations, q in a fixed summation order, child states scattered to the pool.
+// Everything is cl wide where it was 32: states N (cl/2 + 2) floats, pred rows cl, the reward head cl-cl-cl / cl-cl/2-cl/4-1.
 // Indices live on the device: a tree with an index out of range (leaf, child range, len_s, any of its A L actions) is flagged by
 // plan_prep_k, rolls out a zero state instead of reading the pool, gets NaN in its q / reward rows and writes no pool slot.
 #include "common.h"
@@ -14,13 +16,13 @@ namespace stove {
 
 constexpr int kPlanPrepThreads = 256;
 
-// ok[m] = 1 where every index of tree m is in range.  z_in (M A, N, 18), extra (M A, 1 + L, N, 4 + app_dim)
+// ok[m] = 1 where every index of tree m is in range.  z_in (M A, N, zw), extra (M A, 1 + L, N, 4 + app_dim); zw = cl/2 + 2
 __global__ __launch_bounds__(kPlanPrepThreads) void plan_prep_k(const float* __restrict__ z_pool, const int* __restrict__ leaf,
                                                                 const int* __restrict__ child, const int* __restrict__ len_s,
                                                                 const float* __restrict__ app, const int* __restrict__ acts,
                                                                 const float* __restrict__ emb_w, const float* __restrict__ emb_b,
                                                                 float* __restrict__ z_in, float* __restrict__ extra, int* __restrict__ ok,
-                                                                int cap, int A, int L, int D, int N, int app_dim) {
+                                                                int cap, int A, int L, int D, int N, int app_dim, int zw) {
   const int m = blockIdx.x, tid = threadIdx.x;
   const int lf = leaf[m], ch = child[m], ls = len_s[m];
   const int* am = acts + (size_t)m * A * L;
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(kPlanPrepThreads) void plan_prep_k(const float* __r
   for (int i = tid; i < A * L; i += kPlanPrepThreads) bad |= am[i] < 0 || am[i] >= A;
   bad = __syncthreads_or(bad);
   if (tid == 0) ok[m] = !bad;
-  const int zrow = N * 18;
+  const int zrow = N * zw;
   const float* zl = z_pool + ((size_t)m * cap + (bad ? 0 : lf)) * zrow;
   float* zo = z_in + (size_t)m * A * zrow;
   for (int i = tid; i < A * zrow; i += kPlanPrepThreads) zo[i] = bad ? 0.0f : zl[i % zrow];
@@ -50,34 +52,54 @@ __global__ __launch_bounds__(kPlanPrepThreads) void plan_prep_k(const float* __r
   }
 }
 
-// pred (M A, 1 + L, N, 32), z_pred (M A, 1 + L, N, 18) of the rollout -> q (M, A), r_first (M, A), r_roll (M, A, L) (the last two may
-// be NULL) and the state after step 0 of row (m, a) into z_pool[m, child[m] + a].  reward_head_fwd_k's arithmetic, nothing saved.
+// The reward head's parameter block at state-code length CL: the ten tensors in module order, nn.Linear layout (at CL = 32 the
+// RH_* offsets of reward_head.hip), 2 CL^2 + 2 CL + CL^2/2 + CL/2 + CL^2/8 + CL/4 + CL/4 + 1 floats
+template <int CL>
+struct RhCl {
+  static constexpr int H1 = CL / 2, H2 = CL / 4;
+  static constexpr int W0A = 0, B0A = W0A + CL * CL, W0B = B0A + CL, B0B = W0B + CL * CL, W1A = B0B + CL, B1A = W1A + H1 * CL, W1B = B1A + H1,
+                       B1B = W1B + H2 * H1, W1C = B1B + H2, B1C = W1C + H2, kParams = B1C + 1;
+};
+static_assert(RhCl<32>::kParams == kRhParams && RhCl<32>::W1A == RH_W1A && RhCl<32>::B1C == RH_B1C, "the cl = 32 block is reward_head.hip's");
+static_assert(RhCl<16>::kParams == 721 && RhCl<64>::kParams == 10945, "reward-head block sizes");
+
+// pred (M A, 1 + L, N, CL), z_pred (M A, 1 + L, N, CL/2 + 2) of the rollout -> q (M, A), r_first (M, A), r_roll (M, A, L) (the last two
+// may be NULL) and the state after step 0 of row (m, a) into z_pool[m, child[m] + a].  reward_head_fwd_k's arithmetic, nothing saved:
+//   head0 = Linear(CL, CL) - ReLU - Linear(CL, CL) summed over the objects, head1 = Linear(CL, CL/2) - ReLU - Linear(CL/2, CL/4) - ReLU
+//   - Linear(CL/4, 1), sigmoid;
 //   q = (r0 - 1) gamma^len_s + (sum_{k < min(2 D - len_s + 1, L)} (r_k - 1)) (sum_{j = len_s}^{D - 1} gamma^j)
-// (the reference's broadcast product of the two sums; the second one is empty, 0, at len_s = D).  One wave per row, sums in step order.
+// (the reference's broadcast product of the two sums; the second one is empty, 0, at len_s = D).  One wave per row, lane l < CL holds
+// element l (the lanes from CL up repeat lane l - CL's arithmetic and write nothing); sums in step order.  The weights are staged
+// transposed once per workgroup: 42 KiB of LDS at CL = 64.
+template <int CL>
 __global__ __launch_bounds__(64 * kRhWaves) void plan_finish_k(const float* __restrict__ pred, const float* __restrict__ z_pred,
                                                                const float* __restrict__ P, const int* __restrict__ ok,
                                                                const int* __restrict__ child, const int* __restrict__ len_s,
                                                                float* __restrict__ z_pool, float* __restrict__ q, float* __restrict__ r_first,
                                                                float* __restrict__ r_roll, int rows, int cap, int A, int L, int D, int N,
                                                                float gamma) {
-  __shared__ __attribute__((aligned(16))) float Wt0a[1024], Wt0b[1024], Wt1a[512], Wt1b[128], V[32 + 32 + 16 + 8 + 8 + 4], xs[kRhWaves][32];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l = lane & 31;
-  for (int i = tid; i < 1024; i += blockDim.x) {
-    const int o = i >> 5, k = i & 31;                    // W (out o, in k) -> Wt[k][o]
-    Wt0a[k * 32 + o] = P[RH_W0A + i];
-    Wt0b[k * 32 + o] = P[RH_W0B + i];
+  using R = RhCl<CL>;
+  constexpr int H1 = R::H1, H2 = R::H2;
+  static_assert(CL == 16 || CL == 32 || CL == 64, "one wave holds a CL-wide vector; rh_dot_t takes K in fours");
+  __shared__ __attribute__((aligned(16))) float Wt0a[CL * CL], Wt0b[CL * CL], Wt1a[CL * H1], Wt1b[H1 * H2], V[CL + CL + H1 + H2 + H2 + 4],
+      xs[kRhWaves][CL];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l = lane & (CL - 1);
+  for (int i = tid; i < CL * CL; i += blockDim.x) {
+    const int o = i / CL, k = i % CL;                    // W (out o, in k) -> Wt[k][o]
+    Wt0a[k * CL + o] = P[R::W0A + i];
+    Wt0b[k * CL + o] = P[R::W0B + i];
   }
-  for (int i = tid; i < 512; i += blockDim.x) Wt1a[(i & 31) * 16 + (i >> 5)] = P[RH_W1A + i];
-  for (int i = tid; i < 128; i += blockDim.x) Wt1b[(i & 15) * 8 + (i >> 4)] = P[RH_W1B + i];
-  float* b0a = V; float* b0b = V + 32; float* b1a = V + 64; float* b1b = V + 80; float* w1c = V + 88; float* b1c = V + 96;
-  for (int i = tid; i < 32; i += blockDim.x) { b0a[i] = P[RH_B0A + i]; b0b[i] = P[RH_B0B + i]; }
-  for (int i = tid; i < 16; i += blockDim.x) b1a[i] = P[RH_B1A + i];
-  for (int i = tid; i < 8; i += blockDim.x) { b1b[i] = P[RH_B1B + i]; w1c[i] = P[RH_W1C + i]; }
-  if (tid == 0) b1c[0] = P[RH_B1C];
+  for (int i = tid; i < H1 * CL; i += blockDim.x) Wt1a[(i % CL) * H1 + i / CL] = P[R::W1A + i];
+  for (int i = tid; i < H2 * H1; i += blockDim.x) Wt1b[(i % H1) * H2 + i / H1] = P[R::W1B + i];
+  float* b0a = V; float* b0b = V + CL; float* b1a = V + 2 * CL; float* b1b = b1a + H1; float* w1c = b1b + H2; float* b1c = w1c + H2;
+  for (int i = tid; i < CL; i += blockDim.x) { b0a[i] = P[R::B0A + i]; b0b[i] = P[R::B0B + i]; }
+  for (int i = tid; i < H1; i += blockDim.x) b1a[i] = P[R::B1A + i];
+  for (int i = tid; i < H2; i += blockDim.x) { b1b[i] = P[R::B1B + i]; w1c[i] = P[R::W1C + i]; }
+  if (tid == 0) b1c[0] = P[R::B1C];
   __syncthreads();
   float* x = xs[wv];
-  const bool act = lane < 32;
-  const int steps = 1 + L, zrow = N * 18;
+  const bool act = lane < CL;
+  const int steps = 1 + L, zrow = N * (CL / 2 + 2);
   const float nan = __int_as_float(0x7fc00000);
   for (int row = blockIdx.x * kRhWaves + wv; row < rows; row += gridDim.x * kRhWaves) {
     const int m = row / A, a = row - m * A;
@@ -95,23 +117,23 @@ __global__ __launch_bounds__(64 * kRhWaves) void plan_finish_k(const float* __re
     float r0 = 0.0f, s1 = 0.0f;
     for (int t = 0; t < steps; ++t) {
       const size_t it = (size_t)row * steps + t;
-      float h32 = 0.0f;
+      float hsum = 0.0f;
       for (int o = 0; o < N; ++o) {
-        const size_t prow = (it * N + o) * 32;
+        const size_t prow = (it * N + o) * CL;
         if (act) x[l] = pred[prow + l];
-        float h = b0a[l] + rh_dot_t<32, 32>(Wt0a, x, l);
+        float h = b0a[l] + rh_dot_t<CL, CL>(Wt0a, x, l);
         h = fmaxf(h, 0.0f);
         if (act) x[l] = h;
-        h32 += b0b[l] + rh_dot_t<32, 32>(Wt0b, x, l);
+        hsum += b0b[l] + rh_dot_t<CL, CL>(Wt0b, x, l);
       }
-      if (act) x[l] = h32;
-      const float a1 = fmaxf(b1a[l & 15] + rh_dot_t<32, 16>(Wt1a, x, l), 0.0f);
-      if (lane < 16) x[l] = a1;
-      const float a2 = fmaxf(b1b[l & 7] + rh_dot_t<16, 8>(Wt1b, x, l), 0.0f);
-      if (lane < 8) x[l] = a2;
+      if (act) x[l] = hsum;
+      const float a1 = fmaxf(b1a[l & (H1 - 1)] + rh_dot_t<CL, H1>(Wt1a, x, l), 0.0f);
+      if (lane < H1) x[l] = a1;
+      const float a2 = fmaxf(b1b[l & (H2 - 1)] + rh_dot_t<H1, H2>(Wt1b, x, l), 0.0f);
+      if (lane < H2) x[l] = a2;
       float z = b1c[0];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) z = fmaf(w1c[k], x[k], z);
+      for (int k = 0; k < H2; ++k) z = fmaf(w1c[k], x[k], z);
       const float r = 1.0f / (1.0f + expf(-z));
       if (t == 0) {
         r0 = r;

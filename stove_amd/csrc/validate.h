@@ -198,16 +198,18 @@ inline int rollout_bwd(const float* z_last, const float* extra, const float* par
 }
 
 // ---- stove_plan_expand: one expansion of M search trees (csrc/plan.hip).  Everything the host can see; the indices themselves
-// (leaf, child, len_s, acts) are device memory and are checked by the kernels.  The rollout behind it is the cl = 32 one.
+// (leaf, child, len_s, acts) are device memory and are checked by the kernels.  The rollout behind it is the one of the state-code
+// length: `k` = kGnn32 (stove_plan_expand) or gnn_limits_cl(cl) (stove_plan_expand_cl: cl = 16 / 64, N <= 6); a node's input row
+// [state cl/2 | action embedding 4 | appearance] has to fit cl, so app_dim <= cl/2 - 4.
 constexpr int kPlanMaxActions = 64;
-inline bool plan_dims_bad(int M, int A, int L, int N, int app_dim) {
-  if (M < 1 || A < 1 || L < 1 || A > kPlanMaxActions || app_dim < 0 || kGnn32.bad(1, N, 20 + app_dim)) return true;
-  return (long long)M * A * (1 + (long long)L) > 0x7fffffffLL / (8 * 32);        // rows x steps x objects x 32 stays an int
+inline bool plan_dims_bad(int M, int A, int L, int N, int app_dim, const GnnLimits& k = kGnn32) {
+  if (M < 1 || A < 1 || L < 1 || A > kPlanMaxActions || app_dim < 0 || k.bad(1, N, k.lo + 4 + app_dim)) return true;
+  return (long long)M * A * (1 + (long long)L) > 0x7fffffffLL / (k.max_obj * k.hi);        // rows x steps x objects x cl stays an int
 }
 inline int plan_expand(const float* z_pool, const int* leaf, const int* child, const int* len_s, const float* app, const int* acts,
                        const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params, const float* q,
-                       const void* ws, int M, int cap, int A, int L, int D, int N, int app_dim) {
-  if (plan_dims_bad(M, A, L, N, app_dim) || D < 1 || cap < 1 + A) return kStoveInvalidValue;
+                       const void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, const GnnLimits& k = kGnn32) {
+  if (plan_dims_bad(M, A, L, N, app_dim, k) || D < 1 || cap < 1 + A) return kStoveInvalidValue;
   if (null_any(z_pool, emb_w, emb_b, gnn_params, rh_params, q) || null_any(leaf, child, len_s, acts) || ws == nullptr) return kStoveInvalidValue;
   if (app_dim > 0 && app == nullptr) return kStoveInvalidValue;
   return 0;
@@ -219,8 +221,8 @@ inline int plan_expand(const float* z_pool, const int* leaf, const int* child, c
 inline int plan_search(const float* z_pool, const int* first, const int* parent, const int* depth, const int* Ns, const int* Nsa,
                        const double* Qsa, const int* used, const double* min_gap, const int* status, const int* action, const float* app,
                        const int* acts, const float* emb_w, const float* emb_b, const float* gnn_params, const float* rh_params,
-                       const void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int R) {
-  if (plan_dims_bad(M, A, L, N, app_dim) || D < 1 || cap < 1 + A || R < 0) return kStoveInvalidValue;
+                       const void* ws, int M, int cap, int A, int L, int D, int N, int app_dim, int R, const GnnLimits& k = kGnn32) {
+  if (plan_dims_bad(M, A, L, N, app_dim, k) || D < 1 || cap < 1 + A || R < 0) return kStoveInvalidValue;
   if (null_any(z_pool, emb_w, emb_b, gnn_params, rh_params) || null_any(first, parent, depth, Ns, Nsa, used, status, action) ||
       null_any(Qsa, min_gap) || ws == nullptr || (R > 0 && acts == nullptr))
     return kStoveInvalidValue;

@@ -20,6 +20,14 @@ GAMMA = 0.95
 # path may be the default only where tools/plan_bench.py has shown it faster than the composed one beyond the run-to-run spread.
 # profiles/plan_bench.json records 1.10 against 3.68 ms per expansion; the default is the composed path all the same.
 FUSED_WHERE_ELIGIBLE = False
+# The state-code lengths the fused expansion and the device-resident search are offered at.  The kernels serve 16, 32 and 64
+# (ops.plan_expand / ops.plan_search); 16 and 64 are switched on per handler (handler.fused_widths, the `fused_widths` keyword of
+# plan_on_model / plan_on_frames / play, tools/run_mcts.py --fused-widths), so that a model of those widths keeps taking the composed
+# path, and keeps being refused by device_trees = True, unless it is asked for.
+FUSED_WIDTHS = (32,)
+# what the kernels of a width take: (object count, appearance columns) -- csrc/validate.h: plan_dims_bad; the table is held to the
+# library's workspace queries by tests/test_plan_cl_cpu.py
+_FUSED_LIMITS = {16: (6, 4), 32: (8, 12), 64: (6, 28)}
 
 
 def multi_one_hot(actions, action_shape):
@@ -346,6 +354,7 @@ class BatchedMCTSHandler():
             t._f, t._m = self.forest, m
         self.timing = {'host': 0.0, 'device': 0.0}        # seconds of the last run_mcts: tree arithmetic / waiting for the model
         self.device_trees = False      # True: run_mcts keeps the trees on the device too, one ops.plan_search call per search
+        self.fused_widths = FUSED_WIDTHS        # the state-code lengths _fused_unserved lets onto the fused expansion
 
     def _fused_default(self, env):
         c = env.c
@@ -364,17 +373,25 @@ class BatchedMCTSHandler():
         and `rollout_actions` and stay so): True -- the trees go to the device too and all iterations are ONE ops.plan_search call (select and backpropagate
         as kernels around the fused expansion's launches, nothing synchronised in between); the forest is uploaded before and
         downloaded after, so it reads as if searched on the host.  Implies the fused expansion; a model that one does not serve is a
-        ValueError."""
+        ValueError.
+        self.fused_widths (an attribute too, FUSED_WIDTHS = (32,) by default): the state-code lengths the fused expansion is offered
+        at.  A cl = 16 / 64 model takes fused=True or device_trees = True only with its width in there (else the ValueError above)."""
         device_trees = bool(self.device_trees)
         if device_trees:
             if fused is False:
                 raise ValueError('device_trees = True searches on the fused expansion: fused=False contradicts it')
-            why = self._fused_unserved(env)
+            why = self._fused_unserved(env, self.fused_widths)
             if why:
                 raise ValueError('device_trees=True needs the fused expansion, which does not serve this model: ' + why)
             fused = True
         if fused is None:
             fused = self._fused_default(env)
+        elif fused and (env.c.cl != 32 or 32 not in self.fused_widths):
+            # a width is served where the handler offers it, under fused=True as under device_trees.  (A cl = 16 / 64 model asked for
+            # with fused=True used to get as far as ops.plan_expand and its 'do not fit'; it is now refused here, by name.)
+            why = self._fused_unserved(env, self.fused_widths)
+            if why:
+                raise ValueError('fused=True asks for the fused expansion, which does not serve this model: ' + why)
         if not env.c.action_conditioned:
             raise ValueError('planning needs an action-conditioned model (rewards)')
         M, A, D, f = self.num_mcts, self.actions, self.max_rollout, self.forest
@@ -407,25 +424,33 @@ class BatchedMCTSHandler():
         return [int(np.argmax(f.Nsa[m, f.first[m, 0]:f.first[m, 0] + A])) if f.first[m, 0] >= 0 else 0 for m in range(M)]
 
     @staticmethod
-    def _fused_unserved(env):
-        """why the fused expansion (stove_plan_expand) does not serve `env`, or '' if it does"""
+    def _fused_unserved(env, widths=None):
+        """why the fused expansion (stove_plan_expand[_cl]) does not serve `env`, or '' if it does.  widths: the state-code lengths
+        offered (a handler passes its fused_widths; None: FUSED_WIDTHS)"""
         c = env.c
         p = next(env.parameters())
         if not p.is_cuda:
             return 'it is not on the GPU'
         if p.dtype != torch.float32:
             return 'its parameters are %s, not float32' % p.dtype
-        if c.cl != 32:
-            return 'its state code length is %d, not 32' % c.cl
+        widths = FUSED_WIDTHS if widths is None else tuple(widths)
+        if c.cl not in widths or c.cl not in _FUSED_LIMITS:
+            return 'its state code length is %d, not %s' % (c.cl, ' or '.join(str(w) for w in sorted(set(widths) & set(_FUSED_LIMITS))))
+        max_obj, max_app = _FUSED_LIMITS[c.cl]
+        app_dim = c.debug_appearance_dim if getattr(c, 'debug_core_appearance', False) else 0
+        if c.num_obj > max_obj:
+            return 'it has %d objects, the kernels of state code length %d take at most %d' % (c.num_obj, c.cl, max_obj)
+        if app_dim > max_app:
+            return 'its core reads %d appearance columns, the kernels of state code length %d take at most %d' % (app_dim, c.cl, max_app)
         return ''
 
     @staticmethod
     def _fused_weights(env):
-        """what stove_plan_expand reads of the model: embedding, GNN image, reward-head block"""
+        """what stove_plan_expand[_cl] reads of the model: embedding, GNN image of its state-code length, reward-head block"""
         from .. import ops
         dyn = env.dyn
         lay, h0, h1 = dyn.action_embedding_layer, dyn.reward_head0, dyn.reward_head1
-        gnn = ops.gnn_width(32).image(*[t.detach() if t is not None else None for t in dyn.kernel_params(0)[0]]).contiguous()
+        gnn = ops.gnn_width(env.c.cl).image(*[t.detach() if t is not None else None for t in dyn.kernel_params(0)[0]]).contiguous()
         rh = torch.cat([p.detach().float().reshape(-1) for p in (h0[0].weight, h0[0].bias, h0[2].weight, h0[2].bias, h1[0].weight, h1[0].bias,
                                                                   h1[2].weight, h1[2].bias, h1[4].weight, h1[4].bias)])
         return lay.weight.detach().float().contiguous(), lay.bias.detach().float().contiguous(), gnn, rh
@@ -516,13 +541,16 @@ def run_mcts_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, m
     return plan_on_model(img, model, actions, num_parallel_envs, mcts_steps, max_rollout_depth)
 
 
-def plan_on_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False):
+def plan_on_model(img, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False,
+                  fused_widths=None):
     """run_mcts_model (the reference's surface, whose parameter list stays the reference's) with the search's switches as arguments:
-    `fused` as BatchedMCTSHandler.run_mcts takes it, `device_trees` as the handler's attribute of that name."""
-    return plan_on_frames(encode_img(img), model, actions, num_parallel_envs, mcts_steps, max_rollout_depth, fused, device_trees)
+    `fused` as BatchedMCTSHandler.run_mcts takes it, `device_trees` and `fused_widths` as the handler's attributes of those names
+    (fused_widths None: FUSED_WIDTHS)."""
+    return plan_on_frames(encode_img(img), model, actions, num_parallel_envs, mcts_steps, max_rollout_depth, fused, device_trees, fused_widths)
 
 
-def plan_on_frames(x, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False):
+def plan_on_frames(x, model, actions, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False,
+                   fused_widths=None):
     """plan_on_model on frames already in the model's layout: x (envs, time, channels, width, height) float32, on any device (frames
     rendered on the model's device reach it without a host round trip)."""
     dev = next(model.parameters()).device
@@ -534,5 +562,7 @@ def plan_on_frames(x, model, actions, num_parallel_envs=100, mcts_steps=100, max
         mcts = BatchedMCTSHandler(all_mcts, apps[:, -1] if apps is not None else None, action_space=9,
                                   max_rollout_depth=max_rollout_depth)
         mcts.device_trees = device_trees
+        if fused_widths is not None:
+            mcts.fused_widths = tuple(fused_widths)
         all_actions = mcts.run_mcts(model, mcts_steps, fused=fused)
     return all_actions

@@ -72,13 +72,14 @@ def warm_up(envs):
 
 
 def play(model, envs, run_len=100, mcts_steps=100, max_rollout_depth=10, fused=None, device_trees=False, policy='mcts', keep_frames=False,
-         replicas=1):
+         replicas=1, fused_widths=None):
     """One episode of every environment.  envs: a BatchedAvoidance (host or device) or a list of AvoidanceTask (the reference's
     per-environment loop).  policy: 'mcts' plans with `mcts_steps` expansions per tree on `model` (an action-conditioned Stove);
     'random' draws one np.random.randint(9, size=M) per step and needs no model; 'env_mcts' searches the environments themselves
     (mcts_env.plan_on_envs: `replicas` trees of `mcts_steps` iterations per environment, one np.random.randint(9, size=(M replicas,
     mcts_steps, max_rollout_depth)) per step), needs no model either and looks at no frame; a list of AvoidanceTask goes through
-    BatchedAvoidance.from_tasks for the search only.  It raises ValueError for max_rollout_depth < 2, whatever run_len is.
+    BatchedAvoidance.from_tasks for the search only.  fused_widths: the state-code lengths the fused expansion is offered at (None:
+    mcts_stove.FUSED_WIDTHS), as plan_on_frames takes it.  It raises ValueError for max_rollout_depth < 2, whatever run_len is.
     -> dict(actions (run_len, M) int64, rewards (run_len, M) float64, states (run_len, M, N, 4) float64 [, frames (run_len, M, 3, res,
     res) float32 with keep_frames]), the warm-up steps not included."""
     if policy not in ('mcts', 'random', 'env_mcts'):
@@ -101,9 +102,9 @@ def play(model, envs, run_len=100, mcts_steps=100, max_rollout_depth=10, fused=N
             nxt = plan_on_envs(envs if batched else BatchedAvoidance.from_tasks(envs), mcts_steps, max_rollout_depth, replicas)
         elif batched:
             x, acts = rings.tensors()
-            nxt = plan_on_frames(x, model, acts, M, mcts_steps, max_rollout_depth, fused, device_trees)
+            nxt = plan_on_frames(x, model, acts, M, mcts_steps, max_rollout_depth, fused, device_trees, fused_widths)
         else:
-            nxt = plan_on_model(img, model, actions, M, mcts_steps, max_rollout_depth, fused, device_trees)
+            nxt = plan_on_model(img, model, actions, M, mcts_steps, max_rollout_depth, fused, device_trees, fused_widths)
         if batched:
             reward, state = rings.step(nxt)
             frame = rings.frames[:, -1]

@@ -105,12 +105,21 @@ def _plan_model(op, z_pool, app, emb_w, emb_b, gnn_params, rh_params):
     return tensors
 
 
-def _plan_fits(lib, z_pool, app, emb_w, emb_b, gnn_params, rh_params):
-    """whether the model's tensors fit z_pool's M trees of N objects and the library's parameter counts"""
+def _plan_width(z_pool):
+    """the _GnnWidth of a pool of node states (M, cap, N, cl/2 + 2), or None where no planning kernels serve its last dimension"""
+    cl = 2 * (z_pool.shape[-1] - 2) if z_pool.dim() == 4 else 0
+    return _GNN_WIDTHS.get(cl)
+
+
+def _plan_fits(lib, width, z_pool, app, emb_w, emb_b, gnn_params, rh_params):
+    """whether the model's tensors fit z_pool's M trees of N objects and the library's parameter counts at the pool's width"""
+    if width is None:
+        return False
     M, _, N = z_pool.shape[:3]
-    return (z_pool.shape[3] == 18 and tuple(emb_w.shape) == (4 * N, emb_w.shape[1]) and emb_b.numel() == 4 * N
+    rh_floats = lib.stove_reward_head_param_floats() if width.tuned else lib.stove_reward_head_param_floats_cl(width.cl)
+    return (tuple(emb_w.shape) == (4 * N, emb_w.shape[1]) and emb_b.numel() == 4 * N
             and (app is None or tuple(app.shape) == (M, N, app.shape[-1]))
-            and gnn_params.numel() == lib.stove_gnn_param_floats() and rh_params.numel() == lib.stove_reward_head_param_floats())
+            and gnn_params.numel() == width.size('stove_gnn_param_floats') and rh_params.numel() == rh_floats)
 
 
 class _ObjSpnFn(torch.autograd.Function):
@@ -986,11 +995,12 @@ def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, wan
 
 def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, depth, lim_enc, elu, consts, gamma=0.95,
                 want_rewards=False):
-    """One expansion of M search trees (stove_plan_expand, csrc/plan.hip; forward only).  z_pool (M, cap, N, 18) float32 is updated
+    """One expansion of M search trees (stove_plan_expand / stove_plan_expand_cl, csrc/plan.hip; forward only).  z_pool (M, cap, N,
+    cl/2 + 2) float32 -- 10, 18 or 34 wide: the state-code length cl is read from it -- is updated
     in place: row (m, a) rolls the mean model 1 + L steps from z_pool[m, leaf[m]] -- action a, then acts[m A + a, :] -- and the state
     after the first step lands in z_pool[m, child[m] + a].  leaf, child, len_s (M,) and acts (M A, L) are int32 device tensors; app
-    (M, N, app_dim) or None; emb_w (4 N, A), emb_b (4 N) the action embedding; gnn_params the cl = 32 image (gnn_width(32).image(...));
-    rh_params the reward head's 2785 floats; `depth` the search's maximal rollout depth D.
+    (M, N, app_dim) or None; emb_w (4 N, A), emb_b (4 N) the action embedding; gnn_params that width's image (gnn_width(cl).image(...));
+    rh_params the reward head's block at that width (721 / 2785 / 10945 floats); `depth` the search's maximal rollout depth D.
     -> q (M, A) [, r_first (M, A), r_roll (M, A, L) with want_rewards]: the reference's backpropagate value of every child."""
     lib = _lib.load()
     z_pool, app, emb_w, emb_b, gnn_params, rh_params = model = _plan_model('plan_expand', z_pool, app, emb_w, emb_b, gnn_params, rh_params)
@@ -1001,23 +1011,24 @@ def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params,
     A = emb_w.shape[1]
     L = acts.shape[-1]
     app_dim = app.shape[-1] if app is not None else 0
-    if not _plan_fits(lib, *model) or acts.numel() != M * A * L or leaf.numel() != M or child.numel() != M or len_s.numel() != M:
+    width = _plan_width(z_pool)
+    if not _plan_fits(lib, width, *model) or acts.numel() != M * A * L or leaf.numel() != M or child.numel() != M or len_s.numel() != M:
         raise ValueError('ops.plan_expand: argument shapes do not fit M = %d trees, N = %d objects, A = %d actions, L = %d' % (M, N, A, L))
     dev = z_pool.device
     with torch.cuda.device(dev):
         q = torch.empty(M, A, dtype=torch.float32, device=dev)
         r_first = torch.empty(M, A, dtype=torch.float32, device=dev) if want_rewards else None
         r_roll = torch.empty(M, A, L, dtype=torch.float32, device=dev) if want_rewards else None
-        ws = _ws(lib.stove_plan_expand_ws_bytes(M, A, L, N, app_dim), dev)
-        check(lib.stove_plan_expand(ptr(z_pool), ptr(leaf), ptr(child), ptr(len_s), ptr(app), ptr(acts), ptr(emb_w), ptr(emb_b),
-                                    ptr(gnn_params), ptr(rh_params), ptr(q), ptr(r_first), ptr(r_roll), ptr(ws), M, cap, A, L, int(depth), N,
-                                    app_dim, int(lim_enc), int(elu), *[float(c) for c in consts], float(gamma), stream()), 'stove_plan_expand')
+        ws = _ws(width.size('stove_plan_expand_ws_bytes', M, A, L, N, app_dim), dev)
+        width.call('stove_plan_expand', [ptr(z_pool), ptr(leaf), ptr(child), ptr(len_s), ptr(app), ptr(acts), ptr(emb_w), ptr(emb_b),
+                                         ptr(gnn_params), ptr(rh_params), ptr(q), ptr(r_first), ptr(r_roll), ptr(ws)], M, cap, A, L, int(depth),
+                   N, app_dim, int(lim_enc), int(elu), *[float(c) for c in consts], float(gamma), stream())
     return (q, r_first, r_roll) if want_rewards else q
 
 
 def plan_search(z_pool, arrays, app, acts, emb_w, emb_b, gnn_params, rh_params, depth, lim_enc, elu, consts, gamma=0.95, sel_trace=None):
     """A whole search of M trees with the trees on the device (stove_plan_search, csrc/plan_tree.hip; forward only): acts.shape[0]
-    iterations of select / expand / backpropagate in one C call, nothing synchronised.  z_pool (M, cap, N, 18) float32 and the trees
+    iterations of select / expand / backpropagate in one C call, nothing synchronised.  z_pool (M, cap, N, cl/2 + 2) float32 and the trees
     are updated in place.  arrays: dict of contiguous device tensors -- first, parent, depth, Ns, Nsa (M, cap) int32, Qsa (M, cap)
     float64, used, status (M,) int32, min_gap (M,) float64 (Forest.to_device makes them).  acts (R, M A, L) int32, every iteration's
     random-rollout actions; sel_trace (R, M) int32 or None receives the selected leaf per iteration; the rest as ops.plan_expand.
@@ -1028,7 +1039,7 @@ def plan_search(z_pool, arrays, app, acts, emb_w, emb_b, gnn_params, rh_params, 
     dev = z_pool.device
     _arg('plan_search', 'acts', acts, _I32, dev)
     if z_pool.dim() != 4 or acts.dim() != 3:
-        raise ValueError('ops.plan_search: z_pool must be (M, cap, N, 18) and acts (R, M A, L)')
+        raise ValueError('ops.plan_search: z_pool must be (M, cap, N, cl/2 + 2) and acts (R, M A, L)')
     M, cap, N = z_pool.shape[:3]
     A = emb_w.shape[1]
     R, L = acts.shape[0], acts.shape[-1]
@@ -1036,14 +1047,15 @@ def plan_search(z_pool, arrays, app, acts, emb_w, emb_b, gnn_params, rh_params, 
     forest, _ = _forest('plan_search', arrays, M, dev, cap)
     if sel_trace is not None:
         _arg('plan_search', 'sel_trace', sel_trace, _I32, dev, (R, M), 'forest')
-    if not _plan_fits(lib, *model) or tuple(acts.shape) != (R, M * A, L):
+    width = _plan_width(z_pool)
+    if not _plan_fits(lib, width, *model) or tuple(acts.shape) != (R, M * A, L):
         raise ValueError('ops.plan_search: argument shapes do not fit M = %d trees, N = %d objects, A = %d actions, L = %d' % (M, N, A, L))
     with torch.cuda.device(dev):
         action = torch.empty(M, dtype=torch.int32, device=dev)
-        ws = _ws(lib.stove_plan_search_ws_bytes(M, A, L, N, app_dim), dev)
-        check(lib.stove_plan_search(ptr(z_pool), *forest, ptr(action), ptr(sel_trace), ptr(app), ptr(acts), ptr(emb_w), ptr(emb_b),
-                                    ptr(gnn_params), ptr(rh_params), ptr(ws), M, cap, A, L, int(depth), N, app_dim, int(lim_enc), int(elu),
-                                    *[float(c) for c in consts], float(gamma), R, stream()), 'stove_plan_search')
+        ws = _ws(width.size('stove_plan_search_ws_bytes', M, A, L, N, app_dim), dev)
+        width.call('stove_plan_search', [ptr(z_pool), *forest, ptr(action), ptr(sel_trace), ptr(app), ptr(acts), ptr(emb_w), ptr(emb_b),
+                                         ptr(gnn_params), ptr(rh_params), ptr(ws)], M, cap, A, L, int(depth), N, app_dim, int(lim_enc), int(elu),
+                   *[float(c) for c in consts], float(gamma), R, stream())
     return action
 
 

@@ -2,7 +2,7 @@
 """Play avoidance episodes with the tree search on a trained world model (reference scripts/run_mcts.py: main_mcts_model).
 
     python tools/run_mcts.py RUN_NAME CHECKPOINT_DIR [--envs 100 --mcts-steps 100 --depth 10 --run-len 100 --no-gifs]
-                             [--device-envs] [--device-trees] [--policy random | env_mcts] [--replicas 1]
+                             [--device-envs] [--device-trees] [--fused-widths 16,32,64] [--policy random | env_mcts] [--replicas 1]
 
 main_mcts_model restores the model (stove_amd.main.restore_model), builds the reference's environments -- BillardsEnv(n=3, hw=10,
 r=1., res=32, seed=s) under AvoidanceTask(action_force=0.6), s = 0 .. envs - 1 -- and runs stove_amd.mcts.play.play on them:
@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 
 def main_mcts_model(run_name, restore_point, save_gifs=True, num_parallel_envs=100, mcts_steps=100, max_rollout_depth=10, run_len=100,
-                    device_envs=False, device_trees=False, policy='mcts', model=None, out_dir='.', replicas=1):
+                    device_envs=False, device_trees=False, policy='mcts', model=None, out_dir='.', replicas=1, fused_widths=None):
     """the reference's parameters, then the switches of this port (all off by default) -> the list of rewards"""
     from stove_amd.envs import envs
     from stove_amd.envs.batched import BatchedAvoidance
@@ -41,7 +41,7 @@ def main_mcts_model(run_name, restore_point, save_gifs=True, num_parallel_envs=1
         all_envs = BatchedAvoidance.from_tasks(all_envs, device=dev)
     with torch.no_grad():
         out = play(model, all_envs, run_len=run_len, mcts_steps=mcts_steps, max_rollout_depth=max_rollout_depth, device_trees=device_trees,
-                   policy=policy, keep_frames=save_gifs, replicas=replicas)
+                   policy=policy, keep_frames=save_gifs, replicas=replicas, fused_widths=fused_widths)
     results = [float(r) for r in out['rewards'].reshape(-1)]
     if save_gifs and run_len:
         clips = (255 * np.transpose(out['frames'], (1, 0, 2, 3, 4))).astype(np.uint8)            # (envs, run_len, 3, res, res)
@@ -75,6 +75,8 @@ def main():
     ap.add_argument('--no-gifs', action='store_true')
     ap.add_argument('--device-envs', action='store_true', help='step and render the environments on the device (off by default)')
     ap.add_argument('--device-trees', action='store_true', help='keep the search trees on the device (off by default)')
+    ap.add_argument('--fused-widths', default=None, metavar='16,32,64', type=lambda v: tuple(int(w) for w in v.split(',')),
+                    help='state-code lengths the fused expansion (and with it --device-trees) is offered at (default: 32 alone)')
     ap.add_argument('--policy', choices=('mcts', 'random', 'env_mcts'), default='mcts')
     ap.add_argument('--replicas', type=int, default=1, help='independent trees per environment with --policy env_mcts')
     ap.add_argument('--out-dir', default='.')
@@ -83,7 +85,8 @@ def main():
         ap.error('planning on a model needs a checkpoint: give restore_point (or --policy random / env_mcts)')
     results = main_mcts_model(args.run_name, args.restore_point, save_gifs=not args.no_gifs, num_parallel_envs=args.envs,
                               mcts_steps=args.mcts_steps, max_rollout_depth=args.depth, run_len=args.run_len, device_envs=args.device_envs,
-                              device_trees=args.device_trees, policy=args.policy, out_dir=args.out_dir, replicas=args.replicas)
+                              device_trees=args.device_trees, policy=args.policy, out_dir=args.out_dir, replicas=args.replicas,
+                              fused_widths=args.fused_widths)
     print('mean reward per step %.4f (std %.4f) over %d environment steps' % (np.mean(results), np.std(results), len(results)))
 
 
