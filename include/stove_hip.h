@@ -685,6 +685,12 @@ int stove_elbo_bwd(const float* zs, const float* mean, const float* std_, const 
 /* debug aid of the measurement tools: device buffer of 64 int64 cycle stamps ([4 waves][16 phases]) written by
  * workgroup 0 of the small-graph time loops in their last step; NULL (default) switches it off. */
 void stove_debug_set_stamps(long long* device_buffer);
+/* debug aid of the tests: the small-graph recursion (2 <= N <= 6) of the following stove_dynloop_fwd / _bwd calls runs the steps
+ * [ts0, ts1) only, all tensors keeping their (B, Ts, ...) layout.  Forward: a piece with ts0 > 0 starts from the state the previous
+ * piece left in z.  Backward: pieces from the last to the first over the same act and ws; `carry` (B, N, 18 floats on the device)
+ * takes the gradient from step ts0 into the state before it (written when ts0 > 0, read when ts1 < Ts); the piece with ts0 == 0
+ * writes dz1 and g_params.  ts1 <= 0 (default) = the whole range; a piece outside [0, Ts) makes the calls fail. */
+void stove_debug_set_piece(int ts0, int ts1, float* carry);
 
 /* ---- flat parameter arena.  When all model parameters are views into ONE fp32 buffer (and their gradients
  * into one gradient buffer, which is also the data-parallel all-reduce bucket), the SPN tables and the GNN

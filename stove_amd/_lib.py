@@ -125,6 +125,7 @@ def _declare(lib):
         'stove_spn_bake': (I, [P, A, P, P, P, P, P, P]),
         'stove_spn_bake_bwd': (I, [P, A, G, P, P]),
         'stove_debug_set_stamps': (None, [P]),
+        'stove_debug_set_piece': (None, [I, I, P]),
         'stove_glimpse_mean': (I, [P, P, P, I, I, I, P]),
         'stove_objspn_mpe': (I, [T, P, P, P, P, P, I, P]),
         'stove_render_frames': (I, [P, P, I, P, P, I, I, P]),

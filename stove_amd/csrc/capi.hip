@@ -976,7 +976,24 @@ size_t stove_dynloop_act_floats(int B, int Ts, int N) {
 
 // The small-graph kernels keep the piece interface of the round-3 pipelining experiment (the steps [ts0, ts1), the gradient carried
 // between pieces: docs/experiments/r06_pipeline_pieces_removed.patch) -- taking it out changes the device code of the most
-// latency-sensitive kernels, a measured change of its own.  The entry points always run the whole range: 0, Ts, no carry.
+// latency-sensitive kernels, a measured change of its own.  The entry points run the whole range: 0, Ts, no carry -- unless a test
+// has set a piece with stove_debug_set_piece: then the small-graph launches run the steps [ts0, ts1) of the Ts the tensors are laid
+// out for.  Forward: a piece with ts0 > 0 starts from the state the previous piece left in z.  Backward: pieces are called from the
+// last to the first over the same act / ws buffers; the gradient that flows from step ts0 into the state before it goes through
+// `carry` (B, N, 18 floats on the device; written when ts0 > 0, read when ts1 < Ts); the piece with ts0 == 0 writes dz1 and runs the
+// weight-gradient pass over the streams of ALL steps.  ts1 <= 0 (default) switches it off.
+static int g_sm_ts0 = 0, g_sm_ts1 = 0;
+static float* g_sm_carry = nullptr;
+void stove_debug_set_piece(int ts0, int ts1, float* carry) {
+  g_sm_ts0 = ts0;
+  g_sm_ts1 = ts1;
+  g_sm_carry = carry;
+}
+static bool sm_piece(int Ts, int& p0, int& p1) {      // false: a piece is set that is not a range of steps of these tensors
+  p0 = g_sm_ts1 > 0 ? g_sm_ts0 : 0;
+  p1 = g_sm_ts1 > 0 ? g_sm_ts1 : Ts;
+  return p0 >= 0 && p0 < p1 && p1 <= Ts;
+}
 int stove_dynloop_fwd(const float* z1, const float* zsup, const float* zsstd, const float* eps, const float* extra,
                       const float* params, float* z, float* zdyn, float* zdstd, float* mean, float* std_, float* pred, float* act,
                       int B, int Ts, int N, int sin_dim, int lim_enc, int elu, float pos_var, float vel_std, float lat_std,
@@ -985,11 +1002,13 @@ int stove_dynloop_fwd(const float* z1, const float* zsup, const float* zsstd, co
   if (B == 0 || Ts == 0) return 0;
   LoopConst kc{pos_var, vel_std, lat_std};
   if (small_graph(N)) {      // small graphs: (half-)wave-per-node-row formulation, two barriers per step (gnn_small.hip)
+    int p0, p1;
+    if (!sm_piece(Ts, p0, p1)) return (int)hipErrorInvalidValue;
     auto launch = [&](auto save, auto nmx, auto e, auto nt, auto stamp) {
       constexpr int NMX = decltype(nmx)::value;
       return STOVE_LAUNCH_LDS((dyn_loop_fwd_small_k<decltype(save)::value, NMX, decltype(e)::value, decltype(nt)::value, decltype(stamp)::value>),
                               dim3(B), dim3(64 * kSmWaves), SmShape<NMX>::kLdsFloats * sizeof(float), (hipStream_t)stream, z1, zsup, zsstd, eps,
-                              extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, elu, kc, g_sm_stamps, 0, Ts);
+                              extra, params, z, zdyn, zdstd, mean, std_, pred, act, B, Ts, N, sin_dim, lim_enc, elu, kc, g_sm_stamps, p0, p1);
     };
     if (g_sm_stamps != nullptr && act != nullptr && !elu && N == 3)      // tools/loop_stamps.py: the one instantiation that stamps its phases
       return launch(Int<2>{}, Int<4>{}, std::false_type{}, Int<3>{}, std::true_type{});
@@ -1041,6 +1060,9 @@ int stove_dynloop_bwd_overlap(const float* z1, const float* zsup, const float* z
     // small graphs: T-serial data-gradient chain (gnn_small_bwd.hip), then the weight gradients as a throughput pass
     float* gpart = (float*)ws;
     float* dy = gpart + (size_t)B * kGnnGrads;
+    int p0, p1;
+    if (!sm_piece(Ts, p0, p1) || ((p0 > 0 || p1 < Ts) && g_sm_carry == nullptr)) return (int)hipErrorInvalidValue;
+    float* carry = g_sm_carry;
     // HEAD: the instantiations for the gradients the training step hands over; only three and six objects have them
     const bool head = dz != nullptr && dzdyn != nullptr && dmean != nullptr && dstd != nullptr && dpred == nullptr && sin_dim == 16 && lim_enc == 2;
     auto launch = [&](auto nmx, auto e, auto nt, auto hd, auto stamp) {
@@ -1048,7 +1070,7 @@ int stove_dynloop_bwd_overlap(const float* z1, const float* zsup, const float* z
       return STOVE_LAUNCH_LDS((dyn_loop_bwd_small_k<NMX, decltype(e)::value, decltype(nt)::value, decltype(hd)::value, decltype(stamp)::value>),
                               dim3(B), dim3(64 * kSmWaves), smb_lds_floats<NMX>() * sizeof(float), st, zsup, zsstd, eps, params,
                               const_cast<float*>(act), dz, dzdyn, dmean, dstd, dpred, dz1, dzsup, dzsstd, dextra, dy, B, Ts, N, sin_dim, lim_enc,
-                              elu, kc, g_sm_stamps, 0, Ts, (float*)nullptr);
+                              elu, kc, g_sm_stamps, p0, p1, carry);
     };
     int rc;
     if (g_sm_stamps != nullptr && !elu && N == 3 && head) {       // tools/loop_stamps.py: the one instantiation that stamps its phases
@@ -1067,6 +1089,7 @@ int stove_dynloop_bwd_overlap(const float* z1, const float* zsup, const float* z
       });
     }
     if (rc) return rc;
+    if (p0 > 0) return 0;                   // a piece that is not the first: the streams of the steps before it are still to come
     STOVE_TRY(stream_after(sp, st));        // the weight-gradient pass reads the dY streams; it only feeds the optimiser (second stream)
     rc = STOVE_LAUNCH_LDS(gnn_dw_small_k, dim3(B), dim3(256), kDwLdsFloats * sizeof(float), sp, act, (const float*)dy, gpart, B, Ts, N);
     if (rc) return rc;

@@ -617,12 +617,28 @@ __device__ __forceinline__ void sm_edge_phase_mfma(const SmLds& L, const SmCfg& 
   sm_edge_chain<SAVE, ET>(L, cf, act, el, pre, cw, wv == 2 ? 1 : 0);
 }
 
+// Global memory and the serial chain.  On gfx950 loads and stores count on ONE in-order counter, and a wait for a load that follows a
+// branch around a store (the owner-lane stores, the per-wave roles) can only be a full one: a node wave that stores in P1 / P4 and
+// consumes its step inputs in the epilogue then waits for the acknowledgement of stores it has just issued, several times a step.
+// The kernels built for up to four objects (DEFER) therefore keep a node wave's loads and stores apart: the step's inputs are
+// loaded at the loop top, one full wait stands at the start of the epilogue -- a whole step behind the loads and a whole P4 behind
+// the edge phase's stream stores, so that it finds nothing outstanding -- and EVERY store of the node rows (saved activations of
+// P1 and P4 included, out of registers) follows the epilogue's arithmetic.  The wait is written out (sm_wait_vm): the compiler then
+// knows of nothing pending at the loop's back edge and puts no wait of its own at the loop top or in P1, behind those stores.
+__device__ __forceinline__ void sm_wait_vm() { __builtin_amdgcn_s_waitcnt(0x0f70); }      // vmcnt(0), nothing else
+// what P1 / P4 of a node row leave for the deferred stores (lane o: element o of the row)
+struct SmNodeOut {
+  float S, F1, F2, F3, O1;
+};
+
 // One GNN step.  The lane's node row is r = wave (+ 4 for the upper half-wave of a two-rows-per-wave kernel); lane k of the half
 // holds s_in[r][k] in `sinv` (zero beyond sin_dim) and gets RES[o] / PRED[o] of that row back in lane o.  With one row per wave
 // the upper half mirrors the lower.  SAVE: write the activation block (act.* valid).
-template <bool SAVE, int NMX>
+// DEFER: the node rows' saved activations are not stored here but handed back (S, F1, F2, F3, O1 in `no`; SIN, PRED and RES the
+// caller has anyway).
+template <bool SAVE, int NMX, bool DEFER = false>
 __device__ __forceinline__ void sm_step(const SmLds& L, const SmCfg& cf, float sinv, const SmAct& act, float& res_out, float& pred_out,
-                                        const SmEdgeLane (&el)[SmShape<NMX>::ET], const SmChainW& cw) {
+                                        const SmEdgeLane (&el)[SmShape<NMX>::ET], const SmChainW& cw, SmNodeOut& no) {
   constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET;
   constexpr bool HK = RP == 1;                                      // one row per wave: the half-waves split K (sm_wload / sm_dotw)
   __shared__ __attribute__((aligned(16))) float sbuf[NMX][32];     // S back as broadcast float4 reads (see sm_dotw)
@@ -664,7 +680,7 @@ __device__ __forceinline__ void sm_step(const SmLds& L, const SmCfg& cf, float s
     S = (o < cf.lim_enc) ? sinv : e + benc;
     if (own) {
       sbuf[r][o] = S;
-      if (SAVE) {
+      if (SAVE && !DEFER) {
         act.SIN[r * 32 + o] = sinv;
         act.S[r * 32 + o] = S;
       }
@@ -755,7 +771,8 @@ __device__ __forceinline__ void sm_step(const SmLds& L, const SmCfg& cf, float s
     sm_stamp(cf, 14);
     const float RES = sm_dotw<8, HK>(wb, O1) + bo1 + O1;
     sm_stamp(cf, 15);
-    if (SAVE && own) {
+    if (DEFER) no = SmNodeOut{S, F1, F2, F3, O1};
+    if (SAVE && !DEFER && own) {
       act.PRED[r * 32 + o] = pred;
       act.F1[r * 32 + o] = F1;
       act.F2[r * 32 + o] = F2;
@@ -788,6 +805,7 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_fwd_small_k(
   // steps [ts0, ts1) of the Ts the tensors are laid out for: a caller that pipelines the recursion against the scene likelihood of
   // the frames already inferred runs it in pieces; a piece that does not start at 0 takes the state the previous one left in z
   constexpr bool SAVE = SAVEM != 0;
+  constexpr bool DEFER = NMX == 4;      // loads and stores of the node rows kept apart (see sm_wait_vm)
   constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET;
   static_assert(SAVEM == 0 || SAVEM == 2, "no saved activations, or the streams layout");
   static_assert(NT <= NMX, "object count beyond what the kernel is built for");
@@ -817,9 +835,10 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_fwd_small_k(
   WG_SYNC();
   SmChainW cw;
   sm_chain_wbuild(L, cw);       // the edge chains' weight fragments: registers, for all time steps
+  if (DEFER) sm_wait_vm();      // the first step's inputs: nothing pending when the loop is entered
   for (int ts = ts0; ts < ts1; ++ts) {
     const size_t o = ((size_t)b * Ts + ts) * N + r;
-    // this step's epilogue inputs and the next step's extra inputs: issued now, consumed ~2 us later
+    // this step's epilogue inputs and the next step's extra inputs: issued now, consumed a step later
     float ep = 0.0f, ms = 0.0f, ss = 1.0f, xnext = 0.0f;
     if (row) {
       if (l < 16) ep = eps[o * 18 + 2 + l];
@@ -837,8 +856,63 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_fwd_small_k(
     if (SAVE) a = sm_act2(act + (size_t)b * sm_act2_floats(N, Ts), N, Ts, ts);
     cf.stamps = (ts == ts1 - 1) ? stamps : nullptr;
     float res = 0.0f, prd = 0.0f;
-    sm_step<SAVE, NMX>(L, cf, sinv, a, res, prd, el, cw);
-    if (wv < N) {
+    SmNodeOut no{};
+    sm_step<SAVE, NMX, DEFER>(L, cf, sinv, a, res, prd, el, cw, no);
+    if (DEFER) sm_wait_vm();      // every wave: the step's loads, and stores that are a phase old
+    if (DEFER && wv < N) {
+      // epilogue (stove.py:103-170 + constrain_z_dyn): lane d < 16 owns state dim d, lanes 16/17 the two scale dims.  All of the
+      // arithmetic first, then the stores.
+      const float res_s = from_xor16(res);      // RES[16 + d] for d < 16
+      float zv, zd = 0.0f, sd = 0.0f, mu, sg;
+      if (l < 16) {
+        const int d = l;
+        // v_rcp_f32 / v_rsq_f32 (1 ulp) for the two sigmoids' and the product-of-Gaussians' divisions: four IEEE divisions and a
+        // square root were ~40 instructions of the step's serial tail (the backward's epilogue has had them since round 2)
+        const float m = 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-res)) - 1.0f;
+        sd = std_scale(d, kc) * __builtin_amdgcn_rcpf(1.0f + __expf(-res_s));
+        zd = m + (d < 2 ? sinv : 0.0f);
+        if (d < 4) {
+          const float sd2 = sd * sd, ss2 = ss * ss, D = sd2 + ss2;
+          mu = (ss2 * zd + sd2 * ms) * __builtin_amdgcn_rcpf(D);
+          sg = sd * ss * __builtin_amdgcn_rsqf(D);
+        } else {
+          mu = zd;
+          sg = sd;
+        }
+        zv = fmaf(sg, ep, mu);
+      } else {
+        zv = xnext;                                   // becomes s_in[l] of the next step (0 beyond sin_dim)
+        mu = ms;
+        sg = ss;
+      }
+      if (own) {
+        if (l < 16) {
+          zdyn[o * 16 + l] = zd;
+          zdstd[o * 16 + l] = sd;
+          z[o * 18 + 2 + l] = zv;
+          mean[o * 18 + 2 + l] = mu;
+          stdv[o * 18 + 2 + l] = sg;
+        } else if (l < 18) {
+          const int q = l - 16;
+          z[o * 18 + q] = fmaf(ss, ep, ms);
+          mean[o * 18 + q] = mu;
+          stdv[o * 18 + q] = sg;
+        }
+        if (pred != nullptr) pred[o * 32 + l] = prd;
+        if (SAVE) {
+          a.SIN[r * 32 + l] = sinv;
+          a.S[r * 32 + l] = no.S;
+          a.PRED[r * 32 + l] = prd;
+          a.F1[r * 32 + l] = no.F1;
+          a.F2[r * 32 + l] = no.F2;
+          a.F3[r * 32 + l] = no.F3;
+          a.O1[r * 32 + l] = no.O1;
+          a.RES[r * 32 + l] = res;
+        }
+      }
+      sinv = zv;
+    }
+    if (!DEFER && wv < N) {      // five and six objects: every store where its value is formed
       // epilogue (stove.py:103-170 + constrain_z_dyn): lane d < 16 owns state dim d, lanes 16/17 the two scale dims
       const float res_s = from_xor16(res);      // RES[16 + d] for d < 16
       float zv;
@@ -891,6 +965,7 @@ __global__ __launch_bounds__(64 * kSmWaves) void rollout_fwd_small_k(const float
                                                            float* __restrict__ zstd, float* __restrict__ pred,
                                                            int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, LoopConst kc) {
   constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET;
+  constexpr bool DEFER = NMX == 4;      // loads ahead of the stores, one written-out wait between them (see sm_wait_vm)
   static_assert(NT <= NMX, "object count beyond what the kernel is built for");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const SmLds L = sm_carve<NMX>(lds);
@@ -917,14 +992,37 @@ __global__ __launch_bounds__(64 * kSmWaves) void rollout_fwd_small_k(const float
   WG_SYNC();
   SmChainW cw;
   sm_chain_wbuild(L, cw);
+  if (DEFER) sm_wait_vm();
   for (int t = 0; t < num; ++t) {
     const size_t o = ((size_t)b * num + t) * N + r;
     float xnext = 0.0f;
     if (row && l >= 16 && l < sin_dim && t + 1 < num) xnext = extra[(((size_t)b * A + ((t + 1) % A)) * N + r) * E + (l - 16)];
     SmAct a{};
     float res = 0.0f, prd = 0.0f;
-    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw);
-    if (wv < N) {
+    SmNodeOut no{};
+    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw, no);
+    if (DEFER) sm_wait_vm();      // the next step's extra inputs, before the first store of this one
+    if (DEFER && wv < N) {      // all of the arithmetic first, then the stores
+      const float res_s = from_xor16(res);
+      float zv, sd = 0.0f;
+      if (l < 16) {
+        zv = 2.0f * sigmoidf_(res) - 1.0f + (l < 2 ? sinv : 0.0f);
+        if (zstd != nullptr) sd = std_scale(l, kc) * sigmoidf_(res_s);
+      } else {
+        zv = xnext;
+      }
+      if (own) {
+        if (l < 16) {
+          z_pred[o * 18 + 2 + l] = zv;
+          if (zstd != nullptr) zstd[o * 16 + l] = sd;
+        } else if (l < 18) {
+          z_pred[o * 18 + (l - 16)] = scale;
+        }
+        if (pred != nullptr) pred[o * 32 + l] = prd;
+      }
+      sinv = zv;
+    }
+    if (!DEFER && wv < N) {
       const float res_s = from_xor16(res);
       float zv;
       if (l < 16) {
@@ -956,6 +1054,7 @@ __global__ __launch_bounds__(64 * kSmWaves) void rollout_sample_fwd_small_k(cons
                                                                   float* __restrict__ zstd, float* __restrict__ pred,
                                                                   int B, int num, int A, int N, int sin_dim, int lim_enc, int elu, LoopConst kc) {
   constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET;
+  constexpr bool DEFER = NMX == 4;      // loads ahead of the stores, one written-out wait between them (see sm_wait_vm)
   static_assert(NT <= NMX, "object count beyond what the kernel is built for");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const SmLds L = sm_carve<NMX>(lds);
@@ -982,6 +1081,7 @@ __global__ __launch_bounds__(64 * kSmWaves) void rollout_sample_fwd_small_k(cons
   WG_SYNC();
   SmChainW cw;
   sm_chain_wbuild(L, cw);
+  if (DEFER) sm_wait_vm();
   for (int t = 0; t < num; ++t) {
     const size_t o = ((size_t)b * num + t) * N + r;
     float xnext = 0.0f;
@@ -989,8 +1089,33 @@ __global__ __launch_bounds__(64 * kSmWaves) void rollout_sample_fwd_small_k(cons
     const float ep = (row && l < 16) ? eps[o * 16 + l] : 0.0f;       // ahead of the step, off its serial chain
     SmAct a{};
     float res = 0.0f, prd = 0.0f;
-    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw);
-    if (wv < N) {
+    SmNodeOut no{};
+    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw, no);
+    if (DEFER) sm_wait_vm();      // the step's draw and the next step's extra inputs, before the first store of this one
+    if (DEFER && wv < N) {      // all of the arithmetic first, then the stores
+      const float res_s = from_xor16(res);
+      float zv, sd = 0.0f, lq = 0.0f;
+      if (l < 16) {
+        const float mean = 2.0f * sigmoidf_(res) - 1.0f + (l < 2 ? sinv : 0.0f);
+        sd = std_scale(l, kc) * sigmoidf_(res_s);
+        zv = fmaf(sd, ep, mean);
+        lq = sample_log_q(ep, sd);
+      } else {
+        zv = xnext;
+      }
+      if (own) {
+        if (l < 16) {
+          z_pred[o * 18 + 2 + l] = zv;
+          log_q[o * 16 + l] = lq;
+          if (zstd != nullptr) zstd[o * 16 + l] = sd;
+        } else if (l < 18) {
+          z_pred[o * 18 + (l - 16)] = scale;
+        }
+        if (pred != nullptr) pred[o * 32 + l] = prd;
+      }
+      sinv = zv;
+    }
+    if (!DEFER && wv < N) {
       const float res_s = from_xor16(res);
       float zv;
       if (l < 16) {

@@ -251,6 +251,7 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
   // into the state before it leaves through `carry` (B, N, 18; layout of dz1) when ts0 > 0 and enters there when ts1 < Ts.
   constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET, NE4 = (SmShape<NMX>::NE + 3) & ~3;
   constexpr bool HK = RP == 1;       // one node row per wave: the half-waves split K of the row-per-lane dots (gnn_small.hip sm_dotw)
+  constexpr bool DEFER = NMX == 4;   // the node rows' stores at the end of the step, apart from its loads (gnn_small.hip sm_wait_vm)
   static_assert(NT <= NMX, "object count beyond what the kernel is built for");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // the chain is issue-latency bound: where another kernel's wave shares the SIMD (the table gradients that run underneath,
@@ -297,6 +298,7 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
   WG_SYNC();
   SmBChainW cw;
   smb_chain_wbuild(L, cw);      // the edge chains' transposed weights as half-piece fragments: registers, for all time steps
+  if (DEFER) sm_wait_vm();      // the last step's inputs: nothing pending when the loop is entered
   for (int ts = ts1 - 1; ts >= ts0; --ts) {
     cf.stamps = (ts == ts0 + 1 && stamps != nullptr) ? stamps + 64 : nullptr;       // second half of the debug buffer
     sm_stamp(cf, 0);
@@ -316,6 +318,9 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
     }
     float* pos = L.POS + (ts & 1) * (NMX * 4);
     float dS_o0 = 0.0f, dSD = 0.0f, pc = 0.0f;
+    // DEFER: what the node row stores, kept in registers until the end of the step (lane l: element l of the row)
+    float gsup = 0.0f, gsstd = 0.0f, q_dres = 0.0f, q_db = 0.0f, q_dF3 = 0.0f, q_du = 0.0f, q_dbf = 0.0f;
+    float q_dp[4] = {0.0f, 0.0f, 0.0f, 0.0f}, q_dH1p = 0.0f, q_dEnc = 0.0f, q_dsin = 0.0f;
     // ---- Q4: node rows: epilogue, output and affector MLPs backwards ----------------------------------------------
     if (node) {
       SmW<8> wa = sm_wload<8, HK>(L.W + W_O1, 32, l), wb;
@@ -342,7 +347,14 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
           const float rD = rsqrtf(D);
           gzd += gmu * ss2 * iD;
           gsd = gmu * (ms - mu) * iD * 2.0f * sd + gsg * ss * ss2 * iD * rD;
-          if (own) {
+          if (DEFER) {
+            // gsstd: two rounded products and a plain sum, as this gradient has always been formed (inside the owner lanes' block
+            // the two product chains ran as packed multiplies); left to the compiler next to gsd, the sum contracts into an FMA
+            // and the bits move
+#pragma clang fp contract(off)
+            gsup = gmu * sd2 * iD;
+            gsstd = gmu * (zd - mu) * iD * 2.0f * ss + gsg * sd * sd2 * iD * rD;
+          } else if (own) {      // (five and six objects: as it stands, the compiler's choice of contraction not pinned)
             dzsup[o * 6 + 2 + d] = gmu * sd2 * iD;
             dzsstd[o * 6 + 2 + d] = gmu * (zd - mu) * iD * 2.0f * ss + gsg * sd * sd2 * iD * rD;
           }
@@ -353,6 +365,9 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
         if (d < 2) pc = gzd;                              // z_dyn position = previous position + delta
         lo = gzd * 0.5f * (1.0f - m * m);
         hi = gsd * sd * (1.0f - sg_hi);
+      } else if (DEFER) {
+        gsup = gmu;
+        gsstd = gsg;
       } else if (l < 18 && own) {
         dzsup[o * 6 + (l - 16)] = gmu;
         dzsstd[o * 6 + (l - 16)] = gsg;
@@ -378,7 +393,10 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
       const float dbf = (sm_dotw<8, HK>(wa, du) + dF2) * (1.0f - cur.F1 * cur.F1);
       // b5. affector.0
       dSD = sm_dotw<8, HK>(wb, dbf) + cur.dpred;
-      if (own) {
+      if (DEFER) {
+        if (own) L.DSD[r * 32 + l] = dSD;
+        q_dres = dres; q_db = db; q_dF3 = dF3; q_du = du; q_dbf = dbf;
+      } else if (own) {
         L.DSD[r * 32 + l] = dSD;
         g.dRES[r * 32 + l] = dres;
         g.dO1[r * 32 + l] = db;
@@ -391,6 +409,9 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
     sm_stamp(cf, 1);
     WG_SYNC();
     sm_stamp(cf, 2);
+    // every wave, not only the chains that consume `ein`: loads a whole Q4 old, no store in front of them.  Without it the
+    // compiler waits for `ein` again in Q2, where a node wave that is also a chain has just issued the chain's stream stores.
+    if (DEFER) sm_wait_vm();
     // ---- Q3: edges as the columns of the relation chain (wave 3) / the attention chain (wave 2), all column tiles together
     smb_edge_phase_mfma<ET>(L, el, ein, g, elu, NE4, cw);
     sm_stamp(cf, 3);
@@ -419,7 +440,8 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           dpr[lane + 64 * gq] = dp[gq];
-          g.dP[rw * 256 + lane + 64 * gq] = dp[gq];
+          if (DEFER) q_dp[gq] = dp[gq];      // (one row per wave: rw = wv)
+          else g.dP[rw * 256 + lane + 64 * gq] = dp[gq];
         }
         sm_stamp(cf, 7);
         // dS from the edge layers: dP (256) W_ef (256 x 32); the two half-waves split the 256 terms
@@ -463,12 +485,43 @@ __global__ __launch_bounds__(64 * kSmWaves) void dyn_loop_bwd_small_k(
       const float dEnc = raw ? 0.0f : tot;
       // b13. encoder
       const float dsin = sm_dotw<8, HK>(wa, dEnc) + (raw ? tot : 0.0f);
-      if (own) {
+      if (DEFER) {
+        q_dH1p = dH1p; q_dEnc = dEnc; q_dsin = dsin;
+      } else if (own) {
         g.dH1p[r * 32 + l] = dH1p;
         g.dEnc[r * 32 + l] = dEnc;
         if (l >= 16 && l < sin_dim) dextra[o * E + (l - 16)] = dsin;
       }
       car = (l < 16) ? dsin + (l < 2 ? pc : 0.0f) : 0.0f;
+    }
+    if (DEFER) {
+      // The node rows' stores of the whole step, behind its arithmetic and behind ONE written-out full wait (sm_wait_vm,
+      // gnn_small.hip): the wait finds the next step's inputs (loaded at the loop top, a step ago) and the edge phase's stream
+      // stores (a whole Q2 ago) long returned, and the compiler, knowing of nothing pending at the back edge, puts no wait of
+      // its own behind these stores at the loop top, in front of the edge phase's operands or in Q2.
+      sm_wait_vm();
+      if (node && own) {
+        if (l < 4) {
+          dzsup[o * 6 + 2 + l] = gsup;
+          dzsstd[o * 6 + 2 + l] = gsstd;
+        } else if (l >= 16 && l < 18) {
+          dzsup[o * 6 + (l - 16)] = gsup;
+          dzsstd[o * 6 + (l - 16)] = gsstd;
+        }
+        g.dRES[r * 32 + l] = q_dres;
+        g.dO1[r * 32 + l] = q_db;
+        g.dF3[r * 32 + l] = q_dF3;
+        g.duF1[r * 32 + l] = q_du;
+        g.dF1p[r * 32 + l] = q_dbf;
+        g.dSD[r * 32 + l] = dSD;
+        g.dH1p[r * 32 + l] = q_dH1p;
+        g.dEnc[r * 32 + l] = q_dEnc;
+        if (l >= 16 && l < sin_dim) dextra[o * E + (l - 16)] = q_dsin;
+      }
+      if (node) {
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) g.dP[wv * 256 + lane + 64 * gq] = q_dp[gq];
+      }
     }
     sm_stamp(cf, 5);
   }

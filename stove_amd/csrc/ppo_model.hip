@@ -198,7 +198,8 @@ __global__ __launch_bounds__(64 * kSmWaves) void ppo_collect_model_k(
     const size_t o = ((size_t)b * S + t) * N + r;
     SmAct a{};
     float res = 0.0f, prd = 0.0f;
-    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw);
+    SmNodeOut no{};
+    sm_step<false, NMX>(L, cf, sinv, a, res, prd, el, cw, no);
     if (wv < N) {
       float zv = 0.0f;
       if (l < 16) {
