@@ -633,6 +633,26 @@ int stove_plan_search_cl(float* z_pool, int* first, int* parent, int* depth, int
                          int cl, int M, int cap, int A, int L, int D, int N, int app_dim, int lim_enc, int elu,
                          float pos_var, float vel_std, float lat_std, float gamma, int R, void* stream);
 
+/* ---- The model-based PPO arm at state-code lengths other than 32 (csrc/ppo_model_cl.hip): stove_ppo_collect_model with every width
+ * derived from cl = 16 or 64 -- z0 (B, N, cl/2 + 2), z_pred (B, S, N, cl/2 + 2), pred (B, S, N, cl) (optional); gnn_params the
+ * stove_gnn_param_floats_cl(cl) image, rh_params the stove_reward_head_param_floats_cl(cl) block; everything else as there.  One
+ * workgroup of 256 threads per trajectory, laid out as the rollout of stove_rollout_fwd_cl with one sequence per workgroup, every
+ * object count 1 <= N <= 6 in the same kernel; a node's input row is [state cl/2 | action embedding 4 | appearance], so
+ * app_dim <= cl/2 - 4 (4 at cl = 16, 28 at cl = 64).  Per step: obs, values, actions, logp exactly as stove_ppo_collect_model computes
+ * them (the policy reads columns 2 .. 5 of a state row at every width); z_pred[b][s], pred[b][s]: the bits of stove_rollout_fwd_cl with
+ * num = A = S on the extra rows [embedding column of the action + bias | app]; rewards[b][s] = r - 1.0f with r the bits of
+ * stove_plan_expand_cl's r_first for that state and action.  next_value, returns, status (0 / 3) and what a trajectory that stops
+ * leaves unwritten: as there.  One launch on `stream`, no synchronisation (the call can be captured), no atomics, deterministic.
+ * cl other than 16 or 64 (32 included: it has its own entry point), a NULL required array, B < 0, S < 0, N outside 1 .. 6, H outside
+ * 1 .. 128, app_dim outside 0 .. cl/2 - 4, lim_enc outside 0 .. cl, B (S + 1) N cl beyond an int: hipErrorInvalidValue, nothing
+ * launched.  B == 0 is a valid empty call; with S == 0 only obs (B, 1, 4N), next_value and status are written (the (B, S) arrays and
+ * z_pred may then be NULL). */
+int stove_ppo_collect_model_cl(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
+                               const float* gnn_params, const float* rh_params, const float* u, float* z_pred, float* pred, float* obs,
+                               int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status,
+                               int cl, int B, int S, int N, int H, int deep, int app_dim, int lim_enc, int elu, float pos_var,
+                               float vel_std, float lat_std, float hw, float discount, void* stream);
+
 /* ---- Stove._3_only_match_objects / _greedy_match_objects / _volatile_match_objects
  * (stove.py:200-329, 432-514, 331-430): the T-serial nearest-neighbour re-ordering of objects.
  * feat (B,T,N,F) matching features in [-1,1] (positions [, appearance]); mode 0 = '3_only',

@@ -102,6 +102,7 @@ def _declare(lib):
         'stove_ppo_param_floats': (S, [I, I, I]),
         'stove_ppo_collect': (I, [P] * 14 + [I] * 7 + [ctypes.c_double] * 5 + [P]),
         'stove_ppo_collect_model': (I, [P] * 18 + [I] * 8 + [F] * 5 + [P]),
+        'stove_ppo_collect_model_cl': (I, [P] * 18 + [I] * 9 + [F] * 5 + [P]),
         'stove_ppo_image_param_floats': (S, [I, I, I]),
         'stove_ppo_collect_images': (I, [P] * 14 + [I] * 10 + [ctypes.c_double] * 5 + [P]),
         'stove_ppo_update': (I, [P] * 14 + [I] * 7 + [F] * 6 + [I, P]),

@@ -43,6 +43,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "env_search.hip"
 #include "ppo_collect.hip"
 #include "ppo_model.hip"
+#include "ppo_model_cl.hip"
 #include "ppo_update.hip"
 #include "ppo_image.hip"
 #include "ppo_image_update.hip"
@@ -191,6 +192,7 @@ extern "C" {
 //     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
 //     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip);
 //     stove_ppo_collect_model -- the model-based PPO arm: a batch of imagined trajectories in one launch (ppo_model.hip);
+//     stove_ppo_collect_model_cl -- the same on models of state-code length 16 and 64 (ppo_model_cl.hip);
 //     stove_ppo_image_param_floats, stove_ppo_collect_images -- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip);
 //     stove_ppo_update_images_ws_bytes, stove_ppo_update_images -- its update, every epoch and mini-batch in one call (ppo_image_update.hip))
 int stove_abi_version(void) { return 7; }
@@ -1737,6 +1739,26 @@ int stove_ppo_collect_model(const float* z0, const float* app, const float* poli
                             (hipStream_t)stream, z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards,
                             values, logp, next_value, returns, status, sh, B, S, N, app_dim, lim_enc, elu, hw, discount, (int)n,
                             pm_staged<NMX>(n) ? 1 : 0);
+  });
+}
+
+// the same at state-code lengths 16 / 64 (ppo_model_cl.hip): one kernel per width, every object count
+int stove_ppo_collect_model_cl(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
+                               const float* gnn_params, const float* rh_params, const float* u, float* z_pred, float* pred, float* obs,
+                               int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status,
+                               int cl, int B, int S, int N, int H, int deep, int app_dim, int lim_enc, int elu, float pos_var, float vel_std,
+                               float lat_std, float hw, float discount, void* stream) {
+  STOVE_VALIDATE(ppo_collect_model_cl(z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, obs, actions, rewards, values,
+                                      logp, next_value, returns, status, B, S, N, H, app_dim, lim_enc, stove_validate::gnn_limits_cl(cl)));
+  if (B == 0) return 0;
+  (void)pos_var; (void)vel_std; (void)lat_std;          // (the scales of the predicted deviations, which this rollout does not put out)
+  const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
+  const size_t n = ppo_policy::param_floats(sh);
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    return STOVE_LAUNCH_LDS(ppo_collect_model_cl_k<CL>, dim3(B), dim3(256), pc_lds_bytes<CL>(n), (hipStream_t)stream, z0, app, policy_params, emb_w,
+                            emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards, values, logp, next_value, returns, status, sh, B,
+                            S, N, app_dim, lim_enc, elu != 0 ? 1 : 0, hw, discount, (int)n, pc_staged<CL>(n) ? 1 : 0);
   });
 }
 

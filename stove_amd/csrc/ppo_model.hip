@@ -16,6 +16,9 @@
 // One trajectory per workgroup: whether it goes on (a value or a logit not finite ends it) is the same for every wave, which all
 // leave the loop at the same place, so every wave meets every barrier.  Plain vector stores only, no atomics; rewards are written
 // and read back (the returns) by the same thread.  One object goes through a kernel of its own on gnn_forward (at the end of the file).
+// This file is the cl = 32 arm.  Models of state-code length 16 and 64 are served by ppo_model_cl.hip (stove_ppo_collect_model_cl): the
+// same chain around gnn_cl.hip's cl_forward<CL>, one kernel per width for every object count; it reuses the constants and pm_dot_rows
+// of this file.
 #include "common.h"
 #include "ppo_policy.h"
 

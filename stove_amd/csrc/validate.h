@@ -316,6 +316,24 @@ inline int ppo_collect_model(const float* z0, const float* app, const float* pol
   if (S > 0 && (null_any(u, z_pred, rewards, values, logp, returns) || actions == nullptr)) return kStoveInvalidValue;
   return 0;
 }
+// ---- stove_ppo_collect_model_cl: the same call on a model of state-code length cl = 16 / 64 (csrc/ppo_model_cl.hip), `k` =
+// gnn_limits_cl(cl): any other cl (32 included: it has the entry point above) has no limits and is refused.  A node's input row [state
+// cl/2 | action embedding 4 | appearance] has to fit cl, so app_dim <= cl/2 - 4; 0 <= lim_enc <= cl; N <= 6 on both counts.
+inline int ppo_collect_model_cl(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
+                                const float* gnn_params, const float* rh_params, const float* u, const float* z_pred, const float* obs,
+                                const int* actions, const float* rewards, const float* values, const float* logp, const float* next_value,
+                                const float* returns, const int* status, int B, int S, int N, int H, int app_dim, int lim_enc,
+                                const GnnLimits& k) {
+  if (S < 0 || N > kEnvMaxObjects || H < 1 || H > kPpoMaxHidden || app_dim < 0 || app_dim > k.hi || k.bad(B, N, k.lo + 4 + app_dim) ||
+      lim_enc < 0 || lim_enc > k.hi)
+    return kStoveInvalidValue;
+  if ((long long)B * ((long long)S + 1) * N * k.hi > 0x7fffffffLL) return kStoveInvalidValue;
+  if (B == 0) return 0;          // (arrays without elements have no address)
+  if (null_any(z0, policy_params, emb_w, emb_b, gnn_params, rh_params, obs, next_value) || status == nullptr) return kStoveInvalidValue;
+  if (app_dim > 0 && app == nullptr) return kStoveInvalidValue;
+  if (S > 0 && (null_any(u, z_pred, rewards, values, logp, returns) || actions == nullptr)) return kStoveInvalidValue;
+  return 0;
+}
 
 // ---- stove_ppo_collect_images: `warm` warm-up steps and S steps of B environments of N balls under the image policy of F stacked
 // frames and head width H (csrc/ppo_image.hip).  B == 0 is a valid empty call; with S == 0 only the first window frames (B, F, 3, 32, 32),

@@ -1222,18 +1222,22 @@ def ppo_collect_model(z0, app, params, emb_w, emb_b, gnn_params, rh_params, u, h
     consts (pos_var, vel_std, lat_std); hw the environment's width, which scales the observations.
     out: a dict of the tensors to write into (z_pred (B, S, N, 18) [, pred (B, S, N, 32) with want_pred], obs (B, S + 1, 4N), rewards,
     values, logp, returns (B, S), next_value (B,) float32, actions (B, S), status (B,) int32); None allocates them (zeros).
-    -> that dict; status 3: a value or logit of that trajectory was not finite, nothing of that step or after it was written."""
+    -> that dict; status 3: a value or logit of that trajectory was not finite, nothing of that step or after it was written.
+    A z0 that is 10 or 34 wide is a cl = 16 / 64 model's (stove_ppo_collect_model_cl, csrc/ppo_model_cl.hip): z_pred is as wide, pred
+    cl wide, gnn_params gnn_width(cl)'s image, rh_params that width's block (721 / 10945 floats), app_dim at most cl/2 - 4."""
     op = 'ppo_collect_model'
-    if not isinstance(z0, torch.Tensor) or z0.dim() != 3 or z0.shape[2] != 18:
-        raise ValueError('ops.%s: z0 must be a (B, N, 18) tensor' % op)
+    width = _GNN_WIDTHS.get(2 * (z0.shape[2] - 2)) if isinstance(z0, torch.Tensor) and z0.dim() == 3 else None
+    if width is None:
+        raise ValueError('ops.%s: z0 must be a (B, N, 18) tensor (or (B, N, 10) / (B, N, 34): a cl = 16 / 64 model)' % op)
+    cl = width.cl
     z0, app, emb_w, emb_b, gnn_params, rh_params = _plan_model(op, z0, app, emb_w, emb_b, gnn_params, rh_params)
     B, N, dev = z0.shape[0], z0.shape[1], z0.device
     H, deep = int(hidden), int(bool(deep))
     if not 1 <= N <= 6 or not 1 <= H <= 128:
         raise ValueError('ops.%s: the kernel serves 1 .. 6 objects and head widths 1 .. 128, not N = %d, hidden = %d' % (op, N, H))
     app_dim = app.shape[-1] if app is not None else 0
-    if 20 + app_dim > 32 or not 0 <= int(lim_enc) <= 32:
-        raise ValueError('ops.%s: the cl = 32 model takes 20 + app_dim <= 32 inputs and lim_enc in 0 .. 32' % op)
+    if cl // 2 + 4 + app_dim > cl or not 0 <= int(lim_enc) <= cl:
+        raise ValueError('ops.%s: the cl = %d model takes %d + app_dim <= %d inputs and lim_enc in 0 .. %d' % (op, cl, cl // 2 + 4, cl, cl))
     if tuple(emb_w.shape) != (4 * N, 9):
         raise ValueError('ops.%s: emb_w is %s, nine actions on %d objects need %s' % (op, tuple(emb_w.shape), N, (4 * N, 9)))
     if app is not None:
@@ -1245,9 +1249,10 @@ def ppo_collect_model(z0, app, params, emb_w, emb_b, gnn_params, rh_params, u, h
     S = u.shape[1]
     lib = _lib.load()
     _arg(op, 'params', params, _F32, dev, (ppo_param_floats(N, H, deep),), 'policy')
-    _arg(op, 'gnn_params', gnn_params.reshape(-1), _F32, dev, (int(lib.stove_gnn_param_floats()),), 'model')
-    _arg(op, 'rh_params', rh_params.reshape(-1), _F32, dev, (int(lib.stove_reward_head_param_floats()),), 'model')
-    table = {'z_pred': ((B, S, N, 18), _F32), 'pred': ((B, S, N, 32), _F32), 'obs': ((B, S + 1, 4 * N), _F32), 'actions': ((B, S), _I32),
+    rh_floats = lib.stove_reward_head_param_floats() if width.tuned else lib.stove_reward_head_param_floats_cl(cl)
+    _arg(op, 'gnn_params', gnn_params.reshape(-1), _F32, dev, (int(width.size('stove_gnn_param_floats')),), 'model')
+    _arg(op, 'rh_params', rh_params.reshape(-1), _F32, dev, (int(rh_floats),), 'model')
+    table = {'z_pred': ((B, S, N, cl // 2 + 2), _F32), 'pred': ((B, S, N, cl), _F32), 'obs': ((B, S + 1, 4 * N), _F32), 'actions': ((B, S), _I32),
              'rewards': ((B, S), _F32), 'values': ((B, S), _F32), 'logp': ((B, S), _F32), 'next_value': ((B,), _F32),
              'returns': ((B, S), _F32), 'status': ((B,), _I32)}          # (in the C call's order)
     if not (want_pred if out is None else out.get('pred') is not None):
@@ -1256,9 +1261,9 @@ def ppo_collect_model(z0, app, params, emb_w, emb_b, gnn_params, rh_params, u, h
     with torch.cuda.device(dev):
         out = _outputs(op, out, table, dev, 'batch')
         outs = [ptr(out.get(k)) for k in ('z_pred', 'pred')] + [ptr(out[k]) for k in list(table)[-8:]]
-        check(lib.stove_ppo_collect_model(ptr(z0), ptr(app), ptr(params), ptr(emb_w), ptr(emb_b), ptr(gnn_params), ptr(rh_params), ptr(u), *outs,
-                                          B, S, N, H, deep, app_dim, int(lim_enc), int(bool(elu)), *[float(c) for c in consts], float(hw),
-                                          float(discount), stream()), 'stove_ppo_collect_model')
+        width.call('stove_ppo_collect_model', [ptr(z0), ptr(app), ptr(params), ptr(emb_w), ptr(emb_b), ptr(gnn_params), ptr(rh_params), ptr(u),
+                                               *outs], B, S, N, H, deep, app_dim, int(lim_enc), int(bool(elu)), *[float(c) for c in consts],
+                   float(hw), float(discount), stream())
     return out
 
 

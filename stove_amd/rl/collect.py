@@ -16,6 +16,7 @@ ACTIONS = 9
 BASE0, BASE1 = 128, 32
 OK, NON_FINITE = 0, 3
 KEYS = ('obs', 'actions', 'rewards', 'values', 'logp', 'next_value', 'returns', 'status')
+MODEL_STATE_WIDTHS = (10, 18, 34)          # cl/2 + 2 of the models the model-based arm's kernels serve (cl = 16, 32, 64)
 
 
 def uniforms(B, S, seed):
@@ -108,8 +109,9 @@ class PolicyForest:
     # ------------------------------------------------------------------------------------------------ the model-based arm's policy half
     @staticmethod
     def observe_model(z, hw):
-        """(K, N, 18) float32 model states -> (K, 4N) float32: ppo_policy.h's observe_model, positions (z + 1) / 2 * hw, velocities
-        z / 2 * hw, every operation rounded to float32 on its own, hw rounded once (reference runners.py:241-243)"""
+        """(K, N, 18) float32 model states (10 or 34 wide for a cl = 16 / 64 model: only columns 2 .. 5 are read) -> (K, 4N) float32:
+        ppo_policy.h's observe_model, positions (z + 1) / 2 * hw, velocities z / 2 * hw, every operation rounded to float32 on its
+        own, hw rounded once (reference runners.py:241-243)"""
         z = np.asarray(z, dtype=np.float32)
         hw, one, two = np.float32(hw), np.float32(1), np.float32(2)
         with np.errstate(invalid='ignore', over='ignore'):
@@ -121,10 +123,11 @@ class PolicyForest:
 
     def decide_model(self, z, hw, u):
         """One decision per model state: z (K, N, 18) float32, u (K,) float32 uniforms -> (obs (K, 4N), values (K,), actions (K,) int32,
-        logp (K,) float32, margin (K,) float64): the specification of what stove_ppo_collect_model does between two steps of the model."""
+        logp (K,) float32, margin (K,) float64): the specification of what stove_ppo_collect_model does between two steps of the model.
+        States of a cl = 16 / 64 model, (K, N, 10) / (K, N, 34), are read the same way (stove_ppo_collect_model_cl)."""
         z = np.asarray(z, dtype=np.float32)
-        if z.ndim != 3 or z.shape[1:] != (self.N, 18):
-            raise ValueError('z is %s, the policy reads (K, %d, 18)' % (z.shape, self.N))
+        if z.ndim != 3 or z.shape[1] != self.N or z.shape[2] not in MODEL_STATE_WIDTHS:
+            raise ValueError('z is %s, the policy reads (K, %d, 18) (or 10 / 34 wide)' % (z.shape, self.N))
         u = np.asarray(u)
         if u.dtype != np.float32 or u.shape != (z.shape[0],):
             raise ValueError('u must be a float32 vector of %d uniforms' % z.shape[0])

@@ -4,8 +4,9 @@ avoidance task.  `--device-envs` keeps the batch of environments on the GPU, whe
 (stove_ppo_collect); without it the collection runs on the host (collect.PolicyForest) and only the update uses the device.
 `--use-pretrained-model` trains on trajectories imagined by the learned dynamics model restored from `--checkpoint DIR`, started
 from the states that model infers on the recorded sequences of `--data PKL` (pretrained.load_and_encode; the reference hard-codes
-both paths); on a GPU a batch of imagined trajectories is one launch (stove_ppo_collect_model).  The real environment only scores
-the policy after each update.  `--use-images` is the model-free arm on rendered frames, the baseline the learned model is measured
+both paths); on a GPU a batch of imagined trajectories is one launch (stove_ppo_collect_model) on a cl = 32 model, and on a cl = 16 or
+64 model once `--fused-widths 16,32,64` offers it (stove_ppo_collect_model_cl; without the flag such a model takes the composed loop).
+The real environment only scores the policy after each update.  `--use-images` is the model-free arm on rendered frames, the baseline the learned model is measured
 against: the CNN policy on the task's frame buffer, a batch of trajectories in one launch with `--device-envs`
 (stove_ppo_collect_images), else a composed loop of batched steps; its update is torch autograd, or with `--fused-update` one chain
 of launches on the frames the collection wrote (stove_ppo_update_images).  The reference runs this arm when no
@@ -65,6 +66,9 @@ def parse_args(args):
     parser.add_argument('--device', default=None, help='device of the policy (default: cuda when there is one)')
     parser.add_argument('--checkpoint', default=None, help='run directory of the trained dynamics model (--use-pretrained-model)')
     parser.add_argument('--data', default=None, help='pickle of recorded sequences with actions to start from (--use-pretrained-model)')
+    parser.add_argument('--fused-widths', default=None, metavar='16,32,64', type=lambda v: tuple(int(w) for w in v.split(',')),
+                        help='state-code lengths of the learned model at which the one-launch collection of imagined trajectories is '
+                             'offered (--use-pretrained-model; default: 32 alone)')
     args = parser.parse_args(args)
     assert args.task in ['avoidance', 'maxdist', 'mindist']
     assert not (args.gym and args.use_states)
@@ -121,6 +125,8 @@ def build(args, writer=None):
     runner = PPORunner(env=env, task=task, summary_path=os.path.join(args.summary_dir, args.experiment_id), device=device, agent=agent,
                        actor_critic=actor_critic, num_steps=args.num_steps, batch_size=args.batch_size, discount=0.95, writer=writer,
                        device_envs=bool(args.device_envs))
+    if getattr(args, 'fused_widths', None) is not None:
+        runner.fused_widths = tuple(args.fused_widths)
     return runner, actor_critic
 
 

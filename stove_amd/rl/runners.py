@@ -97,8 +97,12 @@ class PPORunner(Runner):
     def __init__(self, env, task, summary_path=None, device=None, agent=None, actor_critic=None, num_steps=128, batch_size=32, discount=0.99,
                  do_train=True, writer=None, device_envs=None):
         """device_envs: False keeps the environments on the host while the policy is updated on `device`; None / True: they live where
-        the policy lives"""
+        the policy lives.  self.fused_widths (an attribute, mcts_stove.FUSED_WIDTHS = (32,) by default): the state-code lengths of the
+        learned model at which the model-based arm's one-launch collection is offered, as BatchedMCTSHandler.fused_widths is for
+        planning; 16 and 64 are switched on by assigning it"""
         super().__init__(env, task, summary_path, device, agent, actor_critic, num_steps, batch_size, discount, do_train, writer)
+        from ..mcts.mcts_stove import FUSED_WIDTHS
+        self.fused_widths = FUSED_WIDTHS
         self.env_device = self.device if device_envs is None or device_envs else torch.device('cpu')
         if self.env_device.type == 'cuda' and self.device.type != 'cuda':
             raise ValueError('device_envs needs the policy on a GPU')
@@ -294,17 +298,18 @@ class PPORunner(Runner):
 
     # ------------------------------------------------------------------------------------------------ the model-based arm
     def fused_serves_model(self, state_model):
-        """whether stove_ppo_collect_model serves this policy on `state_model`: a device, a policy with a kernel_shape(), a float32
-        cl = 32 action-conditioned model with nine actions on the policy's 1 .. 6 objects"""
+        """whether stove_ppo_collect_model[_cl] serves this policy on `state_model`: a device, a policy with a kernel_shape(), a float32
+        action-conditioned model of a state-code length in self.fused_widths with nine actions on the policy's 1 .. 6 objects"""
         from ..mcts.mcts_stove import BatchedMCTSHandler
         c, shape = state_model.c, self.actor_critic.kernel_shape()
-        return (self.device.type == 'cuda' and shape is not None and not BatchedMCTSHandler._fused_unserved(state_model)
+        return (self.device.type == 'cuda' and shape is not None and not BatchedMCTSHandler._fused_unserved(state_model, self.fused_widths)
                 and bool(c.action_conditioned) and c.action_space == 9 and shape[0] == c.num_obj)
 
     def collect_model(self, state_model, z0, apps, fused=None, u=None):
         """S = num_steps imagined steps from the model states z0 (B, N, 18) with appearances apps (B, N, app_dim) or None -> dict of
         z_pred (B, S, N, 18), obs (B, S + 1, 4N), rewards, values, logp, returns (B, S), next_value (B,) float32, actions (B, S),
-        status (B,) on the runner's device.  u: the (B, S) float32 table of uniforms, drawn from numpy's global stream when None."""
+        status (B,) on the runner's device (states cl/2 + 2 wide on a model of another state-code length).  u: the (B, S) float32
+        table of uniforms, drawn from numpy's global stream when None."""
         B, S = z0.shape[0], self.num_steps
         if u is None:
             u = np.random.random_sample((B, S)).astype(np.float32).clip(max=np.float32(1) - np.float32(2) ** -24)
@@ -313,8 +318,11 @@ class PPORunner(Runner):
             raise ValueError('u is %s, the batch needs %s' % (u.shape, (B, S)))
         serves = self.fused_serves_model(state_model)
         if fused and not serves:
-            raise ValueError('fused=True needs the policy and a float32 cl = 32 action-conditioned model with nine actions on a GPU, and '
-                             'Policy(base="control") on the model\'s 1 .. 6 objects with a head of width 1 .. 128')
+            cl = state_model.c.cl
+            why = '' if cl in self.fused_widths else ' (this model has cl = %d; runner.fused_widths offers 16 and 64)' % cl
+            raise ValueError('fused=True needs the policy and a float32 action-conditioned model of a state-code length in fused_widths = %s '
+                             'with nine actions on a GPU, and Policy(base="control") on the model\'s 1 .. 6 objects with a head of width '
+                             '1 .. 128%s' % (tuple(self.fused_widths), why))
         ut = torch.from_numpy(u).to(self.device)
         z0 = z0.to(self.device).float().contiguous()
         apps = None if apps is None else apps.to(self.device).float().contiguous()

@@ -28,7 +28,9 @@ one process from the same start states and uniforms (writes profiles/ppo_model.j
                 launches) and one insert -- calls that all predate the one-launch collection, which is what makes it the baseline
   fused_ms      the one-launch collection (ops.ppo_collect_model), the policy's and the model's images built included
   fused_launch_ms   ops.ppo_collect_model alone on prepared images
-and per imagined step of a trajectory, fused_launch_ms / 128, as step_us.
+and per imagined step of a trajectory, fused_launch_ms / 128, as step_us.  --cl 16 / 64: the same on a model of that state-code length
+(ops.ppo_collect_model on stove_ppo_collect_model_cl), the runner's fused_widths switched on for it; the result goes under the key
+cl16 / cl64 of profiles/ppo_model_cl.json, beside what the file already holds.
 
     python tools/ppo_time.py --images [--reps 5] [--images-hidden 512] [--images-out profiles/ppo_image.json]
 
@@ -67,7 +69,8 @@ def main():
     ap.add_argument('--update', action='store_true', help='time the update alone: torch against the one-launch update')
     ap.add_argument('--update-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_update.json'))
     ap.add_argument('--model', action='store_true', help='time the model-based collection: the composed loop against the one launch')
-    ap.add_argument('--model-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_model.json'))
+    ap.add_argument('--model-out', default=None, help='default: profiles/ppo_model.json, at --cl 16 / 64 profiles/ppo_model_cl.json')
+    ap.add_argument('--cl', type=int, default=32, choices=(16, 32, 64), help='state-code length of the model of --model')
     ap.add_argument('--images', action='store_true', help='time the collection on images: the composed loop against the one launch')
     ap.add_argument('--images-hidden', type=int, default=512, help='head width of the image policy (main_rl\'s default 512)')
     ap.add_argument('--images-out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_image.json'))
@@ -75,6 +78,9 @@ def main():
     ap.add_argument('--images-update-out',
                     default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'ppo_image_update.json'))
     args = ap.parse_args()
+    if args.model_out is None:
+        args.model_out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                      'ppo_model.json' if args.cl == 32 else 'ppo_model_cl.json')
     build.build_library()
     import numpy as np
     import torch
@@ -107,11 +113,14 @@ def main():
         cfg.num_obj, cfg.width, cfg.height, cfg.debug = 3, 32, 32, True
         cfg.device, cfg.dtype, cfg.random_seed = torch.device(dev), torch.float32, 42
         cfg.action_conditioned, cfg.action_space, cfg.debug_core_appearance = True, 9, True
+        cl = args.cl
+        if cl != 32:
+            cfg.cl, cfg.transition_lik_std = cl, [0.01] * (cl // 2)
         torch.manual_seed(0)
         model = Stove(cfg).to(dev)
         for p in model.parameters():
             p.requires_grad_(False)
-        result['model'] = {'cl': 32, 'num_obj': 3, 'app_dim': 3, 'action_space': 9}
+        result['model'] = {'cl': cl, 'num_obj': 3, 'app_dim': 3, 'action_space': 9}
         for B, S in ((32, 128), (256, 128)):
             torch.manual_seed(0)
             np.random.seed(0)
@@ -120,10 +129,12 @@ def main():
             policy = Policy(12, 9, hidden_size=64, base='control')
             agent = PPOAgent(policy, .1, 4, 32, .5, .01, lr=2e-4, eps=1e-5, max_grad_norm=40)
             runner = PPORunner(env, task, None, dev, agent, policy, num_steps=S, batch_size=B, discount=.95)
+            if cl != 32:
+                runner.fused_widths = (cl,)
             u = np.random.random_sample((B, S)).astype(np.float32)
             rs = np.random.RandomState(1)
             z = np.concatenate([np.full((B, 3, 2), 0.1), rs.uniform(-0.7, 0.7, (B, 3, 2)), rs.uniform(-0.1, 0.1, (B, 3, 2)),
-                                rs.uniform(-0.5, 0.5, (B, 3, 12))], axis=2).astype(np.float32)
+                                rs.uniform(-0.5, 0.5, (B, 3, cl // 2 - 4))], axis=2).astype(np.float32)
             z0 = torch.from_numpy(z).to(dev)
             apps = torch.from_numpy(rs.uniform(0, 1, (B, 3, 3)).astype(np.float32)).to(dev)
             assert runner.fused_serves_model(model)
@@ -143,6 +154,10 @@ def main():
             result['batches']['%dx%d' % (B, S)] = row
             print('%dx%d' % (B, S), json.dumps(row), flush=True)
         os.makedirs(os.path.dirname(args.model_out), exist_ok=True)
+        if cl != 32:                                             # one file for the widths other than 32, a key per width
+            whole = json.load(open(args.model_out)) if os.path.isfile(args.model_out) else {}
+            whole['cl%d' % cl] = result
+            result = whole
         with open(args.model_out, 'w') as fh:
             json.dump(result, fh, indent=1, sort_keys=True)
         return
