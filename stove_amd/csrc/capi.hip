@@ -1718,6 +1718,30 @@ int stove_ppo_collect(double* x, double* v, const double* r, const double* m, co
 }
 
 // ---------------------------------------------------------------- the model-based PPO arm: imagined trajectories in one launch (ppo_model.hip)
+// the launch of both entry points on a validated argument block: cl = 32 on the small-graph step (one object on gnn_forward), cl = 16 /
+// 64 on cl_forward (ppo_model_cl.hip), one kernel per width for every object count
+static int ppo_collect_model_launch(int cl, PmArgs A, float pos_var, float vel_std, float lat_std, void* stream) {
+  if (A.B == 0) return 0;
+  (void)pos_var; (void)vel_std; (void)lat_std;          // (the scales of the predicted deviations, which this rollout does not put out)
+  const size_t n = ppo_policy::param_floats(A.sh);
+  A.n_params = (int)n;
+  const dim3 grid(A.B), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (cl != 32)
+    return with_cl(cl, [&](auto w) {
+      constexpr int CL = decltype(w)::value;
+      A.staged = pc_staged<CL>(n) ? 1 : 0;
+      return STOVE_LAUNCH_LDS(ppo_collect_model_cl_k<CL>, grid, block, pc_lds_bytes<CL>(n), st, PM_LAUNCH_ARGS(A));
+    });
+  if (!small_graph(A.N))          // one object: gnn_forward's arithmetic, as stove_rollout_fwd steps it
+    return STOVE_LAUNCH_LDS(ppo_collect_model_one_k, grid, block, kPm1LdsBytes, st, PM_LAUNCH_ARGS(A));
+  return with_small_graph<false>(A.N, A.elu != 0, false, [&](auto nmx, auto e, auto nt) {
+    constexpr int NMX = decltype(nmx)::value;
+    A.staged = pm_staged<NMX>(n) ? 1 : 0;
+    return STOVE_LAUNCH_LDS((ppo_collect_model_k<NMX, decltype(e)::value, decltype(nt)::value>), grid, block, pm_lds_bytes<NMX>(n), st, PM_LAUNCH_ARGS(A));
+  });
+}
+
 int stove_ppo_collect_model(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
                             const float* gnn_params, const float* rh_params, const float* u, float* z_pred, float* pred, float* obs,
                             int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status, int B,
@@ -1725,24 +1749,13 @@ int stove_ppo_collect_model(const float* z0, const float* app, const float* poli
                             float hw, float discount, void* stream) {
   STOVE_VALIDATE(ppo_collect_model(z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, obs, actions, rewards, values, logp,
                                    next_value, returns, status, B, S, N, H, app_dim, lim_enc));
-  if (B == 0) return 0;
-  (void)pos_var; (void)vel_std; (void)lat_std;          // (the scales of the predicted deviations, which this rollout does not put out)
-  const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
-  const size_t n = ppo_policy::param_floats(sh);
-  if (!small_graph(N))          // one object: gnn_forward's arithmetic, as stove_rollout_fwd steps it
-    return STOVE_LAUNCH_LDS(ppo_collect_model_one_k, dim3(B), dim3(256), kPm1LdsBytes, (hipStream_t)stream, z0, app, policy_params, emb_w, emb_b,
-                            gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards, values, logp, next_value, returns, status, sh, B, S,
-                            app_dim, lim_enc, elu != 0 ? 1 : 0, hw, discount);
-  return with_small_graph<false>(N, elu != 0, false, [&](auto nmx, auto e, auto nt) {
-    constexpr int NMX = decltype(nmx)::value;
-    return STOVE_LAUNCH_LDS((ppo_collect_model_k<NMX, decltype(e)::value, decltype(nt)::value>), dim3(B), dim3(64 * kSmWaves), pm_lds_bytes<NMX>(n),
-                            (hipStream_t)stream, z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards,
-                            values, logp, next_value, returns, status, sh, B, S, N, app_dim, lim_enc, elu, hw, discount, (int)n,
-                            pm_staged<NMX>(n) ? 1 : 0);
-  });
+  return ppo_collect_model_launch(32, PmArgs{z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards,
+                                             values, logp, next_value, returns, status, {N, H, deep != 0 ? 1 : 0}, B, S, N, app_dim, lim_enc,
+                                             elu != 0 ? 1 : 0, hw, discount, 0, 0},
+                                  pos_var, vel_std, lat_std, stream);
 }
 
-// the same at state-code lengths 16 / 64 (ppo_model_cl.hip): one kernel per width, every object count
+// the same at state-code lengths 16 / 64
 int stove_ppo_collect_model_cl(const float* z0, const float* app, const float* policy_params, const float* emb_w, const float* emb_b,
                                const float* gnn_params, const float* rh_params, const float* u, float* z_pred, float* pred, float* obs,
                                int* actions, float* rewards, float* values, float* logp, float* next_value, float* returns, int* status,
@@ -1750,16 +1763,10 @@ int stove_ppo_collect_model_cl(const float* z0, const float* app, const float* p
                                float lat_std, float hw, float discount, void* stream) {
   STOVE_VALIDATE(ppo_collect_model_cl(z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, obs, actions, rewards, values,
                                       logp, next_value, returns, status, B, S, N, H, app_dim, lim_enc, stove_validate::gnn_limits_cl(cl)));
-  if (B == 0) return 0;
-  (void)pos_var; (void)vel_std; (void)lat_std;          // (the scales of the predicted deviations, which this rollout does not put out)
-  const ppo_policy::Shape sh{N, H, deep != 0 ? 1 : 0};
-  const size_t n = ppo_policy::param_floats(sh);
-  return with_cl(cl, [&](auto w) {
-    constexpr int CL = decltype(w)::value;
-    return STOVE_LAUNCH_LDS(ppo_collect_model_cl_k<CL>, dim3(B), dim3(256), pc_lds_bytes<CL>(n), (hipStream_t)stream, z0, app, policy_params, emb_w,
-                            emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards, values, logp, next_value, returns, status, sh, B,
-                            S, N, app_dim, lim_enc, elu != 0 ? 1 : 0, hw, discount, (int)n, pc_staged<CL>(n) ? 1 : 0);
-  });
+  return ppo_collect_model_launch(cl, PmArgs{z0, app, policy_params, emb_w, emb_b, gnn_params, rh_params, u, z_pred, pred, obs, actions, rewards,
+                                             values, logp, next_value, returns, status, {N, H, deep != 0 ? 1 : 0}, B, S, N, app_dim, lim_enc,
+                                             elu != 0 ? 1 : 0, hw, discount, 0, 0},
+                                  pos_var, vel_std, lat_std, stream);
 }
 
 // ---------------------------------------------------------------- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip)

@@ -10,7 +10,12 @@
 // Everything is cl wide where it was 32: states N (cl/2 + 2) floats, pred rows cl, the reward head cl-cl-cl / cl-cl/2-cl/4-1.
 // Indices live on the device: a tree with an index out of range (leaf, child range, len_s, any of its A L actions) is flagged by
 // plan_prep_k, rolls out a zero state instead of reading the pool, gets NaN in its q / reward rows and writes no pool slot.
+// The reward head's parameter layout and dots are reward_head.h's (RhCl, rh_dot_t), the embedding of one action is ppo_model_step.h's
+// pm_embed; plan_finish_k's forward is reward_head_fwd_k's arithmetic in its own text, as are the imagined collections'
+// (ppo_model.hip, ppo_model_cl.hip), and the tests hold them all to one another bit for bit.
 #include "common.h"
+#include "ppo_model_step.h"
+#include "reward_head.h"
 
 namespace stove {
 
@@ -40,10 +45,8 @@ __global__ __launch_bounds__(kPlanPrepThreads) void plan_prep_k(const float* __r
     const int e = i % E, r = (i / E) % N, t = (i / (E * N)) % steps, a = i / (E * N * steps);
     float v = 0.0f;
     if (!bad) {
-      if (e < 4) {        // the embedding Linear on a one-hot row, in small_linear_k's order of operations (the same bits)
-        const int act = t == 0 ? a : am[a * L + t - 1], o = r * 4 + e;
-        v = emb_b[o];
-        for (int k = 0; k < A; ++k) v = fmaf(k == act ? 1.0f : 0.0f, emb_w[(size_t)o * A + k], v);
+      if (e < 4) {
+        v = pm_embed(emb_w, emb_b, r * 4 + e, t == 0 ? a : am[a * L + t - 1], A);
       } else {
         v = app[((size_t)m * N + r) * app_dim + (e - 4)];
       }
@@ -51,17 +54,6 @@ __global__ __launch_bounds__(kPlanPrepThreads) void plan_prep_k(const float* __r
     eo[i] = v;
   }
 }
-
-// The reward head's parameter block at state-code length CL: the ten tensors in module order, nn.Linear layout (at CL = 32 the
-// RH_* offsets of reward_head.hip), 2 CL^2 + 2 CL + CL^2/2 + CL/2 + CL^2/8 + CL/4 + CL/4 + 1 floats
-template <int CL>
-struct RhCl {
-  static constexpr int H1 = CL / 2, H2 = CL / 4;
-  static constexpr int W0A = 0, B0A = W0A + CL * CL, W0B = B0A + CL, B0B = W0B + CL * CL, W1A = B0B + CL, B1A = W1A + H1 * CL, W1B = B1A + H1,
-                       B1B = W1B + H2 * H1, W1C = B1B + H2, B1C = W1C + H2, kParams = B1C + 1;
-};
-static_assert(RhCl<32>::kParams == kRhParams && RhCl<32>::W1A == RH_W1A && RhCl<32>::B1C == RH_B1C, "the cl = 32 block is reward_head.hip's");
-static_assert(RhCl<16>::kParams == 721 && RhCl<64>::kParams == 10945, "reward-head block sizes");
 
 // pred (M A, 1 + L, N, CL), z_pred (M A, 1 + L, N, CL/2 + 2) of the rollout -> q (M, A), r_first (M, A), r_roll (M, A, L) (the last two
 // may be NULL) and the state after step 0 of row (m, a) into z_pool[m, child[m] + a].  reward_head_fwd_k's arithmetic, nothing saved:

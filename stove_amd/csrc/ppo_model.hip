@@ -17,14 +17,16 @@
 // leave the loop at the same place, so every wave meets every barrier.  Plain vector stores only, no atomics; rewards are written
 // and read back (the returns) by the same thread.  One object goes through a kernel of its own on gnn_forward (at the end of the file).
 // This file is the cl = 32 arm.  Models of state-code length 16 and 64 are served by ppo_model_cl.hip (stove_ppo_collect_model_cl): the
-// same chain around gnn_cl.hip's cl_forward<CL>, one kernel per width for every object count; it reuses the constants and pm_dot_rows
-// of this file.
+// same chain around gnn_cl.hip's cl_forward<CL>, one kernel per width for every object count.
+// The reward head's layout and dots (RhCl, rh_dot_t, rh_dot_rows: reward_head.h), the constants and the kernels' parameter list
+// (ppo_model_step.h) are shared; the step between two dynamics steps and the reward head's forward are this file's own text, held bit
+// for bit to reward_head.h's rh_forward by the tests: written on shared helpers the launch measured 1 to 1.5 % slower and the cause was
+// not found.
 #include "common.h"
-#include "ppo_policy.h"
+#include "ppo_model_step.h"
 
 namespace stove {
 
-constexpr int kPmObsFloats = 32, kPmHeadFloats = 16, kPmEmbRows = 4 * env_step::kMaxObjects;
 constexpr int kPmRhV = 104;                                        // the reward head's vectors (plan_finish_k's V), padded
 // the launch's LDS beyond the dynamics' (SmShape::kLdsFloats): policy rows, the step's pred rows, the embedding, the reward head's tables
 constexpr int kPmFloats = kPmObsFloats + 2 * ppo_policy::kMaxWidth + kPmHeadFloats + env_step::kMaxObjects * 32 +
@@ -32,8 +34,6 @@ constexpr int kPmFloats = kPmObsFloats + 2 * ppo_policy::kMaxWidth + kPmHeadFloa
 // room for sm_step's and sm_dotw's own arrays (sbuf, sdx, an xb per form of the dot: 3584 bytes in the kernel for six objects), which
 // the compiler places beside the dynamic part
 constexpr size_t kPmStaticBytes = 4096;
-constexpr size_t kPmLdsLimit = 160 * 1024;                          // one CU's LDS, all of which one workgroup may take
-static_assert(4 * env_step::kMaxObjects <= kPmObsFloats && ppo_policy::kHeads <= kPmHeadFloats, "the rows hold the widest case");
 static_assert(ppo_policy::kMaxWidth <= 64 * kSmWaves, "a layer's neurons have a thread each");
 static_assert(kPmFloats % 4 == 0, "the image behind it stays 16-byte aligned");
 
@@ -62,7 +62,8 @@ __device__ __forceinline__ PmLds pm_carve(float* base) {
 }
 
 template <int NMX>
-inline size_t pm_fixed_bytes() { return (size_t)(SmShape<NMX>::kLdsFloats + kPmFloats) * sizeof(float); }
+constexpr size_t pm_fixed_bytes() { return (size_t)(SmShape<NMX>::kLdsFloats + kPmFloats) * sizeof(float); }
+static_assert(pm_fixed_bytes<4>() == 113328 && pm_fixed_bytes<6>() == 118048, "the launch's LDS is part of what `staged` decides");
 // the image is staged when it fits beside everything else
 template <int NMX>
 inline bool pm_staged(size_t n_params) { return pm_fixed_bytes<NMX>() + kPmStaticBytes + n_params * sizeof(float) <= kPmLdsLimit; }
@@ -98,13 +99,7 @@ __device__ __forceinline__ float pm_reward(const PmLds& M, int N, int lane) {
 // emb_w (4N, 9), emb_b (4N); P the dynamics' image; rh the reward head's; u (B, S); z_pred (B, S, N, 18); pred (B, S, N, 32) or null;
 // obs (B, S + 1, 4N); actions, rewards, values, logp, returns (B, S); next_value, status (B,).
 template <int NMX, bool ELU, int NT>
-__global__ __launch_bounds__(64 * kSmWaves) void ppo_collect_model_k(
-    const float* __restrict__ z0, const float* __restrict__ app, const float* __restrict__ params, const float* __restrict__ emb_w,
-    const float* __restrict__ emb_b, const float* __restrict__ P, const float* __restrict__ rh, const float* __restrict__ u,
-    float* __restrict__ z_pred, float* __restrict__ pred, float* __restrict__ obs, int* __restrict__ actions, float* rewards,
-    float* __restrict__ values, float* __restrict__ logp, float* __restrict__ next_value, float* __restrict__ returns,
-    int* __restrict__ status, ppo_policy::Shape sh, int B, int S, int N, int app_dim, int lim_enc, int elu, float hw, float discount,
-    int n_params, int staged) {
+__global__ __launch_bounds__(64 * kSmWaves) void ppo_collect_model_k(PM_KERNEL_PARAMS) {
   constexpr int RP = SmShape<NMX>::RP, ET = SmShape<NMX>::ET;
   static_assert(NT <= NMX, "object count beyond what the kernel is built for");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -124,15 +119,15 @@ __global__ __launch_bounds__(64 * kSmWaves) void ppo_collect_model_k(
   // the reward head's tables, transposed as plan_finish_k keeps them
   for (int i = tid; i < 1024; i += blockDim.x) {
     const int o = i >> 5, k = i & 31;                    // W (out o, in k) -> Wt[k][o]
-    M.Wt0a[k * 32 + o] = rh[RH_W0A + i];
-    M.Wt0b[k * 32 + o] = rh[RH_W0B + i];
+    M.Wt0a[k * 32 + o] = rh[RhCl<32>::W0A + i];
+    M.Wt0b[k * 32 + o] = rh[RhCl<32>::W0B + i];
   }
-  for (int i = tid; i < 512; i += blockDim.x) M.Wt1a[(i & 31) * 16 + (i >> 5)] = rh[RH_W1A + i];
-  for (int i = tid; i < 128; i += blockDim.x) M.Wt1b[(i & 15) * 8 + (i >> 4)] = rh[RH_W1B + i];
-  for (int i = tid; i < 32; i += blockDim.x) { M.V[i] = rh[RH_B0A + i]; M.V[32 + i] = rh[RH_B0B + i]; }
-  for (int i = tid; i < 16; i += blockDim.x) M.V[64 + i] = rh[RH_B1A + i];
-  for (int i = tid; i < 8; i += blockDim.x) { M.V[80 + i] = rh[RH_B1B + i]; M.V[88 + i] = rh[RH_W1C + i]; }
-  if (tid == 0) M.V[96] = rh[RH_B1C];
+  for (int i = tid; i < 512; i += blockDim.x) M.Wt1a[(i & 31) * 16 + (i >> 5)] = rh[RhCl<32>::W1A + i];
+  for (int i = tid; i < 128; i += blockDim.x) M.Wt1b[(i & 15) * 8 + (i >> 4)] = rh[RhCl<32>::W1B + i];
+  for (int i = tid; i < 32; i += blockDim.x) { M.V[i] = rh[RhCl<32>::B0A + i]; M.V[32 + i] = rh[RhCl<32>::B0B + i]; }
+  for (int i = tid; i < 16; i += blockDim.x) M.V[64 + i] = rh[RhCl<32>::B1A + i];
+  for (int i = tid; i < 8; i += blockDim.x) { M.V[80 + i] = rh[RhCl<32>::B1B + i]; M.V[88 + i] = rh[RhCl<32>::W1C + i]; }
+  if (tid == 0) M.V[96] = rh[RhCl<32>::B1C];
   const int W = 4 * N, Ly = ppo_policy::layers(sh);
   for (int i = tid; i < W * ppo_policy::kActions; i += blockDim.x) M.embw[i] = emb_w[i];
   if (tid < W) M.embb[tid] = emb_b[tid];
@@ -232,31 +227,11 @@ __global__ __launch_bounds__(64 * kSmWaves) void ppo_collect_model_k(
 // =================================================================================================
 constexpr int kPm1Floats = kPmObsFloats + 2 * ppo_policy::kMaxWidth + kPmHeadFloats + 32 + 4 * ppo_policy::kActions + 4 + 4;
 constexpr size_t kPm1LdsBytes = (size_t)(kGnnLdsFloats + kPm1Floats) * sizeof(float);
+static_assert(kPm1LdsBytes == 155184, "the launch's LDS");
 static_assert(kPm1LdsBytes + 1024 <= kPmLdsLimit, "gnn_forward's LDS and the policy's rows fit one CU");
 
-// rh_dot_t's sum (the same terms in the same order on the same two chains) on a weight (OUT, K) row-major as the parameter block holds it
-template <int K, int OUT>
-__device__ __forceinline__ float pm_dot_rows(const float* __restrict__ Wm, const float* xs, int l) {
-  float a = 0.0f, b = 0.0f;
-  const int ll = l < OUT ? l : 0;
-#pragma unroll
-  for (int k = 0; k < K; k += 4) {
-    const float4 x4 = *reinterpret_cast<const float4*>(xs + k);
-    a = fmaf(Wm[ll * K + k + 0], x4.x, a);
-    b = fmaf(Wm[ll * K + k + 1], x4.y, b);
-    a = fmaf(Wm[ll * K + k + 2], x4.z, a);
-    b = fmaf(Wm[ll * K + k + 3], x4.w, b);
-  }
-  return a + b;
-}
-
 // grid B, block 256, dynamic LDS kPm1LdsBytes; the arguments of ppo_collect_model_k with N = 1
-__global__ __launch_bounds__(256) void ppo_collect_model_one_k(
-    const float* __restrict__ z0, const float* __restrict__ app, const float* __restrict__ params, const float* __restrict__ emb_w,
-    const float* __restrict__ emb_b, const float* __restrict__ P, const float* __restrict__ rh, const float* __restrict__ u,
-    float* __restrict__ z_pred, float* __restrict__ pred, float* __restrict__ obs, int* __restrict__ actions, float* rewards,
-    float* __restrict__ values, float* __restrict__ logp, float* __restrict__ next_value, float* __restrict__ returns,
-    int* __restrict__ status, ppo_policy::Shape sh, int B, int S, int app_dim, int lim_enc, int elu, float hw, float discount) {
+__global__ __launch_bounds__(256) void ppo_collect_model_one_k(PM_KERNEL_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const GnnLds L = carve(lds);
   float* o = lds + kGnnLdsFloats;
@@ -290,19 +265,19 @@ __global__ __launch_bounds__(256) void ppo_collect_model_one_k(
         const int l = lane & 31;
         const bool lo = lane < 32;
         if (lo) xs[l] = L.PRED[l];
-        float h = rh[RH_B0A + l] + pm_dot_rows<32, 32>(rh + RH_W0A, xs, l);
+        float h = rh[RhCl<32>::B0A + l] + rh_dot_rows<32, 32>(rh + RhCl<32>::W0A, xs, l);
         h = fmaxf(h, 0.0f);
         if (lo) xs[l] = h;
         float h32 = 0.0f;
-        h32 += rh[RH_B0B + l] + pm_dot_rows<32, 32>(rh + RH_W0B, xs, l);
+        h32 += rh[RhCl<32>::B0B + l] + rh_dot_rows<32, 32>(rh + RhCl<32>::W0B, xs, l);
         if (lo) xs[l] = h32;
-        const float a1 = fmaxf(rh[RH_B1A + (l & 15)] + pm_dot_rows<32, 16>(rh + RH_W1A, xs, l), 0.0f);
+        const float a1 = fmaxf(rh[RhCl<32>::B1A + (l & 15)] + rh_dot_rows<32, 16>(rh + RhCl<32>::W1A, xs, l), 0.0f);
         if (lane < 16) xs[l] = a1;
-        const float a2 = fmaxf(rh[RH_B1B + (l & 7)] + pm_dot_rows<16, 8>(rh + RH_W1B, xs, l), 0.0f);
+        const float a2 = fmaxf(rh[RhCl<32>::B1B + (l & 7)] + rh_dot_rows<16, 8>(rh + RhCl<32>::W1B, xs, l), 0.0f);
         if (lane < 8) xs[l] = a2;
-        float z = rh[RH_B1C];
+        float z = rh[RhCl<32>::B1C];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) z = fmaf(rh[RH_W1C + k], xs[k], z);
+        for (int k = 0; k < 8; ++k) z = fmaf(rh[RhCl<32>::W1C + k], xs[k], z);
         const float rw = 1.0f / (1.0f + expf(-z));
         if (lane == 0) rewards[(size_t)b * S + t - 1] = rw - 1.0f;
       }

@@ -13,13 +13,17 @@
 //   reward        plan_finish_k<CL>'s arithmetic on the step's L.PRED rows, minus 1.0f, by wave 3 behind the step (the serial form: reading
 //                 the head's rows a float4 at a time instead changed the launch's time by nothing, DESIGN 4i -- it is not what a step waits for).
 // LDS: GC<64>::kLdsFloats is 147 776 of a CU's 163 840 bytes, so at cl = 64 the reward head's transposed tables (42 KiB) do not fit and
-// its weights are read from global memory in the parameter block's own layout (pm_dot_rows: rh_dot_t's terms in rh_dot_t's order on its
+// its weights are read from global memory in the parameter block's own layout (rh_dot_rows: rh_dot_t's terms in rh_dot_t's order on its
 // two chains); at cl = 16 (76 KB) the tables are staged as plan_finish_k keeps them.
 // One trajectory per workgroup: whether it goes on is the same for every thread, so every thread meets every barrier.  Plain vector
 // stores only, no atomics; rewards are written and read back (the returns) by the same thread.
-// Included from capi.hip after gnn_cl.hip, plan.hip (RhCl) and ppo_model.hip (kPm*, pm_dot_rows).
+// The reward head's layout and dots (RhCl, rh_dot_t, rh_dot_rows: reward_head.h), the constants and the kernel's parameter list
+// (ppo_model_step.h) are shared; the step between two dynamics steps and the reward head's forward (pc_reward) are this file's own
+// text, held bit for bit to reward_head.h's rh_forward by the tests: written on shared helpers a launch measured 4 to 5 % slower at
+// both widths and the cause was not found (the policy block accounted for all of it at cl = 64 and for part of it at cl = 16).
+// Included from capi.hip after gnn_cl.hip, whose GC / ClLds / cl_forward it steps.
 #include "common.h"
-#include "ppo_policy.h"
+#include "ppo_model_step.h"
 
 namespace stove {
 
@@ -38,6 +42,9 @@ struct PcShape {
   // cl_forward places nothing beside the dynamic part today; a KiB is left for what a compiler may
   static_assert(kFixedBytes + 1024 <= kPmLdsLimit, "the step's LDS and the policy's rows fit one CU");
 };
+
+static_assert(PcShape<16>::kFixedBytes == 78720 && PcShape<32>::kFixedBytes == 137328 && PcShape<64>::kFixedBytes == 150896,
+              "the launch's LDS is part of what `staged` decides");
 
 template <int CL>
 struct PcLds {
@@ -89,15 +96,15 @@ __device__ __forceinline__ float pc_reward(const PcLds<CL>& M, const float* pred
   float hsum = 0.0f;
   for (int o = 0; o < N; ++o) {
     if (act) x[l] = pred[o * ld + l];
-    float h = b0a[l] + (ST ? rh_dot_t<CL, CL>(M.Wt0a, x, l) : pm_dot_rows<CL, CL>(rh + R::W0A, x, l));
+    float h = b0a[l] + (ST ? rh_dot_t<CL, CL>(M.Wt0a, x, l) : rh_dot_rows<CL, CL>(rh + R::W0A, x, l));
     h = fmaxf(h, 0.0f);
     if (act) x[l] = h;
-    hsum += b0b[l] + (ST ? rh_dot_t<CL, CL>(M.Wt0b, x, l) : pm_dot_rows<CL, CL>(rh + R::W0B, x, l));
+    hsum += b0b[l] + (ST ? rh_dot_t<CL, CL>(M.Wt0b, x, l) : rh_dot_rows<CL, CL>(rh + R::W0B, x, l));
   }
   if (act) x[l] = hsum;
-  const float a1 = fmaxf(b1a[l & (H1 - 1)] + (ST ? rh_dot_t<CL, H1>(M.Wt1a, x, l) : pm_dot_rows<CL, H1>(rh + R::W1A, x, l)), 0.0f);
+  const float a1 = fmaxf(b1a[l & (H1 - 1)] + (ST ? rh_dot_t<CL, H1>(M.Wt1a, x, l) : rh_dot_rows<CL, H1>(rh + R::W1A, x, l)), 0.0f);
   if (lane < H1) x[l] = a1;
-  const float a2 = fmaxf(b1b[l & (H2 - 1)] + (ST ? rh_dot_t<H1, H2>(M.Wt1b, x, l) : pm_dot_rows<H1, H2>(rh + R::W1B, x, l)), 0.0f);
+  const float a2 = fmaxf(b1b[l & (H2 - 1)] + (ST ? rh_dot_t<H1, H2>(M.Wt1b, x, l) : rh_dot_rows<H1, H2>(rh + R::W1B, x, l)), 0.0f);
   if (lane < H2) x[l] = a2;
   float z = b1c[0];
 #pragma unroll
@@ -109,13 +116,7 @@ __device__ __forceinline__ float pc_reward(const PcLds<CL>& M, const float* pred
 // emb_w (4N, 9), emb_b (4N); P the dynamics' image at CL; rh the reward head's block at CL; u (B, S); z_pred (B, S, N, cl/2 + 2);
 // pred (B, S, N, CL) or null; obs (B, S + 1, 4N); actions, rewards, values, logp, returns (B, S); next_value, status (B,).
 template <int CL>
-__global__ __launch_bounds__(256) void ppo_collect_model_cl_k(
-    const float* __restrict__ z0, const float* __restrict__ app, const float* __restrict__ params, const float* __restrict__ emb_w,
-    const float* __restrict__ emb_b, const float* __restrict__ P, const float* __restrict__ rh, const float* __restrict__ u,
-    float* __restrict__ z_pred, float* __restrict__ pred, float* __restrict__ obs, int* __restrict__ actions, float* rewards,
-    float* __restrict__ values, float* __restrict__ logp, float* __restrict__ next_value, float* __restrict__ returns,
-    int* __restrict__ status, ppo_policy::Shape sh, int B, int S, int N, int app_dim, int lim_enc, int elu, float hw, float discount,
-    int n_params, int staged) {
+__global__ __launch_bounds__(256) void ppo_collect_model_cl_k(PM_KERNEL_PARAMS) {
   using K = GC<CL>;
   using R = RhCl<CL>;
   constexpr int D = K::D, ZW = K::ZW, LDN = K::LDN, LDZ = K::LDZ;

@@ -5,31 +5,14 @@
 // of SURVEY 8 row A8 still running on library GEMMs).  One wave per (sequence, step) item, lane l < 32 = element l of a 32-wide vector; a
 // layer is the input vector through a per-wave LDS scratch, read back as broadcasts, against the lane's weight column / row in LDS.
 // Parameters come packed as the layers' own tensors one after the other (nn.Linear layout, weight (out, in) row-major):
-//   [W0a 1024 | b0a 32 | W0b 1024 | b0b 32 | W1a 512 | b1a 16 | W1b 128 | b1b 8 | W1c 8 | b1c 1]  = kRhParams floats,
-// the gradient comes back in the same layout (per-wave partial sums reduced in a fixed order: bitwise reproducible).
+//   [W0a 1024 | b0a 32 | W0b 1024 | b0b 32 | W1a 512 | b1a 16 | W1b 128 | b1b 8 | W1c 8 | b1c 1]  = kRhParams floats
+// (RhCl<32> of reward_head.h, the one description of the block at every state-code length), the gradient comes back in the same
+// layout (per-wave partial sums reduced in a fixed order: bitwise reproducible).
 #include "common.h"
+#include "reward_head.h"
 
 namespace stove {
 
-constexpr int RH_W0A = 0, RH_B0A = 1024, RH_W0B = 1056, RH_B0B = 2080, RH_W1A = 2112, RH_B1A = 2624, RH_W1B = 2640, RH_B1B = 2768, RH_W1C = 2776,
-              RH_B1C = 2784, kRhParams = 2785;
-constexpr int kRhWaves = 4;
-
-// y[l] = sum_k Wt[k * OUT + l] x[k]  (lane l < OUT), x broadcast from the wave's LDS scratch
-template <int K, int OUT>
-__device__ __forceinline__ float rh_dot_t(const float* Wt, const float* xs, int l) {
-  float a = 0.0f, b = 0.0f;
-#pragma unroll
-  for (int k = 0; k < K; k += 4) {
-    const float4 x4 = *reinterpret_cast<const float4*>(xs + k);
-    const int ll = l < OUT ? l : 0;
-    a = fmaf(Wt[(k + 0) * OUT + ll], x4.x, a);
-    b = fmaf(Wt[(k + 1) * OUT + ll], x4.y, b);
-    a = fmaf(Wt[(k + 2) * OUT + ll], x4.z, a);
-    b = fmaf(Wt[(k + 3) * OUT + ll], x4.w, b);
-  }
-  return a + b;
-}
 // dx[k] = sum_l W[l * K + k] dy[l]  (lane k < K), dy broadcast from the scratch; W row-major (OUT, K)
 template <int K, int OUT>
 __device__ __forceinline__ float rh_dot_n(const float* W, const float* dys, int k) {
@@ -50,20 +33,21 @@ __device__ __forceinline__ float rh_dot_n(const float* W, const float* dys, int 
 __global__ __launch_bounds__(64 * kRhWaves) void reward_head_fwd_k(const float* __restrict__ pred, const float* __restrict__ P, float* __restrict__ reward,
                                                                      float* __restrict__ H0, float* __restrict__ Q, float* __restrict__ A1,
                                                                      float* __restrict__ A2, int items, int N) {
+  using R = RhCl<32>;
   __shared__ __attribute__((aligned(16))) float Wt0a[1024], Wt0b[1024], Wt1a[512], Wt1b[128], V[32 + 32 + 16 + 8 + 8 + 4], xs[kRhWaves][32];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l = lane & 31;
   for (int i = tid; i < 1024; i += blockDim.x) {
     const int o = i >> 5, k = i & 31;                    // W (out o, in k) -> Wt[k][o]
-    Wt0a[k * 32 + o] = P[RH_W0A + i];
-    Wt0b[k * 32 + o] = P[RH_W0B + i];
+    Wt0a[k * 32 + o] = P[R::W0A + i];
+    Wt0b[k * 32 + o] = P[R::W0B + i];
   }
-  for (int i = tid; i < 512; i += blockDim.x) Wt1a[(i & 31) * 16 + (i >> 5)] = P[RH_W1A + i];      // (16, 32) -> [k][16]
-  for (int i = tid; i < 128; i += blockDim.x) Wt1b[(i & 15) * 8 + (i >> 4)] = P[RH_W1B + i];       // (8, 16)  -> [k][8]
+  for (int i = tid; i < 512; i += blockDim.x) Wt1a[(i & 31) * 16 + (i >> 5)] = P[R::W1A + i];      // (16, 32) -> [k][16]
+  for (int i = tid; i < 128; i += blockDim.x) Wt1b[(i & 15) * 8 + (i >> 4)] = P[R::W1B + i];       // (8, 16)  -> [k][8]
   float* b0a = V; float* b0b = V + 32; float* b1a = V + 64; float* b1b = V + 80; float* w1c = V + 88; float* b1c = V + 96;
-  for (int i = tid; i < 32; i += blockDim.x) { b0a[i] = P[RH_B0A + i]; b0b[i] = P[RH_B0B + i]; }
-  for (int i = tid; i < 16; i += blockDim.x) b1a[i] = P[RH_B1A + i];
-  for (int i = tid; i < 8; i += blockDim.x) { b1b[i] = P[RH_B1B + i]; w1c[i] = P[RH_W1C + i]; }
-  if (tid == 0) b1c[0] = P[RH_B1C];
+  for (int i = tid; i < 32; i += blockDim.x) { b0a[i] = P[R::B0A + i]; b0b[i] = P[R::B0B + i]; }
+  for (int i = tid; i < 16; i += blockDim.x) b1a[i] = P[R::B1A + i];
+  for (int i = tid; i < 8; i += blockDim.x) { b1b[i] = P[R::B1B + i]; w1c[i] = P[R::W1C + i]; }
+  if (tid == 0) b1c[0] = P[R::B1C];
   __syncthreads();
   float* x = xs[wv];
   const bool act = lane < 32;
@@ -109,12 +93,13 @@ __global__ __launch_bounds__(64 * kRhWaves) void reward_head_bwd_k(const float* 
                                                                      const float* __restrict__ Q, const float* __restrict__ A1,
                                                                      const float* __restrict__ A2, const float* __restrict__ d_reward,
                                                                      float* __restrict__ d_pred, float* __restrict__ part, int items, int N) {
+  using R = RhCl<32>;
   __shared__ __attribute__((aligned(16))) float W0a[1024], W0b[1024], W1a[512], W1b[128], w1c[8], ds[kRhWaves][32], xs[kRhWaves][32];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l = lane & 31;
-  for (int i = tid; i < 1024; i += blockDim.x) { W0a[i] = P[RH_W0A + i]; W0b[i] = P[RH_W0B + i]; }
-  for (int i = tid; i < 512; i += blockDim.x) W1a[i] = P[RH_W1A + i];
-  for (int i = tid; i < 128; i += blockDim.x) W1b[i] = P[RH_W1B + i];
-  for (int i = tid; i < 8; i += blockDim.x) w1c[i] = P[RH_W1C + i];
+  for (int i = tid; i < 1024; i += blockDim.x) { W0a[i] = P[R::W0A + i]; W0b[i] = P[R::W0B + i]; }
+  for (int i = tid; i < 512; i += blockDim.x) W1a[i] = P[R::W1A + i];
+  for (int i = tid; i < 128; i += blockDim.x) W1b[i] = P[R::W1B + i];
+  for (int i = tid; i < 8; i += blockDim.x) w1c[i] = P[R::W1C + i];
   __syncthreads();
   float* d = ds[wv];
   float* x = xs[wv];
@@ -203,23 +188,23 @@ __global__ __launch_bounds__(64 * kRhWaves) void reward_head_bwd_k(const float* 
   if (act) {
 #pragma unroll
     for (int k = 0; k < 32; ++k) {
-      out[RH_W0A + l * 32 + k] = gW0a[k];
-      out[RH_W0B + l * 32 + k] = gW0b[k];
+      out[R::W0A + l * 32 + k] = gW0a[k];
+      out[R::W0B + l * 32 + k] = gW0b[k];
     }
-    out[RH_B0A + l] = gb0a;
-    out[RH_B0B + l] = gb0b;
+    out[R::B0A + l] = gb0a;
+    out[R::B0B + l] = gb0b;
     if (l < 16) {
 #pragma unroll
-      for (int k = 0; k < 32; ++k) out[RH_W1A + l * 32 + k] = gW1a[k];
-      out[RH_B1A + l] = gb1a;
+      for (int k = 0; k < 32; ++k) out[R::W1A + l * 32 + k] = gW1a[k];
+      out[R::B1A + l] = gb1a;
     }
     if (l < 8) {
 #pragma unroll
-      for (int k = 0; k < 16; ++k) out[RH_W1B + l * 16 + k] = gW1b[k];
-      out[RH_B1B + l] = gb1b;
-      out[RH_W1C + l] = gw1c;
+      for (int k = 0; k < 16; ++k) out[R::W1B + l * 16 + k] = gW1b[k];
+      out[R::B1B + l] = gb1b;
+      out[R::W1C + l] = gw1c;
     }
-    if (l == 0) out[RH_B1C] = gb1c;
+    if (l == 0) out[R::B1C] = gb1c;
   }
 }
 

@@ -72,6 +72,36 @@ def test_model_half_equals_the_existing_rollout_on_the_kernels_actions(name):
     assert np.array_equal(_bits(rewards.cpu().numpy()), _bits(got['rewards']))
 
 
+@pytest.mark.parametrize('name', ['b1_s1_n1_h32', 'b3_s5_n3_h64', 'b5_s6_n6_h128_deep'])
+def test_rewards_equal_the_planning_kernels(name):
+    """Bit for bit, the cl = 32 twin of tests/test_gpu_ppo_model_cl.py's test: the state before every step (b, t) in slot 0 of a pool
+    of M = B S trees, one ops.plan_expand (stove_plan_expand: plan_finish_k<32>) with A = 9, L = 1 and the trajectory's appearance:
+    r_first[m, actions[b, t]] - 1.0f is rewards[b, t], the child state of that action is z_pred[b, t]."""
+    from stove_amd import ops
+    B, S, N, H, deep, app_dim = C.CASES[name][:6]
+    got = C.kernel_run(name)
+    st = C.case_model(name)
+    _, app = C.start(name)
+    before = torch.from_numpy(C.states_before(name, got)[:, :S]).reshape(B * S, N, 18)
+    M, A, cap = B * S, 9, 10
+    pool = torch.full((M, cap, N, 18), float('nan'))
+    pool[:, 0] = before
+    pool = pool.to(DEV)
+    emb_w, emb_b, gnn, rh = C.weights(st)
+    i32 = lambda v: torch.full((M,), v, dtype=torch.int32, device=DEV)                     # noqa: E731
+    acts = torch.from_numpy(np.random.RandomState(32 + N).randint(0, A, (M * A, 1)).astype(np.int32)).to(DEV)
+    apps = None if app is None else app.repeat_interleave(S, 0).contiguous()
+    q, r_first, r_roll = ops.plan_expand(pool, i32(0), i32(1), i32(1), apps, acts, emb_w, emb_b, gnn, rh, 2, 2, st.dyn.use_elu,
+                                         st.dyn.loop_consts(), 0.95, want_rewards=True)
+    torch.cuda.synchronize()
+    chosen = torch.from_numpy(got['actions'].astype(np.int64)).reshape(M)
+    rows = torch.arange(M)
+    want = (r_first.cpu()[rows, chosen] - torch.tensor(1.0, dtype=torch.float32)).numpy().reshape(B, S)
+    assert want.dtype == np.float32 and np.array_equal(_bits(want), _bits(got['rewards']))
+    kids = pool.cpu()[rows, 1 + chosen].numpy().reshape(B, S, N, 18)
+    assert np.array_equal(_bits(kids), _bits(got['z_pred']))
+
+
 # ------------------------------------------------------------------------------------------------ 3. the returns
 @pytest.mark.parametrize('name', list(C.CASES))
 def test_returns_equal_the_runners(name):
