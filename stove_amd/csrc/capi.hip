@@ -600,6 +600,12 @@ constexpr int kLateTableGradGlimpses = 16384;
 // and LDS that kernel leaves free).  Measured in round 2 (B = 256): the SPN backward phase 600 -> 495 us without them, the
 // recursion's backward 470 -> 545 us with them on its SIMDs, the step 3.273 -> 3.254 ms.  (The round-1 placement -- right behind
 // their producer, next to pix / bgspn_bwd -- was a switch until round 5.)
+// Both workgroups must be resident on one CU: the recursion's dynamic LDS (smb_lds_floats<4>, gnn_small_bwd.hip), its 1 KB of
+// static LDS (the waves' exchange rows, gnn_small.hip) and 512 B of allocation granule, plus the table-gradient kernel's tile,
+// within 160 KB.  (Registers: 310 of a SIMD lane's 512 there, in granules of 8, so at most 200 here -- held by the kernel's
+// amdgpu_num_vgpr attribute.)
+static_assert(kTgLdsU + smb_lds_floats<4>() * (int)sizeof(float) + 64 * kSmWaves * (int)sizeof(float) + 512 <= 160 * 1024,
+              "objspn_tablegrad_under_k no longer fits into the LDS that dyn_loop_bwd_small_k<4, ..> leaves free");
 
 // fork_from: see stove_scene_fwd_from (the background chain's inputs -- frames, z, saved, dll -- must be ready in its order)
 int stove_scene_bwd_from(const StoveSpnTables* t, const float* frames, const float* z, int n_frames, int n_obj, int seq_frames,

@@ -748,16 +748,18 @@ __global__ __launch_bounds__(128 * R) void objspn_tablegrad_k(
 // The same three contractions shaped to run UNDERNEATH the recursion's backward (dyn_loop_bwd_small_k: one 4-wave workgroup per
 // CU for ~0.47 ms, 360 of a SIMD's 512 registers, bound by dependent-issue latency while the rest of the chip idles).  A
 // 12-wave workgroup of objspn_tablegrad_k (3 waves x 158 registers per SIMD) cannot be resident next to it, so held back
-// until then it simply ran afterwards; this variant is 4 waves -- ONE per SIMD -- well inside the 152 registers that are left:
+// until then it simply ran afterwards; this variant is 4 waves -- ONE per SIMD -- inside the registers that are left (below):
 // workgroup = one replica (grid.y = R), wave = (side, half); half 0 owns the side's first leaf and sum-weight tiles 0..3,
 // half 1 the second leaf, tiles 4..6 and (side 0) the root: 36 accumulator registers per wave.  With one wave per SIMD
 // nothing hides an MFMA's latency but the wave's own independent accumulators, so the products go tile-innermost (5 / 4
 // independent MFMAs back to back).  Every workgroup stages the whole glimpse tile for its one replica: six times the tile
 // reads of the wide kernel, out of the MALL, at a time when HBM is nearly idle.  Same fixed summation order per output as
 // objspn_tablegrad_k over the same chunk count -> bitwise reproducible (the chunking differs between the two kernels).
+// Registers: the recursion's backward (N <= 4) allocates 310 of a SIMD lane's 512 (256 + 54, in granules of 8), which leaves 200.
+// __launch_bounds__(256, 2) alone would allow 256; amdgpu_num_vgpr(100) is the cap -- on a unified register file the compiler
+// doubles it (vector + accumulation registers), so 200 in all, and the build's resource remark must show no scratch under it.
 template <int R, int S, int G, int K>
-__global__ __launch_bounds__(256, 3) void objspn_tablegrad_under_k(      // <= 168 registers: the recursion's backward (N <= 4) holds at most 306 of a SIMD's 512
-   
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(100))) void objspn_tablegrad_under_k(
     const float* __restrict__ xw, const float* __restrict__ Dscr, const float* __restrict__ Sscr, const float* __restrict__ Rscr,
     const int* __restrict__ scope, float* __restrict__ part_c, float* __restrict__ part_w, float* __restrict__ part_r,
     int n_batches, int n_chunks, const float* __restrict__ scale) {
@@ -791,12 +793,15 @@ __global__ __launch_bounds__(256, 3) void objspn_tablegrad_under_k(      // <= 1
     c_feat[t] = row / S;
     c_row[t] = 2 * scope[(r * 4 + L) * S + row % S];
   }
-  int w_e1[TWH], w_e2[TWH];
+  // float offsets, inside a sum node's [NS][64] block, of this lane's 16 samples of gamma[k] and of E1[j1], E2[j2] of sum-weight row
+  // j2 G + j1 (the blocks' own addresses are wave-uniform)
+  const int o_kk = 16 * kk, o_g = min(rr, K - 1) * 64 + 16 * kk;
+  int o_e1[TWH], o_e2[TWH];
 #pragma unroll
   for (int i = 0; i < TWH; ++i) {
     const int row = min(16 * (half * TWH + i) + rr, G * G - 1);
-    w_e1[i] = K + row % G;
-    w_e2[i] = K + G + row / G;
+    o_e1[i] = (K + row % G) * 64 + 16 * kk;
+    o_e2[i] = (K + G + row / G) * 64 + 16 * kk;
   }
   f4 acc_c[TC], acc_w[TWH], acc_r = f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -804,16 +809,78 @@ __global__ __launch_bounds__(256, 3) void objspn_tablegrad_under_k(      // <= 1
 #pragma unroll
   for (int i = 0; i < TWH; ++i) acc_w[i] = f4{0.0f, 0.0f, 0.0f, 0.0f};
 
+  // ---- the batch loop, software-pipelined.  With one wave per SIMD a global load that stands in front of its consumer costs a
+  // whole L2 / MALL round trip with nothing to switch to, and the loop used to have about thirty of them per batch (the tile's
+  // float4 one by one, every operand group of the sum section and of the root).  Now every operand is requested ahead of the
+  // MFMAs that hide it:
+  //   tile    the NEXT batch's 2 D x 64 floats go into registers (TI float4 per thread, all in flight at once) behind the last
+  //           operand fetch of the sum section, and into LDS behind the closing barrier -- there is no LDS for a second buffer;
+  //   leaf    the NEXT batch's four Dscr float4 are requested with them (the leaf section of this batch is over by then);
+  //   sums    gamma / E1 / E2 (and rho / EA / EB in the root wave, whose four MFMAs per h now ride behind the sum tiles' of the
+  //           same h) of h = 0 are requested at the top of the batch and land under the leaf section's MFMAs, those of h + 1
+  //           in front of the MFMAs of h.
+  // Which products are formed, from what, and the order of every accumulator's MFMAs over batches, h and e are unchanged.
+  constexpr int NT4 = 2 * D * 16, TI = (NT4 + 255) / 256;       // float4 of a tile; per thread (the last one: the first NT4 % 256 threads)
+  const bool wrow = ((threadIdx.x >> 4) & 1) != 0;              // a thread keeps its four samples and its row parity over the copy
+  const bool root = side == 0 && half == 1;
+  float* const tile_dst = tileP + (threadIdx.x >> 4) * LD + 4 * (threadIdx.x & 15);
+  float4 tv[TI], tsc, dn[4];
+  auto tile_fetch = [&](int b) {
+    const float4* src = reinterpret_cast<const float4*>(xw + (size_t)b * (D * 2 * 64));
+#pragma unroll
+    for (int j = 0; j < TI; ++j)
+      if (256 * (j + 1) <= NT4 || (int)threadIdx.x + 256 * j < NT4) tv[j] = src[threadIdx.x + 256 * j];
+    tsc = wrow ? tg_scale4(scale, b * 64 + 4 * (threadIdx.x & 15)) : float4{1.0f, 1.0f, 1.0f, 1.0f};
+  };
+  auto tile_store = [&]() {          // as tg_stage_tile: the w rows times the samples' dL/d root
+#pragma unroll
+    for (int j = 0; j < TI; ++j)          // float4 i = thread + 256 j: row (thread >> 4) + 16 j, one address and 13 constant offsets
+      if (256 * (j + 1) <= NT4 || (int)threadIdx.x + 256 * j < NT4) {
+        float4 v = tv[j];
+        v.x *= tsc.x; v.y *= tsc.y; v.z *= tsc.z; v.w *= tsc.w;
+        *reinterpret_cast<float4*>(tile_dst + j * 16 * LD) = v;
+      }
+    // the batch's 64 scale values go through LDS as well: gamma and rho take them from there.  Threads 16 .. 31 hold exactly
+    // them (w rows, samples 4 (thread & 15) ..)
+    if ((threadIdx.x >> 4) == 1) *reinterpret_cast<float4*>(scl + 4 * (threadIdx.x & 15)) = tsc;
+  };
+  auto leaf_fetch = [&](int b) {
+    const float* dp = Dscr + (size_t)__builtin_amdgcn_readfirstlane((b * R + r) * 4 + L) * (G * 64);      // (wave-uniform: a scalar base)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dn[q] = *reinterpret_cast<const float4*>(dp + o_g + 4 * q);
+  };
+  struct SumIn { float4 g, a[TWH], b[TWH], q, ea, eb; };
+  auto sum_fetch = [&](int b, int h, SumIn& s) {
+    const float* nb = Sscr + (size_t)__builtin_amdgcn_readfirstlane(b * R * 2 + node) * (NS * 64) + 4 * h;
+    s.g = *reinterpret_cast<const float4*>(nb + o_g);
+#pragma unroll
+    for (int i = 0; i < TWH; ++i) {
+      s.a[i] = *reinterpret_cast<const float4*>(nb + o_e1[i]);
+      s.b[i] = *reinterpret_cast<const float4*>(nb + o_e2[i]);
+    }
+    if (root) {
+      const float* rp = Rscr + (size_t)__builtin_amdgcn_readfirstlane(b * R + r) * ((1 + 2 * K) * 64) + 4 * h;
+      s.q = *reinterpret_cast<const float4*>(rp + o_kk);
+      s.ea = *reinterpret_cast<const float4*>(rp + 64 + o_g);
+      s.eb = *reinterpret_cast<const float4*>(rp + (1 + K) * 64 + o_g);
+    }
+  };
+
+  if (c < n_batches) {
+    tile_fetch(c);
+    leaf_fetch(c);
+  }
   for (int b = c; b < n_batches; b += n_chunks) {
-    tg_stage_tile<D, LD, 256>(tileP, xw + (size_t)b * (D * 2 * 64), scale, b * 64);
-    // the batch's 64 scale values go through LDS as well: gamma and rho take them from there (as global loads inside this
-    // one-wave-per-SIMD chain they stretched the kernel 514 -> 570 us)
-    if (threadIdx.x < 16) *reinterpret_cast<float4*>(scl + 4 * threadIdx.x) = tg_scale4(scale, b * 64 + 4 * threadIdx.x);
+    // workgroups differ in their batch counts: nothing is fetched past a workgroup's last batch, which requests its own operands
+    // once more instead (no branch around the requests, and nothing they fill stays live around the loop for it)
+    const int bn = b + n_chunks < n_batches ? b + n_chunks : b;
+    tile_store();
+    const float4 d0 = dn[0], d1 = dn[1], d2 = dn[2], d3 = dn[3];
     __syncthreads();
+    SumIn cur;
+    sum_fetch(b, 0, cur);
     // ---- leaf coefficients of leaf L: A = features of its pixels, B = its gradients
     {
-      const float4* dp = reinterpret_cast<const float4*>(Dscr + (((size_t)(b * R + r) * 4 + L) * G + min(rr, G - 1)) * 64 + 16 * kk);
-      const float4 d0 = dp[0], d1 = dp[1], d2 = dp[2], d3 = dp[3];
       const float dv[16] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w, d2.x, d2.y, d2.z, d2.w, d3.x, d3.y, d3.z, d3.w};
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
@@ -836,43 +903,37 @@ __global__ __launch_bounds__(256, 3) void objspn_tablegrad_under_k(      // <= 1
           for (int t = 0; t < TC; ++t) acc_c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(fv[t][e], dv[4 * h + e], acc_c[t], 0, 0, 0);
       }
     }
-    // ---- this half's sum-node weight tiles: A = E1[j1] E2[j2], B = gamma
-    {
-      const float* nb = Sscr + (size_t)(b * R * 2 + node) * NS * 64 + 16 * kk;
-      const float* gp = nb + min(rr, K - 1) * 64;
+    __builtin_amdgcn_sched_barrier(0);      // (the requests of h = 1 stay behind the leaf section: registers)
+    // ---- this half's sum-node weight tiles: A = E1[j1] E2[j2], B = gamma; behind them, in the root wave (side 0, half 1), the
+    // replica's root weights: A = rho EB[j2], B = EA[j1]
 #pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const float4 g4 = *reinterpret_cast<const float4*>(gp + 4 * h);
-        const float4 s4 = *reinterpret_cast<const float4*>(scl + 16 * kk + 4 * h);
-        const float gv[4] = {g4.x * s4.x, g4.y * s4.y, g4.z * s4.z, g4.w * s4.w};
-        float pr[TWH][4];
+    for (int h = 0; h < 4; ++h) {
+      const float4 s4 = *reinterpret_cast<const float4*>(scl + 16 * kk + 4 * h);
+      const float gv[4] = {cur.g.x * s4.x, cur.g.y * s4.y, cur.g.z * s4.z, cur.g.w * s4.w};
+      float pr[TWH][4];
 #pragma unroll
-        for (int i = 0; i < TWH; ++i) {
-          const float4 a4 = *reinterpret_cast<const float4*>(nb + w_e1[i] * 64 + 4 * h);
-          const float4 b4 = *reinterpret_cast<const float4*>(nb + w_e2[i] * 64 + 4 * h);
-          pr[i][0] = a4.x * b4.x; pr[i][1] = a4.y * b4.y; pr[i][2] = a4.z * b4.z; pr[i][3] = a4.w * b4.w;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int i = 0; i < TWH; ++i)      // (tile 7 of half 1 does not exist: its products are computed and never stored)
-            acc_w[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(pr[i][e], gv[e], acc_w[i], 0, 0, 0);
+      for (int i = 0; i < TWH; ++i) {
+        pr[i][0] = cur.a[i].x * cur.b[i].x; pr[i][1] = cur.a[i].y * cur.b[i].y; pr[i][2] = cur.a[i].z * cur.b[i].z; pr[i][3] = cur.a[i].w * cur.b[i].w;
       }
-    }
-    // ---- root weights of the replica (side 0, half 1): A = rho EB[j2], B = EA[j1]
-    if (side == 0 && half == 1) {
-      const float* rp = Rscr + (size_t)(b * R + r) * (1 + 2 * K) * 64 + 16 * kk;
-      const float4* rho = reinterpret_cast<const float4*>(rp);
-      const float4* ea = reinterpret_cast<const float4*>(rp + (1 + min(rr, K - 1)) * 64);
-      const float4* eb = reinterpret_cast<const float4*>(rp + (1 + K + min(rr, K - 1)) * 64);
+      float ra[4], rb[4];
+      if (root) {
+        ra[0] = cur.q.x * s4.x * cur.eb.x; ra[1] = cur.q.y * s4.y * cur.eb.y; ra[2] = cur.q.z * s4.z * cur.eb.z; ra[3] = cur.q.w * s4.w * cur.eb.w;
+        rb[0] = cur.ea.x; rb[1] = cur.ea.y; rb[2] = cur.ea.z; rb[3] = cur.ea.w;
+      }
+      if (h < 3) {
+        sum_fetch(b, h + 1, cur);
+      } else {
+        tile_fetch(bn);
+        leaf_fetch(bn);
+      }
 #pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const float4 q4 = rho[h], a4 = ea[h], b4 = eb[h];
-        const float4 s4 = *reinterpret_cast<const float4*>(scl + 16 * kk + 4 * h);
-        acc_r = __builtin_amdgcn_mfma_f32_16x16x4f32(q4.x * s4.x * b4.x, a4.x, acc_r, 0, 0, 0);
-        acc_r = __builtin_amdgcn_mfma_f32_16x16x4f32(q4.y * s4.y * b4.y, a4.y, acc_r, 0, 0, 0);
-        acc_r = __builtin_amdgcn_mfma_f32_16x16x4f32(q4.z * s4.z * b4.z, a4.z, acc_r, 0, 0, 0);
-        acc_r = __builtin_amdgcn_mfma_f32_16x16x4f32(q4.w * s4.w * b4.w, a4.w, acc_r, 0, 0, 0);
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < TWH; ++i)      // (tile 7 of half 1 does not exist: its products are computed and never stored)
+          acc_w[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(pr[i][e], gv[e], acc_w[i], 0, 0, 0);
+      if (root) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc_r = __builtin_amdgcn_mfma_f32_16x16x4f32(ra[e], rb[e], acc_r, 0, 0, 0);
       }
     }
     __syncthreads();      // the LDS images are restaged for the next batch
@@ -1111,6 +1172,10 @@ int objspn_backward_data(const float* xw, const int* scope, const int* leaf_slot
   return 0;
 }
 
+// dynamic LDS of objspn_tablegrad_under_k: the glimpse tile [2 x 100 rows][68] and the batch's 64 scale values.  It has to fit into
+// a CU's 160 KB NEXT TO the recursion's backward: checked where both sizes are known (csrc/capi.hip, at kLateTableGradGlimpses)
+constexpr int kTgLdsU = (2 * 100 * 68 + 64) * (int)sizeof(float);
+
 // scratch: objspn_scratch_floats(n) from objspn_backward_data (scale == nullptr) or from objspn_forward_unit (scale = the
 // upstream gradient per sample: a multiple of 64 floats, zeros beyond sample n); partial: objspn_partial_floats()
 int objspn_backward_params(const float* xw, const int* scope, float* g_coef, float* g_wsum, float* g_wroot, const float* scratch,
@@ -1131,7 +1196,6 @@ int objspn_backward_params(const float* xw, const int* scope, float* g_coef, flo
   int chunks = nb < kObjChunks ? nb : kObjChunks;
   if (under) {
     // one resident round next to the recursion's workgroups: 6 workgroups (replicas) per chunk, one per CU
-    constexpr int kTgLdsU = (2 * 100 * 68 + 64) * (int)sizeof(float);      // + the recursion's 106 880 B + 512 B < 160 KB
     if (chunks > kObjChunks / 6) chunks = (kObjChunks / 6) & ~7;      // 40: a multiple of 8 (XCD-aware placement), 240 workgroups
     int rc = (int)hipFuncSetAttribute((const void*)objspn_tablegrad_under_k<6, 25, 10, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, kTgLdsU);
     if (rc) return rc;
