@@ -609,6 +609,31 @@ int stove_rollout_bwd_cl(const float* z_last, const float* extra, const float* p
                          float* g_params, void* ws, int cl, int B, int num, int A, int N, int sin_dim, int lim_enc, int elu,
                          float pos_var, float vel_std, float lat_std, void* stream);
 
+/* ---- The state-supervised baseline (csrc/gnn_sup.hip; reference model/supairvised): the interaction network on given object states
+ * (x, y, vx, vy) at cl = 16 or 64, 1 <= N <= 6, V >= 1 observed frames, R >= 1 predicted ones.  With core = the GNN step on a cl-wide
+ * code (sin_dim = cl, lim_enc = 4; params: the stove_gnn_param_floats_cl(cl) image that stove_rollout_fwd_cl takes):
+ *   code_0 = [x[:, 0] | latent0];   warm-up i = 1..V-1: code_i = [x[:, i] | core(code_{i-1})[..., 4:]];
+ *   rollout k = 0..R-1: res = core(cur), cur = [res[..., :2] + cur[..., :2] | res[..., 2:]], pred[:, k] = cur[..., :4].
+ * stove_sup_rollout_fwd: x (B,V,N,4), latent0 (B,N,cl-4) -> pred (B,R,N,4) in one launch; codes (B,V-1+R,N,cl), optional, receives
+ * the input code of every step, which is what the backward recomputes from.
+ * stove_sup_rollout_bwd: d_pred (B,R,N,4) -> g_params (stove_gnn_grad_floats_cl(cl) floats) and d_latent0 (B,N,cl-4) (optional),
+ * every element overwritten; x gets no gradient.  One launch over the steps in reverse plus the fixed-order reduction of the
+ * per-workgroup weight gradients (no atomics: two calls agree bit for bit); ws: stove_sup_rollout_bwd_ws_bytes(cl, B, N) bytes, 0 for
+ * what the call rejects.
+ * stove_sup_loss: pred, future (B,R,N,4) -> losses[3] = (total, pred, delta) with, over the columns < end (2 or 4) and M = B N end,
+ * pred = sum_t discount^(t+1) sum (pred_t - future_t)^2 / M and, with_delta != 0, delta = sum_{t<R-1} 6 discount^(t+1)
+ * sum ((pred_{t+1} - pred_t) - (future_{t+1} - future_t))^2 / M; d_pred (B,R,N,4) = d total / d pred, zeros in the columns >= end.
+ * One launch in one workgroup, summed in a fixed order; B, R >= 1.
+ * B == 0 is a valid empty rollout call (the backward then zeroes g_params).  A NULL required pointer, any other cl, N, V, R or end, or
+ * a NULL ws: hipErrorInvalidValue, nothing launched. */
+int stove_sup_rollout_fwd(const float* x, const float* latent0, const float* params, float* pred, float* codes, int cl, int B, int V,
+                          int R, int N, int elu, void* stream);
+size_t stove_sup_rollout_bwd_ws_bytes(int cl, int B, int N);
+int stove_sup_rollout_bwd(const float* x, const float* params, const float* codes, const float* d_pred, float* d_latent0,
+                          float* g_params, void* ws, int cl, int B, int V, int R, int N, int elu, void* stream);
+int stove_sup_loss(const float* pred, const float* future, float* losses, float* d_pred, int B, int R, int N, int end, int with_delta,
+                   double discount, void* stream);
+
 /* ---- Planning at state-code lengths other than 32 (csrc/plan.hip, csrc/plan_tree.hip): stove_plan_expand and stove_plan_search with
  * every width derived from cl = 16 or 64 -- z_pool (M, cap, N, cl/2 + 2); gnn_params the stove_gnn_param_floats_cl(cl) image that
  * stove_rollout_fwd_cl takes, which is the rollout behind these calls (child states bit for bit its z_pred); a node's input row is

@@ -117,6 +117,10 @@ def _declare(lib):
         'stove_dynloop_bwd_cl': (I, [P] * 18 + [I] * 7 + [F] * 3 + [P]),
         'stove_rollout_fwd_cl': (I, [P] * 6 + [I] * 8 + [F] * 3 + [P]),
         'stove_rollout_sample_fwd_cl': (I, [P] * 8 + [I] * 8 + [F] * 3 + [P]),
+        'stove_sup_rollout_fwd': (I, [P] * 5 + [I] * 6 + [P]),
+        'stove_sup_rollout_bwd_ws_bytes': (S, [I, I, I]),
+        'stove_sup_rollout_bwd': (I, [P] * 7 + [I] * 6 + [P]),
+        'stove_sup_loss': (I, [P] * 4 + [I] * 5 + [ctypes.c_double, P]),
         'stove_match_objects': (I, [P, P, P, I, I, I, I, I, P]),
         'stove_profile_enable': (None, [I]),
         'stove_lstm_cell_fwd': (I, [P, P, P, P, P, I, I, I, P]),

@@ -29,6 +29,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "gnn_small.hip"
 #include "gnn_small_bwd.hip"
 #include "gnn_cl.hip"
+#include "gnn_sup.hip"
 #include "lstm.hip"
 #include "arena.hip"
 #include "state.hip"
@@ -194,7 +195,9 @@ extern "C" {
 //     stove_ppo_collect_model -- the model-based PPO arm: a batch of imagined trajectories in one launch (ppo_model.hip);
 //     stove_ppo_collect_model_cl -- the same on models of state-code length 16 and 64 (ppo_model_cl.hip);
 //     stove_ppo_image_param_floats, stove_ppo_collect_images -- the PPO arm on images: a batch of trajectories in one launch (ppo_image.hip);
-//     stove_ppo_update_images_ws_bytes, stove_ppo_update_images -- its update, every epoch and mini-batch in one call (ppo_image_update.hip))
+//     stove_ppo_update_images_ws_bytes, stove_ppo_update_images -- its update, every epoch and mini-batch in one call (ppo_image_update.hip);
+//     stove_sup_rollout_fwd, stove_sup_rollout_bwd_ws_bytes, stove_sup_rollout_bwd, stove_sup_loss -- the state-supervised baseline:
+//     teacher-forced warm-up and rollout in one launch each way, and its discounted loss (gnn_sup.hip))
 int stove_abi_version(void) { return 7; }
 
 const char* stove_error_string(int code) { return hipGetErrorString((hipError_t)code); }
@@ -1313,6 +1316,46 @@ int stove_rollout_bwd_cl(const float* z_last, const float* extra, const float* p
     STOVE_LAUNCH_CHECK();
     return 0;
   });
+}
+
+// ---------------------------------------------------------------- state-supervised baseline (gnn_sup.hip)
+int stove_sup_rollout_fwd(const float* x, const float* latent0, const float* params, float* pred, float* codes, int cl, int B, int V,
+                          int R, int N, int elu, void* stream) {
+  STOVE_VALIDATE(sup_rollout_fwd(x, latent0, params, pred, cl, B, V, R, N));
+  if (B == 0) return 0;
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    return STOVE_LAUNCH_LDS(gnn_sup_rollout_k<CL>, dim3(cl_blocks<CL>(B, N)), dim3(256), SupC<CL>::kLdsFloats * sizeof(float), (hipStream_t)stream,
+                            x, latent0, params, pred, codes, B, V, R, N, cl_group_for<CL>(B, N), elu);
+  });
+}
+
+size_t stove_sup_rollout_bwd_ws_bytes(int cl, int B, int N) { return stove_gnn_bwd_ws_bytes_cl(cl, B, N); }
+
+int stove_sup_rollout_bwd(const float* x, const float* params, const float* codes, const float* d_pred, float* d_latent0,
+                          float* g_params, void* ws, int cl, int B, int V, int R, int N, int elu, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  STOVE_VALIDATE(sup_rollout_bwd(x, params, codes, d_pred, g_params, ws, cl, B, V, R, N));
+  return with_cl(cl, [&](auto w) {
+    constexpr int CL = decltype(w)::value;
+    using K = GC<CL>;
+    if (B == 0) return (int)hipMemsetAsync(g_params, 0, K::kGrads * sizeof(float), st);
+    const int nb = cl_blocks<CL>(B, N);
+    int rc = STOVE_LAUNCH_LDS(gnn_sup_rollout_bwd_k<CL>, dim3(nb), dim3(256), SupC<CL>::kLdsFloats * sizeof(float), st, params, codes, d_pred,
+                              d_latent0, (float*)ws, B, V, R, N, cl_group_for<CL>(B, N), elu);
+    if (rc) return rc;
+    STOVE_LAUNCH(reduce_chunks_k, dim3((K::kGrads + 31) / 32), dim3(256), 0, st, (const float*)ws, g_params, K::kGrads, nb, 0);
+    STOVE_LAUNCH_CHECK();
+    return 0;
+  });
+}
+
+int stove_sup_loss(const float* pred, const float* future, float* losses, float* d_pred, int B, int R, int N, int end, int with_delta,
+                   double discount, void* stream) {
+  STOVE_VALIDATE(sup_loss(pred, future, losses, d_pred, B, R, N, end));
+  STOVE_LAUNCH(sup_loss_k, dim3(1), dim3(kSupLossThreads), 0, (hipStream_t)stream, pred, future, losses, d_pred, B, R, N, end, with_delta, discount);
+  STOVE_LAUNCH_CHECK();
+  return 0;
 }
 
 // ---------------------------------------------------------------- flat parameter arena

@@ -197,6 +197,30 @@ inline int rollout_bwd(const float* z_last, const float* extra, const float* par
   return (null_any(z_last, params, z_pred) || ws == nullptr) ? kStoveInvalidValue : 0;
 }
 
+// ---- the state-supervised baseline (stove_sup_*, csrc/gnn_sup.hip): V observed frames of N objects, R predicted ones, on the
+// width-generic core (cl = 16 / 64, N <= 6).  B == 0 is a valid empty rollout (the backward then zeroes g_params); codes and d_latent0
+// are optional; the loss has no empty call (a mean over nothing).
+inline bool sup_dims_bad(int cl, int B, int V, int R, int N) {
+  if (gnn_limits_cl(cl).bad(B, N, cl) || V < 1 || R < 1) return true;
+  return (long long)V + R - 1 > 0x7fffffffLL;        // (the number of steps is an int)
+}
+inline int sup_rollout_fwd(const float* x, const float* latent0, const float* params, const float* pred, int cl, int B, int V, int R, int N) {
+  if (sup_dims_bad(cl, B, V, R, N)) return kStoveInvalidValue;
+  if (B == 0) return 0;
+  return null_any(x, latent0, params, pred) ? kStoveInvalidValue : 0;
+}
+inline int sup_rollout_bwd(const float* x, const float* params, const float* codes, const float* d_pred, const float* g_params,
+                           const void* ws, int cl, int B, int V, int R, int N) {
+  if (sup_dims_bad(cl, B, V, R, N) || g_params == nullptr) return kStoveInvalidValue;
+  if (B == 0) return 0;
+  return (null_any(x, params, codes, d_pred) || ws == nullptr) ? kStoveInvalidValue : 0;
+}
+inline int sup_loss(const float* pred, const float* future, const float* losses, const float* d_pred, int B, int R, int N, int end) {
+  if (B < 1 || R < 1 || N < 1 || N > kMaxObjectsCl || (end != 2 && end != 4)) return kStoveInvalidValue;
+  if ((long long)B * R * N * 4 > 0x7fffffffLL) return kStoveInvalidValue;          // (the entries are counted in int)
+  return null_any(pred, future, losses, d_pred) ? kStoveInvalidValue : 0;
+}
+
 // ---- stove_plan_expand: one expansion of M search trees (csrc/plan.hip).  Everything the host can see; the indices themselves
 // (leaf, child, len_s, acts) are device memory and are checked by the kernels.  The rollout behind it is the one of the state-code
 // length: `k` = kGnn32 (stove_plan_expand) or gnn_limits_cl(cl) (stove_plan_expand_cl: cl = 16 / 64, N <= 6); a node's input row

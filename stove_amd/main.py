@@ -45,9 +45,13 @@ def build_config(sh_args=None, restore=None, extras=None):
         if extra is not None:
             update.update(extra)
     if str_to_attr(update.get('supairvised', False)):
-        raise NotImplementedError('the supervised ablation (reference model/supairvised) is out of scope')
-    from .video_prediction.config import StoveConfig
+        from .supairvised.config import SupStoveConfig as StoveConfig
+    else:
+        from .video_prediction.config import StoveConfig
     config = load_args(StoveConfig(), update)
+    if config.supairvised and config.load_encoder is not None:
+        from .supairvised.supstove import NO_SUPERVISOR
+        raise NotImplementedError(NO_SUPERVISOR)
     torch.set_num_threads(config.max_threads)
     if isinstance(config.dtype, str):
         config.dtype = eval(config.dtype)
@@ -79,7 +83,10 @@ def restore_model(restore, extras=None, config=None, load=True):
         extras = dict(extras or {})
         extras.setdefault('nolog', True)
         config = build_config(restore=restore, extras=extras)
-    from .video_prediction.stove import Stove
+    if config.supairvised:
+        from .supairvised.supstove import SupStove as Stove
+    else:
+        from .video_prediction.stove import Stove
     stove = Stove(config).to(config.device).type(config.dtype)
     if load and stove.c.checkpoint_path is not None:
         ckpt = torch.load(stove.c.checkpoint_path, map_location=stove.c.device)
@@ -93,5 +100,8 @@ def main(sh_args=None, restore=None, extras=None):
     test_dataset = StoveDataset(config, test=True)
     config = load_args(config, train_dataset.data_info)
     stove = restore_model(restore, extras, config, load=False)
-    from .video_prediction.train import Trainer
+    if config.supairvised:
+        from .supairvised.train import SupTrainer as Trainer
+    else:
+        from .video_prediction.train import Trainer
     return Trainer(config, stove, train_dataset, test_dataset)

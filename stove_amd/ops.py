@@ -993,6 +993,99 @@ def rollout(z_last, extra, image, num, lim_enc, elu, consts, want_std=False, wan
     return out[:3] if eps is None else out
 
 
+class _SupRolloutFn(torch.autograd.Function):
+    """The state-supervised rollout (csrc/gnn_sup.hip), one launch for the V - 1 teacher-forced and the R free steps each way.  The
+    forward keeps every step's input code; the backward recomputes each step from it.  Differentiable: pred -> latent0 and the
+    parameter image; x gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, latent0, w_img, v_img, wt_img, width, num, elu, want_codes, sink=None):
+        x, latent0 = _f32(x), _f32(latent0)
+        B, V, N = x.shape[:3]
+        dev = x.device
+        params = width.image(_f32(w_img), _f32(v_img), _f32(wt_img))
+        grad = want_codes or any(ctx.needs_input_grad)
+        with torch.cuda.device(dev):
+            pred = torch.empty(B, num, N, 4, dtype=torch.float32, device=dev)
+            codes = torch.empty(B, V - 1 + num, N, width.cl, dtype=torch.float32, device=dev) if grad else None
+            check(_lib.load().stove_sup_rollout_fwd(ptr(x), ptr(latent0), ptr(params), ptr(pred), ptr(codes), width.cl, B, V, num, N,
+                                                    int(elu), stream()), 'stove_sup_rollout_fwd')
+        ctx.save_for_backward(x, params, codes)
+        ctx.cfg = (width, num, int(elu))
+        ctx.sink, ctx.flat = sink, v_img is None
+        if codes is None:
+            codes = pred.new_zeros(0)
+        ctx.mark_non_differentiable(codes)
+        return pred, codes
+
+    @staticmethod
+    def backward(ctx, d_pred, _d_codes):
+        x, params, codes = ctx.saved_tensors
+        width, num, elu = ctx.cfg
+        B, V, N = x.shape[:3]
+        dev = x.device
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            d_latent0 = torch.empty(B, N, width.cl - 4, dtype=torch.float32, device=dev)
+            g = torch.empty(width.size('stove_gnn_grad_floats'), dtype=torch.float32, device=dev)
+            ws = _ws(lib.stove_sup_rollout_bwd_ws_bytes(width.cl, B, N), dev)
+            check(lib.stove_sup_rollout_bwd(ptr(x), ptr(params), ptr(codes), ptr(_f32(d_pred)), ptr(d_latent0), ptr(g), ptr(ws), width.cl,
+                                            B, V, num, N, elu, stream()), 'stove_sup_rollout_bwd')
+        if ctx.sink is not None:
+            ctx.sink(g)
+        if ctx.sink is not None or ctx.flat:      # (a prebuilt image is not a leaf of the layers' parameters: the sink is its way back)
+            return (None, d_latent0) + (None,) * 8
+        return (None, d_latent0, *width.split(g)) + (None,) * 6
+
+
+def sup_rollout(x, latent0, image, num_rollout, elu, sink=None, want_codes=False):
+    """State-supervised rollout: x (B,V,N,4) observed states, latent0 (B,N,cl-4) -> pred (B,num_rollout,N,4).  The first V - 1 steps
+    run the core on [x[:, i] | latent carried on], the rest feed the whole cl-wide result back with the position increment added
+    (reference supairvised/dynamics.py with debug_rollout).  `image` / `sink` as for ops.rollout; cl = 16 or 64.
+    want_codes: -> (pred, codes (B,V-1+num_rollout,N,cl)), the input code of every step (no gradient flows through it)."""
+    cl = latent0.shape[-1] + 4
+    if cl not in GNN_CL_WIDTHS:
+        raise NotImplementedError('ops.sup_rollout runs the width-generic kernels, cl in %s; got cl = %d' % (GNN_CL_WIDTHS, cl))
+    B, V, N = x.shape[:3]
+    if tuple(x.shape) != (B, V, N, 4) or tuple(latent0.shape) != (B, N, cl - 4):
+        raise ValueError('ops.sup_rollout: x is %s and latent0 %s, wanted (B, V, N, 4) and (B, N, cl - 4)' % (tuple(x.shape), tuple(latent0.shape)))
+    pred, codes = _SupRolloutFn.apply(x, _sunk(latent0, sink), image[0], image[1], image[2], gnn_width(cl), int(num_rollout), elu,
+                                      bool(want_codes), sink)
+    return (pred, codes) if want_codes else pred
+
+
+class _SupLossFn(torch.autograd.Function):
+    """SupTrainer.compute_loss without its (zero) reconstruction term: the losses and d total / d pred in one launch."""
+
+    @staticmethod
+    def forward(ctx, pred, future, discount, end, with_delta):
+        pred, future = _f32(pred), _f32(future)
+        B, R, N = pred.shape[:3]
+        dev = pred.device
+        with torch.cuda.device(dev):
+            losses = torch.empty(3, dtype=torch.float32, device=dev)
+            d_pred = torch.empty_like(pred)
+            check(_lib.load().stove_sup_loss(ptr(pred), ptr(future), ptr(losses), ptr(d_pred), B, R, N, int(end), int(bool(with_delta)),
+                                             float(discount), stream()), 'stove_sup_loss')
+        ctx.save_for_backward(d_pred)
+        total, pred_loss, delta_loss = losses.unbind(0)
+        ctx.mark_non_differentiable(pred_loss, delta_loss)
+        return total, pred_loss, delta_loss
+
+    @staticmethod
+    def backward(ctx, g_total, _gp, _gd):
+        d_pred, = ctx.saved_tensors
+        return d_pred * g_total, None, None, None, None
+
+
+def sup_loss(pred, future, discount, end=4, with_delta=True):
+    """pred, future (B,R,N,4) -> (total, pred_loss, delta_loss) of the supervised baseline's discounted rollout loss over the columns
+    < end.  Only `total` is differentiable, and only in pred: its backward scales the gradient the forward's launch left."""
+    if pred.shape != future.shape or pred.dim() != 4 or pred.shape[-1] != 4:
+        raise ValueError('ops.sup_loss: pred is %s and future %s, wanted two (B, R, N, 4)' % (tuple(pred.shape), tuple(future.shape)))
+    return _SupLossFn.apply(pred, future.detach(), float(discount), int(end), bool(with_delta))
+
+
 def plan_expand(z_pool, leaf, child, len_s, app, acts, emb_w, emb_b, gnn_params, rh_params, depth, lim_enc, elu, consts, gamma=0.95,
                 want_rewards=False):
     """One expansion of M search trees (stove_plan_expand / stove_plan_expand_cl, csrc/plan.hip; forward only).  z_pool (M, cap, N,

@@ -59,7 +59,10 @@ class Dynamics(nn.Module):
         # anything else (the default 'relu') selects leaky_relu(0.01).  Kept on purpose.
         self.use_elu = self.c.debug_nonlinear == 'leaky_relu'
         self.nonlinear = F.elu if self.use_elu else F.leaky_relu
+        self._init_transition_std()
 
+    def _init_transition_std(self):
+        cl = self.c.cl
         std = list(self.c.transition_lik_std)
         if cl != 32 and len(std) != cl // 2:
             # (the reference pads its 4-entry default to 16 entries, which only fits cl = 32)

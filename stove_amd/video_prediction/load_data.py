@@ -3,7 +3,8 @@
 `data` dicts are what the simulators in stove_amd/envs produce (or the reference's pickles):
 X (episodes, frames, res, res, 3) or already channel-first, y (episodes, frames, n_obj, 4) and, for
 action-conditioned data, action / reward / done.  Labels are rescaled to the model's [-1, 1]
-frame; they only feed error metrics, never the loss.
+frame; they only feed error metrics, never the loss -- except with config.supairvised, where they
+are the supervised baseline's inputs and targets and get the reference's scaling for it.
 """
 import pickle
 
@@ -47,8 +48,16 @@ class StoveDataset(Dataset):
             'num_obj': self.total_data.shape[2], 'num_frames': self.total_data.shape[1]}
         if self.c.debug_add_noise and not test:
             self.total_data += 0.02 / 2 * coord_lim * np.random.normal(size=self.total_data.shape)
-        self.total_data *= 2 / coord_lim                         # positions and velocities to the [-1, 1] frame
-        self.total_data[..., :2] -= 1
+        if getattr(self.c, 'supairvised', False):
+            # the supervised baseline's own scaling (reference load_data.py:101-109): positions to [0, 2], velocities doubled,
+            # frames as one clipped channel sum
+            self.total_data *= 10 / coord_lim
+            self.total_data[..., :2] /= 5
+            self.total_data[..., 2:] *= 2
+            self.total_img = np.expand_dims(np.clip(self.total_img.sum(2), 0, 1), 2)
+        else:
+            self.total_data *= 2 / coord_lim                     # positions and velocities to the [-1, 1] frame
+            self.total_data[..., :2] -= 1
         n_eps, n_frames = self.total_img.shape[:2]
         clip_len = (self.c.num_visible + self.c.num_rollout) * self.c.frame_step
         starts = n_frames - clip_len + 1
