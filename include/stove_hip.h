@@ -422,6 +422,24 @@ int stove_env_sequences(const double* x0, const double* v0, const double* r, con
                         float* frames, int* collisions, int* in_bounds, int* status, int B, int N, int T, int granularity, int res,
                         int use_colors, int drift, int kind, double hw, double t, double friction, double action_force, void* stream);
 
+/* ---- Data synthesis: the starts and action rows of B sequences drawn in one launch (csrc/env_draw.hip, csrc/env_draw.h;
+ * stove_amd/envs/synth.py's draw_starts_counter is the specification).  Sequence b is a pure function of its seed, seed0 + b with seed0 =
+ * seed_hi 2^32 + seed_lo, through Philox4x32-10 counters (stream, attempt, block): NOT the numbers numpy's RandomState gives the host
+ * path, the same distributions.  r (B, N) double, the radii: read only; 1 <= N <= 6.  kind 0, billiards (PhysicsEnv.init_x / init_v):
+ * attempt k draws x = u hw / 2 + hw / 4 and is good iff every ball lies inside [r, hw - r] and no pair is closer than r_i + r_j; the
+ * start is the good attempt with the lowest index among 0 .. max_tries - 1; v is 2 N normals scaled to the norm 0.5, times
+ * uniform(1 / v_factor, v_factor) where v_factor > 0.  kind 1, gravity (GravityEnv.init_x / init_v): x = u 0.9 hw / 2 + hw / 2, good iff
+ * all pairs are farther apart than hw / 3; the lowest good attempt among 0 .. 999, else attempt 999 (max_tries is not consulted); v from
+ * the sign draw and two normals per ball around v_factor.  x0, v0 (B, N, 2) double.  tries (B,): the index of the attempt taken plus one.
+ * actions (B, T) or NULL: MonteCarloActionPolicy(9, 0.2 + 0.1 u)'s row, indices in [0, 9); drawn whatever the status.
+ * status (B,): 0 drawn; 1 no good billiards attempt among max_tries -- x0 and v0 rows zero, tries = max_tries.  Every element of every
+ * output is written.  The values equal the specification's bit for bit (integer arithmetic up to the uniform double, then IEEE double
+ * add, multiply, divide, sqrt, uncontracted; the logarithm is env_draw.h's own).  One launch on `stream`, one wave per sequence, no
+ * synchronisation (the call can be captured), no LDS, no atomics.  A NULL r, x0, v0, tries or status, B < 0, N outside 1 .. 6, T < 0,
+ * max_tries < 1, kind outside {0, 1}: hipErrorInvalidValue, nothing launched.  B == 0 is a valid empty call. */
+int stove_env_draw_starts(const double* r, double* x0, double* v0, int* actions, int* tries, int* status, uint32_t seed_lo,
+                          uint32_t seed_hi, int B, int N, int T, int kind, int max_tries, double hw, double v_factor, void* stream);
+
 /* ---- Tree search on those environments themselves (csrc/env_search.hip, csrc/env_search.h; the host forest EnvForest of
  * stove_amd/mcts/mcts_env.py is the specification): R independent trees per environment, T = M R, tree e R + k searching from
  * environment e's state x, v (M, N, 2), r, m (M, N) double, which is read only.  Nine actions, c = 1, rollout depth D >= 2.  Trees as in

@@ -98,6 +98,7 @@ def _declare(lib):
         'stove_plan_search_cl': (I, [P] * 19 + [I] * 10 + [F] * 4 + [I, P]),
         'stove_env_step': (I, [P] * 8 + [I] * 6 + [ctypes.c_double] * 4 + [P]),
         'stove_env_sequences': (I, [P] * 10 + [I] * 8 + [ctypes.c_double] * 4 + [P]),
+        'stove_env_draw_starts': (I, [P] * 6 + [ctypes.c_uint32] * 2 + [I] * 5 + [ctypes.c_double] * 2 + [P]),
         'stove_env_search': (I, [P] * 15 + [I] * 8 + [ctypes.c_double] * 4 + [P]),
         'stove_ppo_param_floats': (S, [I, I, I]),
         'stove_ppo_collect': (I, [P] * 14 + [I] * 7 + [ctypes.c_double] * 5 + [P]),

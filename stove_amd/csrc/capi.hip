@@ -41,6 +41,7 @@ static_assert(stove_validate::kStoveInvalidValue == (int)hipErrorInvalidValue, "
 #include "render.hip"
 #include "env.hip"
 #include "env_sequences.hip"
+#include "env_draw.hip"
 #include "env_search.hip"
 #include "ppo_collect.hip"
 #include "ppo_model.hip"
@@ -189,6 +190,7 @@ extern "C" {
 //     stove_env_step -- a batch of avoidance / billiards environments stepped and rendered in place (env.hip);
 //     stove_env_search -- tree search on those environments themselves, one launch per planning step (env_search.hip);
 //     stove_env_sequences -- whole training sequences, billiards or gravity, every state and frame in one launch (env_sequences.hip);
+//     stove_env_draw_starts -- their starts and action rows, drawn from a counter-based stream in one launch (env_draw.hip);
 //     stove_render_frames_any -- frames of any size and channel count, with the squared pixel error fused in;
 //     stove_ppo_param_floats, stove_ppo_collect -- the PPO arm: a batch of trajectories on states in one launch (ppo_collect.hip);
 //     stove_ppo_update -- its update, every epoch and mini-batch in one launch (ppo_update.hip);
@@ -1715,6 +1717,22 @@ int stove_env_sequences(const double* x0, const double* v0, const double* r, con
   const env_step::Params p{N, granularity, drift != 0 ? 1 : 0, hw, t, friction, action_force};
   STOVE_LAUNCH(env_sequences_k, dim3(B), dim3(kSeqThreads), 0, (hipStream_t)stream, x0, v0, r, m, actions, y, frames, collisions, in_bounds,
                status, p, T, res, use_colors != 0 ? 1 : 0, kind);
+  STOVE_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- data synthesis: starts and action rows drawn in one launch (env_draw.hip)
+int stove_env_draw_starts(const double* r, double* x0, double* v0, int* actions, int* tries, int* status, uint32_t seed_lo, uint32_t seed_hi,
+                          int B, int N, int T, int kind, int max_tries, double hw, double v_factor, void* stream) {
+  STOVE_VALIDATE(env_draw_starts(r, x0, v0, tries, status, B, N, T, kind, max_tries));
+  if (B == 0) return 0;
+  const uint64_t seed0 = ((uint64_t)seed_hi << 32) | seed_lo;
+  const int rc = with_count<6>(N, [&](auto n) {
+    STOVE_LAUNCH(env_draw_starts_k<decltype(n)::value>, dim3((B + kDrawWaves - 1) / kDrawWaves), dim3(kDrawThreads), 0, (hipStream_t)stream,
+                 r, x0, v0, actions, tries, status, seed0, B, T, kind, max_tries, hw, v_factor);
+    return 0;
+  });
+  if (rc) return rc;
   STOVE_LAUNCH_CHECK();
   return 0;
 }

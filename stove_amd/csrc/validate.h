@@ -289,6 +289,15 @@ inline int env_sequences(const double* x0, const double* v0, const double* r, co
   return (null_any(x0, v0, r, m, y) || null_any(collisions, in_bounds, status)) ? kStoveInvalidValue : 0;
 }
 
+// ---- stove_env_draw_starts: the starts and, with `actions`, the action rows of B sequences of N balls drawn on the device
+// (csrc/env_draw.hip).  B == 0 is a valid empty call; actions is optional, and with T == 0 nothing of it is written.
+inline int env_draw_starts(const double* r, const double* x0, const double* v0, const int* tries, const int* status, int B, int N, int T,
+                           int kind, int max_tries) {
+  if (B < 0 || N < 1 || N > kEnvMaxObjects || T < 0 || kind < 0 || kind > 1 || max_tries < 1) return kStoveInvalidValue;
+  if (B == 0) return 0;          // (arrays without elements have no address)
+  return (null_any(r, x0, v0) || null_any(tries, status)) ? kStoveInvalidValue : 0;
+}
+
 // ---- stove_env_search: R trees per environment searched on M environments of N balls (csrc/env_search.hip).  M == 0 is a valid empty
 // call, and so is runs == 0 (only `action` is written; draws may be NULL).  The table and the trees are device memory and are checked
 // by the kernel (status).

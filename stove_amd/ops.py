@@ -1208,6 +1208,36 @@ def env_sequences(x0, v0, r, m, actions, t_len, granularity, res, hw, t=1.0, fri
     return out
 
 
+def env_draw_starts(r, t_len, seed0, hw, gravity=False, v_factor=0.0, with_actions=False, max_tries=1 << 20, out=None):
+    """The starts and action rows of B sequences drawn in one launch from the counter-based stream (stove_env_draw_starts,
+    csrc/env_draw.hip; synth.draw_starts_counter is the specification).  r (B, N) float64 device tensor, the radii: read only; sequence b
+    has the seed seed0 + b.  v_factor: billiards' init_v_factor (0: none), gravity's factor.  out: dict of tensors to write into (x0, v0
+    (B, N, 2) float64, actions (B, t_len) int32 -- absent or None: no action rows --, tries, status (B,) int32); None allocates them.
+    -> that dict (actions None without with_actions); status 1: none of max_tries billiards attempts was good, zero x0 and v0 rows."""
+    lib = _lib.load()
+    _on_gpu('env_draw_starts', 'r', r, 'synth.draw_starts_counter')
+    _arg('env_draw_starts', 'r', r, _F64, r.device)
+    if r.dim() != 2:
+        raise ValueError('ops.env_draw_starts: r must be (B, N)')
+    (B, N), dev, T, max_tries, seed0 = r.shape, r.device, int(t_len), int(max_tries), int(seed0) & 0xffffffffffffffff
+    if T < 0:
+        raise ValueError('ops.env_draw_starts: t_len must not be negative')
+    if not 1 <= max_tries <= 0x7fffffff:
+        raise ValueError('ops.env_draw_starts: max_tries must be in [1, 2^31)')
+    table = {'x0': ((B, N, 2), _F64), 'v0': ((B, N, 2), _F64), 'actions': ((B, T), _I32), 'tries': ((B,), _I32), 'status': ((B,), _I32)}
+    if not (with_actions if out is None else out.get('actions') is not None):
+        del table['actions']
+    elif gravity:
+        raise ValueError('ops.env_draw_starts: gravity takes no actions')
+    with torch.cuda.device(dev):
+        out = _outputs('env_draw_starts', out, table, dev, 'batch', torch.empty)
+        check(lib.stove_env_draw_starts(ptr(r), ptr(out['x0']), ptr(out['v0']), ptr(out.get('actions')), ptr(out['tries']), ptr(out['status']),
+                                        seed0 & 0xffffffff, seed0 >> 32, B, N, T, int(bool(gravity)), max_tries, float(hw), float(v_factor),
+                                        stream()), 'stove_env_draw_starts')
+    out.setdefault('actions', None)
+    return out
+
+
 def env_search(x, v, r, m, draws, arrays, depth, granularity, hw, t=1.0, friction=0.0, action_force=0.6, drift=False, replicas=1):
     """Tree search on M avoidance environments themselves (stove_env_search, csrc/env_search.hip): `replicas` trees per environment,
     T = M replicas, all draws.shape[1] iterations in one launch, nothing synchronised.  x, v (M, N, 2), r, m (M, N) float64 device
